@@ -6,7 +6,10 @@ over synthetic TPC-H-shaped Arrow columns that are already resident in HBM when 
 the reference's `--mem-table` mode, benchmarks/src/tpch/run.rs:72-74).  value = input rows (customer + orders +
 lineitem) of the whole job / wall time, max over ranks.
 
-Extra objects in the JSON line:
+A plain run sets up, warms up, times --steps steps and prints the result line (--dump-outputs DIR also writes the last timed step's
+result columns).  Everything else it can measure or check runs only with --full.
+
+Extra objects in the JSON line (--full):
   roofline     dominant kernel by device time: algorithmic bytes per launch / average launch duration (HIP events
                recorded on the stream the kernel runs on, through dfgpu_profile_*), against 8 TB/s HBM3E.
   cpu_baseline the oracle's restatement of the same plan (oracle/dfo_tpch.c, "port") timed on this box's host cores
@@ -18,7 +21,7 @@ Extra objects in the JSON line:
                unclustered group-bys, SortExec, the ClickBench Q28 shape, each with ms_per_step, rows_per_s and its roofline figures.
   plans        (N > 1) ms per step of the other two distribution plans, measured after the timed region.
 Output: the LAST stdout line is one compact JSON object (< 8 KB: the contract's keys, roofline, cpu_baseline, result_check.ok, one ms_per_step
-scalar per nested workload); the full result object goes to bench_detail.json next to this file and to stderr.
+scalar per nested workload); with --full the whole result object goes to bench_detail.json next to this file and to stderr.
 Launch for N > 1:  python bench.py --gpus N  starts the N ranks itself (a child torch.distributed.run, before this process touches the GPU);
 under an external launcher (WORLD_SIZE set) it is one of the ranks and WORLD_SIZE must equal --gpus.
 """
@@ -99,6 +102,31 @@ def measure_copy_bandwidth(torch):
     return 2 * 4 * (1 << 30) / (ms * 1e-3) / 1e9
 
 
+DUMP_LIMIT_BYTES = 60_000_000    # --dump-outputs: data bytes over all files (under 64 MB with the .npy headers)
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(out_dir, batches, tpch):
+    """The Q3 result as a caller receives it (rows in the plan's output order), one float64 .npy per column: l_orderkey, revenue (the Decimal128(38,4)
+    value, unscaled / 1e4), o_orderdate (days since the epoch), o_shippriority.  Above DUMP_LIMIT_BYTES the same seeded, sorted sample of rows is taken
+    from every column.  Returns the number of rows written."""
+    import numpy as np
+    r = tpch.q3_result_to_numpy(batches)
+    lo, hi = r["revenue"][:, 0].view(np.int64), r["revenue"][:, 1].view(np.int64)
+    assert np.array_equal(hi, lo >> 63), "revenue beyond Int64: not representable in the dump"
+    cols = {"l_orderkey": r["l_orderkey"].astype(np.float64), "revenue": lo.astype(np.float64) / 1e4,
+            "o_orderdate": r["o_orderdate"].astype(np.float64), "o_shippriority": r["o_shippriority"].astype(np.float64)}
+    n = len(lo)
+    keep = DUMP_LIMIT_BYTES // (8 * len(cols))
+    if n > keep:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+        cols = {k: v[rows] for k, v in cols.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in cols.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return min(n, keep)
+
+
 METRIC = "rows/sec hash-join+agg, TPC-H SF100 Q3"
 PARALLELISM = {"colocated": "%d GPUs, range-sharded tables: RCCL all-gather of the customer build side, partition-local orders-lineitem join + aggregation, gather of sorted partitions",
                "broadcast": "%d GPUs, CollectLeft joins: RCCL all-gather of build sides + all-to-all of partial aggregates",
@@ -109,10 +137,10 @@ ROOFLINE_KEYS = ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic
 CPU_KEYS = ("value", "unit", "cores", "cpu_model", "kind", "sample")
 
 
-def compact_line(detail):
+def compact_line(detail, detail_file="bench_detail.json"):
     """The one stdout line: the contract's keys, the roofline and cpu_baseline objects cut to scalars, one ms_per_step scalar per nested
-    workload.  Everything else (per-kernel tables, notes, step arrays) stays in bench_detail.json / stderr.  Same shape as the reference's
-    own report: one query, its iterations averaged (benchmarks/src/tpch/run.rs:120-156)."""
+    workload.  Everything else (per-kernel tables, notes, step arrays) stays in bench_detail.json / stderr (detail_file: None when no side file
+    was written).  Same shape as the reference's own report: one query, its iterations averaged (benchmarks/src/tpch/run.rs:120-156)."""
     top = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")
     line = {k: detail.get(k) for k in top}
     cfg = detail.get("config") or {}
@@ -138,7 +166,7 @@ def compact_line(detail):
         ms["q3_plan_" + name] = w.get("ms_per_step")
     if ms:
         line["ms_per_step_other"] = ms
-    line["detail"] = "bench_detail.json"
+    line["detail"] = detail_file
     text = json.dumps(line, separators=(",", ":"))
     if len(text) > LINE_LIMIT:          # never lose the headline to a long string: drop the optional parts
         line.pop("ms_per_step_other", None)
@@ -152,27 +180,33 @@ def compact_line(detail):
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: per-kernel roofline, copy bandwidth, result check, "
+                                                        "general paths, shuffled inputs, nested workloads, CPU baseline (N = 1); the other plans and workloads (N > 1)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's Q3 result columns as DIR/<column>.npy (float64, rank 0)")
     ap.add_argument("--sf", type=float, default=100.0, help="TPC-H scale factor of the whole job")
-    ap.add_argument("--cpu-sf", type=float, default=30.0, help="scale factor of the bounded CPU-baseline sample (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-sf", type=float, default=30.0, help="--full: scale factor of the bounded CPU-baseline sample (0 = skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse the N > 1 path on one GPU)")
     ap.add_argument("--one-device", action="store_true", help="rehearsal: every rank uses cuda:0 (needs --backend gloo)")
-    ap.add_argument("--no-shuffled", action="store_true", help="N = 1: skip Q3 over row-wise permuted tables")
-    ap.add_argument("--no-workloads", action="store_true", help="N = 1: skip the nested other plan shapes (bench_workloads.py)")
+    ap.add_argument("--no-shuffled", action="store_true", help="--full, N = 1: skip Q3 over row-wise permuted tables")
+    ap.add_argument("--no-workloads", action="store_true", help="--full: skip the nested other plan shapes (bench_workloads.py; dist_workloads.py for N > 1)")
     ap.add_argument("--workloads", default="q1_decimal,q1_float64,q5,q18,hash_join,groupby_int64,groupby_decimal_3key,sort,partition,parquet_scan,csv_scan,clickbench_uniform_1000000,clickbench_zipf_1000000",
-                    help="N = 1: which plan shapes of bench_workloads.py to nest under \"workloads\"")
+                    help="--full, N = 1: which plan shapes of bench_workloads.py to nest under \"workloads\"")
     ap.add_argument("--collective-deadline", type=float, default=180.0, help="N > 1: seconds without progress (no exchange started, no step finished) after which a rank reports where it stands and exits with code 3 instead of hanging the job")
     ap.add_argument("--native-exchange", action="store_true", help="N > 1 workloads: ShuffleExec through the C entry point dfgpu_exchange (RCCL inside libdfgpu.so) instead of torch.distributed collectives")
     ap.add_argument("--option", action="append", default=[], metavar="KEY=VALUE", help="ctx option set before the run (dfgpu_ctx_set_option), e.g. --option mailbox_readback=0 for an A/B run")
     ap.add_argument("--launch-check", action="store_true", help="only rendezvous the ranks (gloo, CPU) and report ranks_seen: rehearses the launcher without a GPU")
-    ap.add_argument("--detail", default="", help="where the full result object goes (default: bench_detail.json next to bench.py); it is also written to stderr")
+    ap.add_argument("--detail", default="", help="--full: where the full result object goes (default: bench_detail.json next to bench.py); it is also written to stderr")
     ap.add_argument("--plan", choices=["colocated", "broadcast", "shuffle"], default="shuffle",
                     help="N > 1: colocated = customer build side broadcast, orders-lineitem join and aggregation partition-local (the shards are co-partitioned on "
                          "the order key, as TPC-H files are); broadcast = both build sides all-gathered (CollectLeft), partial aggregates shuffled; "
                          "shuffle = the reference's fully partitioned plan (hash repartition of every join / aggregate input)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 class Watchdog:
@@ -323,9 +357,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # Per-kernel breakdown: one untimed step with every kernel bracketed by HIP events (the last warm-up step, or one step
+    # --full: per-kernel breakdown from one untimed step with every kernel bracketed by HIP events (the last warm-up step, or one step
     # after the timed region when --warmup 0).  An event pair costs ~10 us of stream bubble, so the timed region itself
-    # brackets only the dominant kernel found here -- that is the measurement the roofline object reports.
+    # brackets only the dominant kernel found here -- that is the measurement the roofline object reports.  A plain run brackets nothing.
     def profiled_step():
         ctx.profile_select(None)
         ctx.profile_enable(True)
@@ -338,7 +372,7 @@ def main():
     breakdown = None
     gc.collect(); gc.disable()          # the timed region must not contain a cyclic-GC pass of the Python wrappers (bench_workloads.py: one such pass cost a single step 65 ms)
     for w in range(args.warmup):
-        if w == args.warmup - 1:
+        if args.full and w == args.warmup - 1:
             breakdown = profiled_step()
         else:
             step()
@@ -348,10 +382,11 @@ def main():
     host_syncs = None
     if breakdown:
         breakdown, host_syncs = split_syncs(breakdown)
-    dominant = max(breakdown.items(), key=lambda kv: kv[1][1])[0] if breakdown else "k_probe_match_bitmap"
-    ctx.profile_select(dominant)
-    ctx.profile_enable(True)
-    ctx.profile_read()
+    if args.full:
+        dominant = max(breakdown.items(), key=lambda kv: kv[1][1])[0] if breakdown else "k_probe_match_bitmap"
+        ctx.profile_select(dominant)
+        ctx.profile_enable(True)
+        ctx.profile_read()
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -359,10 +394,16 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    prof, _ = split_syncs(ctx.profile_read())
-    ctx.profile_enable(False)
-    if breakdown is None:
-        breakdown, host_syncs = split_syncs(profiled_step())
+    timed_out = last_out[0]             # the last timed step's result (the --full legs below run further steps)
+    prof = {}
+    if args.full:
+        prof, _ = split_syncs(ctx.profile_read())
+        ctx.profile_enable(False)
+        if breakdown is None:
+            breakdown, host_syncs = split_syncs(profiled_step())
+    if args.dump_outputs and rank == 0:
+        n_dumped = dump_outputs(args.dump_outputs, timed_out or [], tpch)
+        sys.stderr.write("bench.py: %d result rows written to %s\n" % (n_dumped, args.dump_outputs))
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -411,9 +452,9 @@ def main():
     logical_scan = {"bytes_per_input_row": Q3_BYTES_PER_ROW, "GBps": round(Q3_BYTES_PER_ROW * rows_total / (ms_per_step * 1e-3) / 1e9, 1),
                     "note": "logical bytes of every referenced column / step time; NOT HBM traffic (filtered rows' payload columns are never read)"}
 
-    # ---- N = 1: result check at full scale, the general (hash) paths of the same query, the other target plan shapes
+    # ---- --full, N = 1: result check at full scale, the general (hash) paths of the same query, the other target plan shapes
     result_check = general = workloads = other_plans = dist_workloads = shuffled = None
-    if world == 1:
+    if args.full and world == 1:
         got = tpch.q3_checksum_result(last_out[0] or [])
         want = tpch.q3_checksum_torch(tensors)
         result_check = {"ok": got == want, "device": got, "torch": want, "what": "result groups, wrapping Int64 sums of l_orderkey and of unscaled revenue: the last timed step against plain torch ops over the same tensors"}
@@ -480,7 +521,7 @@ def main():
             workloads = {r["workload"]: {k: r[k] for k in ("input_rows", "result_rows", "ms_per_step", "rows_per_s", "algorithmic_GBps", "frac_of_hbm_peak", "algorithmic_bytes_per_row", "roofline", "host_syncs_per_step", "host_syncs_by_cause", "result_check", "step_ms", "memory_GB") if k in r}
                          | {"kernel_ms_per_step": dict(list(r["kernel_ms_per_step"].items())[:8])} | {k: r[k] for k in r if k in ("cardinality", "build_rows", "probe_rows", "rows_per_build_key", "partitions", "exchange", "file_bytes", "decoded_bytes", "decoded_GBps", "file_GBps", "from_host_image_ms", "from_host_image_decoded_GBps", "row_groups",
                                                                                                                                                     "ms_per_step_median", "from_host_image_reads_ms", "host_image", "match_fraction", "global_table_ms_per_step", "hash_table_ms_per_step")} for r in res}
-    else:
+    elif args.full:
         # the other two distribution plans, after the timed region (every rank takes part: they hold collectives)
         other_plans = {}
         for name in ("shuffle", "broadcast", "colocated"):
@@ -569,7 +610,7 @@ def main():
 
     # ---- CPU baseline: the oracle's restatement of the same plan on a bounded sample (rank 0, N = 1 only)
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_sf > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_sf > 0:
         from oracle import pyoracle as po
         import numpy as np
         cpu_sf = min(args.cpu_sf, args.sf)
@@ -615,22 +656,24 @@ def main():
             if workloads is not None:
                 detail["workloads"] = workloads
         else:
-            detail["plans"] = other_plans
+            if other_plans is not None:
+                detail["plans"] = other_plans
             if dist_workloads:
                 detail["workloads"] = dist_workloads
             detail["config"]["plan"] = args.plan
             detail["config"]["exchange_path"] = ("dfgpu_exchange (C ABI, RCCL grouped send / recv inside libdfgpu.so)" if args.native_exchange else "exchange.py over torch.distributed (%s): one metadata all-gather + one all-to-all(v) per exchange" % args.backend) + \
                 "; Q3's own plans always use the torch.distributed path, --native-exchange switches the Q5 / ClickBench workloads"
-        # everything measured goes to a side file + stderr; the LAST stdout line is the compact object the driver parses
-        text = json.dumps(detail)
-        try:
-            with open(args.detail or os.path.join(ROOT, "bench_detail.json"), "w") as f:
-                f.write(json.dumps(detail, indent=1) + "\n")
-        except OSError as e:
-            sys.stderr.write("bench.py: bench_detail.json not written: %r\n" % (e,))
-        sys.stderr.write(text + "\n"); sys.stderr.flush()
+        # --full: everything measured goes to a side file + stderr; the LAST stdout line is the compact object the driver parses
+        if args.full:
+            text = json.dumps(detail)
+            try:
+                with open(args.detail or os.path.join(ROOT, "bench_detail.json"), "w") as f:
+                    f.write(json.dumps(detail, indent=1) + "\n")
+            except OSError as e:
+                sys.stderr.write("bench.py: bench_detail.json not written: %r\n" % (e,))
+            sys.stderr.write(text + "\n"); sys.stderr.flush()
         sys.stdout.flush()
-        print(compact_line(detail), flush=True)
+        print(compact_line(detail, "bench_detail.json" if args.full else None), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -18,7 +18,7 @@ run3() {   # name, program and its arguments: kernel stats, FETCH_SIZE, WRITE_SI
   rm -rf $O/${name}_fetch $O/${name}_write $O/${name}_stats
 }
 for p in $PASSES; do case $p in
-  q3)  run3 q3 $R/bench.py --no-workloads --no-cpu-baseline --no-shuffled --steps 10 --warmup 3 --detail $O/q3_detail.json ;;
+  q3)  run3 q3 $R/bench.py --full --no-workloads --no-cpu-baseline --no-shuffled --steps 10 --warmup 3 --detail $O/q3_detail.json ;;
   q3s) run3 q3s $R/profiles/q3_shuffled_run.py --sf 100 --steps 5 --warmup 2 ;;
   gb)  run3 gb20 $R/bench_workloads.py --only groupby_int64_unclustered_20000000 --sf 100        # one workload per process: kernel names repeat across them
        run3 cbu $R/bench_workloads.py --only clickbench_uniform_1000000 --sf 100
@@ -26,6 +26,6 @@ for p in $PASSES; do case $p in
   hj)  run3 hj $R/bench_workloads.py --only hash_join_plain --sf 100 ;;
   sort) run3 sort $R/bench_workloads.py --only sort --sf 100 ;;
   shares)   # one rank's share of the Q3 step at 8 / 4 / 2 GPUs when nothing has to move: clustered, general paths, shuffled
-    for sf in 12.5 25 50; do python3 $R/bench.py --sf $sf --steps 20 --warmup 5 --no-workloads --no-cpu-baseline --detail $O/share_sf$sf.json 2> /dev/null | tail -1 > $O/share_sf$sf.line.json; echo "share sf $sf rc=$?"; done ;;
+    for sf in 12.5 25 50; do python3 $R/bench.py --full --sf $sf --steps 20 --warmup 5 --no-workloads --no-cpu-baseline --detail $O/share_sf$sf.json 2> /dev/null | tail -1 > $O/share_sf$sf.line.json; echo "share sf $sf rc=$?"; done ;;
 esac; done
 cd $O; ls -la; tail -q -n 2 *_stats.log 2>/dev/null | cut -c1-400; (cat share_sf*.line.json 2>/dev/null | cut -c1-700) || true

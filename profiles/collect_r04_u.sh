@@ -8,6 +8,6 @@ tail -3 $O/r04_${T}_pytest.log
 [ $rc -ne 0 ] && exit $rc
 bash profiles/collect_r04.sh $T q3 shares
 cd "$GRAFT_REPO_ROOT"
-timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/r04_${T}_stdout.txt 2> $O/r04_${T}_stderr.txt; rc=$?
+timeout -k 10 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r04_${T}_stdout.txt 2> $O/r04_${T}_stderr.txt; rc=$?
 cp bench_detail.json $O/r04_${T}_bench_detail.json; tail -c 2600 $O/r04_${T}_stdout.txt
 exit $rc

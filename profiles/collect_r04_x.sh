@@ -10,6 +10,6 @@ wl() { timeout -k 10 200 python3 bench_workloads.py --only $1 --sf 100 --steps 5
 wl sort "" sort
 wl clickbench_uniform_1000000 "" cbu
 wl clickbench_zipf_1000000 "" cbz
-timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/r04_${T}_stdout.txt 2> $O/r04_${T}_stderr.txt; rc=$?
+timeout -k 10 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r04_${T}_stdout.txt 2> $O/r04_${T}_stderr.txt; rc=$?
 cp bench_detail.json $O/r04_${T}_bench_detail.json; tail -c 2200 $O/r04_${T}_stdout.txt
 exit $rc

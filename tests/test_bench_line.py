@@ -80,3 +80,87 @@ def test_world_size_must_equal_gpus():
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
     r = run_bench(["--gpus", "1", "--launch-check"], env={"WORLD_SIZE": "2", "RANK": "0"})
     assert r.returncode != 0
+
+
+def test_steps_must_be_positive():
+    r = run_bench(["--steps", "0", "--launch-check"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+class _Col:
+    def __init__(self, a):
+        self.a = a
+
+    def to_arrow(self):
+        return self.a
+
+
+class _Batch:
+    def __init__(self, cols):
+        self.columns = [_Col(c) for c in cols]
+
+
+def q3_batch(keys, revenue, dates):
+    import decimal
+    import pyarrow as pa
+    return _Batch([pa.array(keys, pa.int64()), pa.array([decimal.Decimal(r) for r in revenue], pa.decimal128(38, 4)),
+                   pa.array(dates, pa.date32()), pa.array([0] * len(keys), pa.int32())])
+
+
+def test_dump_outputs_are_float64_columns_in_result_order(tmp_path):
+    import numpy as np
+    from dfgpu import tpch
+    batches = [q3_batch([5, 3], ["12.3456", "-7.0001"], [9000, 9001]), q3_batch([11], ["0.5"], [8000])]
+    assert bench.dump_outputs(str(tmp_path), batches, tpch) == 3
+    got = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert set(got) == {"l_orderkey", "revenue", "o_orderdate", "o_shippriority"}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["l_orderkey"].tolist() == [5, 3, 11] and got["revenue"].tolist() == [12.3456, -7.0001, 0.5]
+    assert got["o_orderdate"].tolist() == [9000, 9001, 8000] and got["o_shippriority"].tolist() == [0, 0, 0]
+
+
+def test_dump_outputs_sample_is_bounded_and_fixed(tmp_path, monkeypatch):
+    import numpy as np
+    from dfgpu import tpch
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 8 * 100)        # room for 100 of the 1000 rows
+    batches = [q3_batch(list(range(1000)), ["%d.25" % i for i in range(1000)], [9000] * 1000)]
+    runs = []
+    for d in ("a", "b"):
+        assert bench.dump_outputs(str(tmp_path / d), batches, tpch) == 100
+        runs.append({f: np.load(os.path.join(tmp_path, d, f)) for f in os.listdir(tmp_path / d)})
+    keys = runs[0]["l_orderkey.npy"]
+    assert len(keys) == 100 and np.all(np.diff(keys) > 0)                                   # the same rows of every column, in result order
+    assert np.array_equal(runs[0]["revenue.npy"], keys + 0.25)
+    assert all(np.array_equal(runs[0][f], runs[1][f]) for f in runs[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_result(ctx, tmp_path):
+    """A plain run: the contract's keys and nothing that takes runs of its own; --dump-outputs holds the last step's Q3 result, checked against
+    the plain-torch recomputation over the same generated tables."""
+    import numpy as np
+    from dfgpu import tpch
+    r = run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--sf", "1", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["unit"] == "rows/s" and line["higher_is_better"] is True
+    assert abs(line["value"] - line["config"]["input_rows"] / (line["ms_per_step"] * 1e-3)) <= 0.02 * line["value"]       # ms_per_step is rounded to 1 us
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "result_check" not in line and "ms_per_step_other" not in line
+    cols = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert all(v.dtype == np.float64 and len(v) == line["config"]["result_rows"] for v in cols.values())
+    want = tpch.q3_checksum_torch(tpch.gen_device_tensors(1.0))
+    assert len(cols["l_orderkey"]) == want["groups"] and int(cols["l_orderkey"].astype(np.int64).sum()) == want["sum_orderkey"]
+    assert int(np.rint(cols["revenue"] * 1e4).astype(np.int64).sum()) == want["sum_revenue"]
+    assert np.all(np.diff(cols["revenue"]) <= 0)                                                # revenue DESC
+
+
+@pytest.mark.gpu
+def test_full_run_keeps_the_other_measurements(ctx, tmp_path):
+    r = run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--sf", "1", "--full", "--no-workloads", "--cpu-sf", "0.1", "--detail", str(tmp_path / "detail.json")])
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["result_check"] == {"ok": True} and line["detail"] == "bench_detail.json"
+    assert line["roofline"]["measured_copy_GBps"] > 0 and line["cpu_baseline"]["kind"] == "port"
+    assert set(line["ms_per_step_other"]) == {"q3_general_paths", "q3_shuffled_inputs"}
+    detail = json.load(open(tmp_path / "detail.json"))
+    assert detail["roofline"]["kernel_ms_per_step"] and detail["q3_general_paths"]["result_check"]
