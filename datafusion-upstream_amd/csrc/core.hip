@@ -375,6 +375,83 @@ __global__ void __launch_bounds__(BLOCK) k_slist_copy(const uint8_t* lbytes, con
   const uint32_t len = (uint32_t)(voff[j + 1] - voff[j]); const uint8_t* src = lbytes + spos[j]; uint8_t* o = out + voff[j];
   for (uint32_t b = 0; b < len; b++) o[b] = src[b];
 }
+
+// ---------------------------------------------------------------- context options
+// Every option of dfgpu_ctx_set_option / dfgpu_ctx_get_option (documented in include/dfgpu.h): how it is read and how it is written.  get == nullptr: set only (an
+// action); set == nullptr: read only.
+struct CtxOption { const char* name; int64_t (*get)(const dfgpu_ctx*); void (*set)(dfgpu_ctx*, int64_t); };
+#define OPT_GET(M) [](const dfgpu_ctx* c) -> int64_t { return (int64_t)c->M; }
+#define OPT_BOOL(M) OPT_GET(M), [](dfgpu_ctx* c, int64_t v) { c->M = v != 0; }
+#define OPT_INT(M) OPT_GET(M), [](dfgpu_ctx* c, int64_t v) { c->M = v; }
+#define OPT_MIN(M, LO) OPT_GET(M), [](dfgpu_ctx* c, int64_t v) { c->M = v < LO ? LO : v; }
+#define OPT_RANGE(M, LO, HI) OPT_GET(M), [](dfgpu_ctx* c, int64_t v) { if (v < LO || v > HI) fail(DFGPU_INVALID_ARGUMENT, #M ": " #LO " .. " #HI); c->M = v; }
+#define OPT_READ(M) OPT_GET(M), nullptr
+static const CtxOption kCtxOptions[] = {
+  { "force_hash_collisions", OPT_BOOL(force_hash_collisions) },
+  { "first_seen_group_order", OPT_BOOL(first_seen_group_order) },
+  { "join_rank_index", OPT_BOOL(join_rank_index) },
+  { "join_rank_index_unsorted", OPT_BOOL(join_rank_index_unsorted) },
+  { "join_lazy_build_rows", OPT_BOOL(join_lazy_build_rows) },
+  { "join_selection_output", OPT_BOOL(join_selection_output) },
+  { "join_key_packing", OPT_BOOL(join_key_packing) },
+  { "join_swap_small_semi", OPT_BOOL(join_swap_small_semi) },
+  { "join_partitioned", OPT_BOOL(join_partitioned) },
+  { "join_partitioned_min_build", OPT_INT(join_partitioned_min_build) },
+  { "join_partitioned_min_probe", OPT_INT(join_partitioned_min_probe) },
+  { "join_partitioned_big", OPT_BOOL(join_partitioned_big) },
+  { "join_partitioned_hashed", OPT_BOOL(join_partitioned_hashed) },
+  { "join_partitioned_hash_mask", [](const dfgpu_ctx* c) -> int64_t { return c->join_partitioned_hash_mask == ~0ull ? 0 : (int64_t)c->join_partitioned_hash_mask; },
+                                  [](dfgpu_ctx* c, int64_t v) { c->join_partitioned_hash_mask = v <= 0 ? ~0ull : (uint64_t)v; } },          // 0 == all bits
+  { "join_partition_rows", OPT_INT(join_partition_rows) },
+  { "group_run_detection", OPT_BOOL(group_run_detection) },
+  { "group_lazy_keys", OPT_BOOL(group_lazy_keys) },
+  { "group_dictionary_canon", OPT_BOOL(group_dictionary_canon) },
+  { "fused_aggregate_min_rows", OPT_INT(fused_aggregate_min_rows) },
+  { "agg_order_inverse_map", OPT_BOOL(agg_order_inverse_map) },
+  { "agg_partitioned", OPT_BOOL(agg_partitioned) },
+  { "agg_partitioned_force", OPT_BOOL(agg_partitioned_force) },
+  { "agg_partitioned_min_rows", OPT_INT(agg_partitioned_min_rows) },
+  { "agg_pack_estimate_min_rows", OPT_INT(agg_pack_estimate_min_rows) },
+  { "agg_preaggregate_distinct", OPT_READ(pa_last_distinct) },
+  { "agg_spill_state_bytes", OPT_INT(agg_spill_state_bytes) },
+  { "agg_spill_ranges", OPT_RANGE(agg_spill_ranges, 1, 4096) },
+  { "sort_packed_keys", OPT_BOOL(sort_packed_keys) },
+  { "sort_packed_min_rows", OPT_MIN(sort_packed_min_rows, 2) },
+  { "sort_estimate_ranges", OPT_BOOL(sort_estimate_ranges) },
+  { "sort_topk_words_min_rows", OPT_MIN(sort_topk_words_min_rows, 2) },
+  { "sort_one_block_max_rows", OPT_MIN(sort_one_block_max_rows, 0) },
+  { "sort_onesweep_min_rows", OPT_MIN(sort_onesweep_min_rows, 2) },
+  { "sort_onesweep_rows", OPT_GET(sort_onesweep_rows), [](dfgpu_ctx* c, int64_t v) { c->sort_onesweep_rows = v == 16 ? 16 : v > 0 ? 8 : 0; } },      // 16, 8 or 0
+  { "sort_onesweep_fused_finish", OPT_BOOL(sort_onesweep_fused_finish) },
+  { "sort_fused_small_passes", OPT_BOOL(sort_fused_small_passes) },
+  { "sort_spill_bytes", OPT_INT(sort_spill_bytes) },
+  { "sort_spill_ranges", OPT_RANGE(sort_spill_ranges, 1, 4096) },
+  { "spm_merge_rows", OPT_GET(spm_merge_rows), [](dfgpu_ctx* c, int64_t v) { if (v < 0) fail(DFGPU_INVALID_ARGUMENT, "spm_merge_rows: >= 0"); c->spm_merge_rows = v; } },
+  { "memory_limit", OPT_INT(memory_limit) },
+  { "live_bytes", OPT_READ(live_bytes) },              // device bytes held by live buffers of this ctx
+  { "cached_bytes", OPT_READ(cached_bytes) },          // freed blocks kept for reuse
+  // give the freed blocks the ctx keeps for reuse back to the driver (≙ MemoryPool::shrink): after the stream has drained, so no kernel still reads them
+  { "trim_cache", nullptr, [](dfgpu_ctx* c, int64_t) {
+      HIP_CHECK(hipStreamSynchronize(c->stream));
+      std::lock_guard<std::mutex> l(*c->alloc_mu); for (auto& x : *c->free_blocks) (void)hipFree(x.second); c->free_blocks->clear(); c->cached_bytes = 0; } },
+  { "mailbox_readback", OPT_BOOL(mailbox_readback) },
+  { "collect_metrics", OPT_BOOL(collect_metrics) },
+  // nests: +1 enters a deferred region, 0 leaves it and raises what the region deferred; reads the depth
+  { "defer_flag_checks", OPT_GET(defer_flag_checks), [](dfgpu_ctx* c, int64_t v) {
+      if (v) c->defer_flag_checks++;
+      else { if (c->defer_flag_checks > 0) c->defer_flag_checks--; if (c->defer_flag_checks == 0) flush_flags(c); } } },
+};
+#undef OPT_GET
+#undef OPT_BOOL
+#undef OPT_INT
+#undef OPT_MIN
+#undef OPT_RANGE
+#undef OPT_READ
+static const CtxOption& ctx_option(const char* key) {
+  const std::string k = key ? key : "";
+  for (const CtxOption& o : kCtxOptions) if (k == o.name) return o;
+  fail(DFGPU_INVALID_ARGUMENT, "unknown option '%s'", k.c_str());
+}
 }  // namespace dfgpu
 
 extern "C" {
@@ -418,109 +495,18 @@ dfgpu_status dfgpu_ctx_synchronize(dfgpu_ctx* ctx) {
 }
 dfgpu_status dfgpu_ctx_set_option(dfgpu_ctx* ctx, const char* key, int64_t value) {
   return guard(ctx, [&] {
-    std::string k = key ? key : "";
-    if (k == "force_hash_collisions") ctx->force_hash_collisions = value != 0;
-    else if (k == "first_seen_group_order") ctx->first_seen_group_order = value != 0;
-    else if (k == "join_rank_index") ctx->join_rank_index = value != 0;
-    else if (k == "join_rank_index_unsorted") ctx->join_rank_index_unsorted = value != 0;
-    else if (k == "join_lazy_build_rows") ctx->join_lazy_build_rows = value != 0;
-    else if (k == "join_selection_output") ctx->join_selection_output = value != 0;
-    else if (k == "agg_order_inverse_map") ctx->agg_order_inverse_map = value != 0;
-    else if (k == "join_bitmap_partitioned") ctx->join_bitmap_partitioned = value != 0;
-    else if (k == "join_bitmap_partitioned_min_rows") ctx->join_bitmap_partitioned_min_rows = value;
-    else if (k == "join_key_packing") ctx->join_key_packing = value != 0;
-    else if (k == "group_run_detection") ctx->group_run_detection = value != 0;
-    else if (k == "group_lazy_keys") ctx->group_lazy_keys = value != 0;
-    else if (k == "group_dictionary_canon") ctx->group_dictionary_canon = value != 0;
-    else if (k == "join_swap_small_semi") ctx->join_swap_small_semi = value != 0;
-    else if (k == "fused_aggregate_min_rows") ctx->fused_aggregate_min_rows = value;
-    else if (k == "sort_packed_keys") ctx->sort_packed_keys = value != 0;
-    else if (k == "memory_limit") ctx->memory_limit = value;
-    else if (k == "mailbox_readback") ctx->mailbox_readback = value != 0;
-    else if (k == "trim_cache") {        // give the freed blocks the ctx keeps for reuse back to the driver (≙ MemoryPool::shrink): after the stream has drained, so no kernel still reads them
-      HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      std::lock_guard<std::mutex> l(*ctx->alloc_mu); for (auto& x : *ctx->free_blocks) (void)hipFree(x.second); ctx->free_blocks->clear(); ctx->cached_bytes = 0;
-    }
-    else if (k == "agg_spill_state_bytes") ctx->agg_spill_state_bytes = value;
-    else if (k == "sort_estimate_ranges") ctx->sort_estimate_ranges = value != 0;
-    else if (k == "sort_topk_words_min_rows") ctx->sort_topk_words_min_rows = value < 2 ? 2 : value;
-    else if (k == "partition_two_round_staging") ctx->partition_two_round_staging = value != 0;
-    else if (k == "sort_payload_in_last_pass") ctx->sort_payload_in_last_pass = value != 0;
-    else if (k == "sort_onesweep_fused_finish") ctx->sort_onesweep_fused_finish = value != 0;
-    else if (k == "sort_one_block_max_rows") ctx->sort_one_block_max_rows = value < 0 ? 0 : value;
-    else if (k == "sort_onesweep_min_rows") ctx->sort_onesweep_min_rows = value < 2 ? 2 : value;
-    else if (k == "sort_onesweep_rows") ctx->sort_onesweep_rows = value == 16 ? 16 : value > 0 ? 8 : 0;
-    else if (k == "sort_fused_small_passes") ctx->sort_fused_small_passes = value != 0;
-    else if (k == "sort_packed_min_rows") ctx->sort_packed_min_rows = value < 2 ? 2 : value;
-    else if (k == "sort_spill_bytes") ctx->sort_spill_bytes = value;
-    else if (k == "spm_merge_rows") { if (value < 0) fail(DFGPU_INVALID_ARGUMENT, "spm_merge_rows: >= 0"); ctx->spm_merge_rows = value; }
-    else if (k == "sort_spill_ranges") { if (value < 1 || value > 4096) fail(DFGPU_INVALID_ARGUMENT, "sort_spill_ranges: 1 .. 4096"); ctx->sort_spill_ranges = value; }
-    else if (k == "agg_spill_ranges") { if (value < 1 || value > 4096) fail(DFGPU_INVALID_ARGUMENT, "agg_spill_ranges: 1 .. 4096"); ctx->agg_spill_ranges = value; }
-    else if (k == "collect_metrics") ctx->collect_metrics = value != 0;
-    else if (k == "agg_partitioned") ctx->agg_partitioned = value != 0;
-    else if (k == "agg_partitioned_force") ctx->agg_partitioned_force = value != 0;
-    else if (k == "agg_partitioned_min_rows") ctx->agg_partitioned_min_rows = value;
-    else if (k == "agg_pack_estimate_min_rows") ctx->agg_pack_estimate_min_rows = value;
-    else if (k == "join_partitioned") ctx->join_partitioned = value != 0;
-    else if (k == "join_partitioned_min_build") ctx->join_partitioned_min_build = value;
-    else if (k == "join_partitioned_min_probe") ctx->join_partitioned_min_probe = value;
-    else if (k == "join_partitioned_big") ctx->join_partitioned_big = value != 0;
-    else if (k == "join_partitioned_hashed") ctx->join_partitioned_hashed = value != 0;
-    else if (k == "join_partitioned_hash_mask") ctx->join_partitioned_hash_mask = value <= 0 ? ~0ull : (uint64_t)value;
-    else if (k == "join_partition_rows") ctx->join_partition_rows = value;
-    else if (k == "defer_flag_checks") {            // nests: +1 enters a deferred region, 0 leaves it and raises what the region deferred
-      if (value) ctx->defer_flag_checks++;
-      else { if (ctx->defer_flag_checks > 0) ctx->defer_flag_checks--; if (ctx->defer_flag_checks == 0) flush_flags(ctx); }
-    }
-    else fail(DFGPU_INVALID_ARGUMENT, "unknown option '%s'", k.c_str());
+    const CtxOption& o = ctx_option(key);
+    if (!o.set) fail(DFGPU_INVALID_ARGUMENT, "option '%s' is read only", o.name);
+    o.set(ctx, value);
   });
 }
 
 dfgpu_status dfgpu_ctx_get_option(dfgpu_ctx* ctx, const char* key, int64_t* out) {
   return guard(ctx, [&] {
-    std::string k = key ? key : "";
     if (!out) fail(DFGPU_INVALID_ARGUMENT, "ctx_get_option: null out");
-    if (k == "force_hash_collisions") *out = ctx->force_hash_collisions;
-    else if (k == "first_seen_group_order") *out = ctx->first_seen_group_order;
-    else if (k == "join_rank_index") *out = ctx->join_rank_index;
-    else if (k == "join_rank_index_unsorted") *out = ctx->join_rank_index_unsorted ? 1 : 0;
-    else if (k == "join_lazy_build_rows") *out = ctx->join_lazy_build_rows ? 1 : 0;
-    else if (k == "join_selection_output") *out = ctx->join_selection_output ? 1 : 0;
-    else if (k == "agg_order_inverse_map") *out = ctx->agg_order_inverse_map ? 1 : 0;
-    else if (k == "join_bitmap_partitioned") *out = ctx->join_bitmap_partitioned ? 1 : 0;
-    else if (k == "join_bitmap_partitioned_min_rows") *out = ctx->join_bitmap_partitioned_min_rows;
-    else if (k == "join_key_packing") *out = ctx->join_key_packing;
-    else if (k == "group_run_detection") *out = ctx->group_run_detection;
-    else if (k == "group_dictionary_canon") *out = ctx->group_dictionary_canon;
-    else if (k == "join_swap_small_semi") *out = ctx->join_swap_small_semi;
-    else if (k == "fused_aggregate_min_rows") *out = ctx->fused_aggregate_min_rows;
-    else if (k == "sort_packed_keys") *out = ctx->sort_packed_keys;
-    else if (k == "memory_limit") *out = ctx->memory_limit;
-    else if (k == "mailbox_readback") *out = ctx->mailbox_readback ? 1 : 0;
-    else if (k == "agg_spill_state_bytes") *out = ctx->agg_spill_state_bytes;
-    else if (k == "sort_estimate_ranges") *out = ctx->sort_estimate_ranges ? 1 : 0;
-    else if (k == "sort_packed_min_rows") *out = ctx->sort_packed_min_rows;
-    else if (k == "sort_spill_bytes") *out = ctx->sort_spill_bytes;
-    else if (k == "spm_merge_rows") *out = ctx->spm_merge_rows;
-    else if (k == "sort_spill_ranges") *out = ctx->sort_spill_ranges;
-    else if (k == "agg_spill_ranges") *out = ctx->agg_spill_ranges;
-    else if (k == "collect_metrics") *out = ctx->collect_metrics;
-    else if (k == "agg_preaggregate_distinct") *out = ctx->pa_last_distinct;      // read only
-    else if (k == "live_bytes") *out = (int64_t)ctx->live_bytes;              // read only: device bytes held by live buffers of this ctx
-    else if (k == "cached_bytes") *out = (int64_t)ctx->cached_bytes;          // read only: freed blocks kept for reuse
-    else if (k == "live_bytes") *out = (int64_t)ctx->live_bytes;              // read only: device memory the ctx's arrays hold right now
-    else if (k == "agg_partitioned") *out = ctx->agg_partitioned;
-    else if (k == "agg_partitioned_force") *out = ctx->agg_partitioned_force;
-    else if (k == "agg_partitioned_min_rows") *out = ctx->agg_partitioned_min_rows;
-    else if (k == "agg_pack_estimate_min_rows") *out = ctx->agg_pack_estimate_min_rows;
-    else if (k == "join_partitioned") *out = ctx->join_partitioned;
-    else if (k == "join_partitioned_min_build") *out = ctx->join_partitioned_min_build;
-    else if (k == "join_partitioned_min_probe") *out = ctx->join_partitioned_min_probe;
-    else if (k == "join_partitioned_hashed") *out = ctx->join_partitioned_hashed ? 1 : 0;
-    else if (k == "join_partitioned_hash_mask") *out = ctx->join_partitioned_hash_mask == ~0ull ? 0 : (int64_t)ctx->join_partitioned_hash_mask;
-    else if (k == "join_partition_rows") *out = ctx->join_partition_rows;
-    else if (k == "defer_flag_checks") *out = ctx->defer_flag_checks;
-    else fail(DFGPU_INVALID_ARGUMENT, "unknown option '%s'", k.c_str());
+    const CtxOption& o = ctx_option(key);
+    if (!o.get) fail(DFGPU_INVALID_ARGUMENT, "option '%s' cannot be read", o.name);
+    *out = o.get(ctx);
   });
 }
 

@@ -55,9 +55,6 @@ struct dfgpu_ctx {
   uint64_t join_partitioned_hash_mask = ~0ull;       // tests: AND-ed onto the key hashes of the hashed mode, so that different keys collide
   bool join_partitioned_hashed = true;       // builds the integer mode of the partitioned join does not take (several key columns that do not pack, Utf8 / dictionary keys, null_equals_null) go through it on 64-bit key hashes
   bool join_partitioned_big = true;                            // builds beyond 2048 x join_partition_rows rows: up to 4096 partitions (else they decline to the global table)
-  // membership-bitmap probes of unclustered keys through a key-range partition (pjoin.hip bp_probe).  OFF: measured slower than the random probes it replaces (TPC-H Q3 over
-  // shuffled tables at SF100: partition 6.9 ms + probe 2.0 ms against 6.8 ms of random probes -- the LDS-staged scatter moves ~120 G rows/s whatever the row width)
-  bool join_bitmap_partitioned = false; int64_t join_bitmap_partitioned_min_rows = 1 << 24;
   bool join_partitioned = true; int64_t join_partitioned_min_build = 1 << 20, join_partitioned_min_probe = 1 << 22, join_partition_rows = 14000;
   int64_t fused_aggregate_min_rows = 1 << 20;
   bool sort_packed_keys = true;     // large sorts over fixed-width keys: range-packed u64 keys + stable one-pass partition per digit (sort.hip)
@@ -93,8 +90,6 @@ struct dfgpu_ctx {
   int64_t sort_topk_words_min_rows = 1 << 23;                  // SortExec with fetch <= n / 16: from this many rows on (keys packing into a word with the row number) the radix select runs on the packed words; below, on byte planes
   int64_t sort_one_block_max_rows = 8192;                      // byte-plane sorts of at most this many rows (<= 8192): every pass inside one launch of one workgroup; 0 = off
   int64_t sort_onesweep_min_rows = 1 << 20;
-  bool partition_two_round_staging = false;                    // radix partition into 513 .. 2048 partitions: every column staged in two rounds of half a tile (74 KB of LDS: two workgroups per CU).  Off: measured slower -- twice the barriers and predicated loads cost more than the second workgroup brings (ClickBench uniform: scatter 1.79 -> 2.44 ms; three-key Decimal128 group-by 1.49 -> 1.99 ms; 1 M Int64 groups 1.26 -> 1.43 ms)
-  bool sort_payload_in_last_pass = false;                      // dfgpu_sort_take: the last one-sweep pass gathers the payload columns (else the caller's take() does, afterwards).  Off: measured slower (100 M rows, one 8-byte payload column: passes + gather 6.36 ms inside the last pass against 3.89 + 2.13 ms apart; both sides are bound by memory requests, the random reads in the scatter phase only slow the pass down)
   bool sort_onesweep_fused_finish = true;                      // the last one-sweep pass writes row numbers and rebuilt key columns instead of the words (no k_pk_finish pass)
   int sort_onesweep_rows = 16;                                  // word-mode sorts of 2^20 .. 2^30 rows: one launch per pass (look-back over published tile counts, sort.hip); rows per lane of a tile (8 or 16), 0 = the three-launch passes
   bool sort_fused_small_passes = true;                         // inputs below 2^20 rows: the per-pass scan is folded into the scatter (two launches per varying key byte instead of three)

@@ -884,9 +884,7 @@ static dfgpu_status join_probe_impl(dfgpu_ctx* ctx, const dfgpu_join_table* t, c
       }
       use_bitmap = t->bitmap && pk->type == t->keys[0]->type;      // same physical integer type, no dictionary
       if (!use_bitmap && !t->slots) build_hash_table(ctx, const_cast<dfgpu_join_table*>(t), false);   // rank index cannot serve this probe column
-      if (use_bitmap && bp_probe(ctx, t, pk, mk, n, (uint64_t*)match_bits->ptr)) {
-        // unclustered keys: probed partition by partition of the key range (pjoin.hip)
-      } else if (use_bitmap) {
+      if (use_bitmap) {
         KernelTimer kt_(ctx, "k_probe_match_bitmap");
         int64_t rows_per_block = (int64_t)BLOCK * PM_ROWS;
         const uint64_t* kvp = pk->validity ? (const uint64_t*)pk->validity->ptr : nullptr;

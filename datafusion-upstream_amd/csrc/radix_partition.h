@@ -87,14 +87,13 @@ __global__ void __launch_bounds__(NT) k_rp_hist(H hs, int64_t n, uint32_t P, int
 }
 
 // LDS of the scatter: cnt[P] u32 | delta[P] u32 | spid[TILE] u16 | slidx[TILE] u16 | stage[TILE] u64 | (STABLE) wcnt[NT / 64][P] u16
-template <int NT> static inline size_t rp_scatter_lds(uint32_t P, bool stable, int rounds = 1) {
-  return (size_t)P * 8 + (size_t)NT * RP_R * 4 + 8 + (size_t)NT * RP_R * 8 / (size_t)rounds + (stable ? (size_t)(NT / WAVE) * P * 2 : 0);
+template <int NT> static inline size_t rp_scatter_lds(uint32_t P, bool stable) {
+  return (size_t)P * 8 + (size_t)NT * RP_R * 4 + 8 + (size_t)NT * RP_R * 8 + (stable ? (size_t)(NT / WAVE) * P * 2 : 0);
 }
 
-// ROUNDS = 2: a column is staged and written out in two rounds of half a tile each (rows whose staged position lies in the round's half), so the staging buffer is half
-// as large: the 8192-row tile of the many-partition case then needs 74 KB instead of 106 KB of LDS and TWO workgroups fit a CU (one loading while the other writes) --
-// what the partitioned join's own scatter does (pjoin.hip); twice the barriers per column.  Measured (round 4, call y) and left off by default (ctx option
-// partition_two_round_staging): the pre-aggregation's 1024-way scatter of 100 M rows x three 8-byte columns 1.79 -> 2.44 ms.
+// ROUNDS: rounds in which a column is staged and written out; only 1 is launched.  Two rounds of half a tile (half the staging LDS, two workgroups per CU) measured
+// slower (1024-way scatter of 100 M rows x three 8-byte columns 1.79 -> 2.44 ms) and their launch was removed.  The one-trip round loop stays: without it the compiler
+// schedules the 1024-thread instantiations differently (row loads wait behind the hash; ClickBench uniform pa_scatter 1.76 -> 1.93 ms).
 template <int NT, bool STABLE, typename H, bool LO16 = false, int ROUNDS = 1>          // LO16: some column is RP_LO16 (an instantiation of its own: the extra branch in the column loop cost the others 10 %)
 __global__ void __launch_bounds__(NT) k_rp_scatter(H hs, int64_t n, uint32_t P, int64_t ntiles, const uint32_t* goff, RpCols cols) {
   extern __shared__ uint32_t rp_lds[];
@@ -335,12 +334,6 @@ static RpResult rp_partition(dfgpu_ctx* ctx, H hs, int64_t n, uint32_t P, const 
     if (direct && P <= 16) hipLaunchKernelGGL((k_rp_scatter_direct<512, 16, H>), dim3(grid), dim3(512), 0, ctx->stream, hs, n, P, ntiles, (const uint32_t*)counts->ptr, cols);
     else if (direct) hipLaunchKernelGGL((k_rp_scatter_direct<512, 256, H>), dim3(grid), dim3(512), 0, ctx->stream, hs, n, P, ntiles, (const uint32_t*)counts->ptr, cols);
     else if (small_wg) RP_LAUNCH(256, true) else if (stable) RP_LAUNCH(512, true)
-    else if (big && ctx->partition_two_round_staging) {          // the 8192-row tile staged in two rounds: two workgroups per CU
-      if (lo16) { HIP_CHECK(hipFuncSetAttribute((const void*)k_rp_scatter<1024, false, H, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-        hipLaunchKernelGGL((k_rp_scatter<1024, false, H, true, 2>), dim3(grid), dim3(1024), rp_scatter_lds<1024>(P, false, 2), ctx->stream, hs, n, P, ntiles, (const uint32_t*)counts->ptr, cols); }
-      else { HIP_CHECK(hipFuncSetAttribute((const void*)k_rp_scatter<1024, false, H, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-        hipLaunchKernelGGL((k_rp_scatter<1024, false, H, false, 2>), dim3(grid), dim3(1024), rp_scatter_lds<1024>(P, false, 2), ctx->stream, hs, n, P, ntiles, (const uint32_t*)counts->ptr, cols); }
-    }
     else if (big) RP_LAUNCH(1024, false) else RP_LAUNCH(512, false)
 #undef RP_LAUNCH
     KERNEL_CHECK(); }

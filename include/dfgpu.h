@@ -109,29 +109,28 @@ DFGPU_API dfgpu_status dfgpu_ctx_synchronize(dfgpu_ctx *ctx);
  * the same path on 64-bit key hashes, every emitted pair verified in the columns; "join_partitioned_hash_mask" (0 = all bits; tests) == bits of the hash that are kept;
  * "agg_partitioned" (1/0), "agg_partitioned_min_rows", "agg_partitioned_force" (1 = skip the sample's verdict; tests) == let the plan layer's
  * AggregateExec pre-aggregate large batches of high-cardinality unclustered keys partition by partition out of LDS (dfgpu_agg_preaggregate);
+ * "agg_pack_estimate_min_rows" (default 2^22) == when the pre-aggregation packs several key columns into one word, batches of at least this many rows take the value ranges from
+ * every (n / 2^19)-th row, widened, and check every row against them while packing (a row outside repeats the step with exact ranges; same groups);
  * "agg_preaggregate_distinct" (read only) == 1 when the last dfgpu_agg_preaggregate call on this ctx emitted every key in exactly one partial row;
  * "mailbox_readback" (1/0) == the host reads device words (counts, ranges, error flags) through a pinned mailbox -- a one-workgroup kernel posts them with a sequence number, the host
  * polls -- instead of a device-to-host copy followed by a stream synchronisation (same values; the switch exists for A/B runs);
  * "join_selection_output" (1/0) == let the plan layer's HashJoinExec answer an Inner join whose build side contributes key columns only with the probe batch under a selection
  * (dfgpu_join_probe_selection) when the operator above fuses selections (rows and row order identical); "join_lazy_build_rows" (1/0) == build rows of a deferred probe looked up on demand;
- * "join_bitmap_partitioned" (0/1, default 0), "join_bitmap_partitioned_min_rows" == probe a membership bitmap larger than an L2 by key range when a sample finds the probe keys
- * unclustered (pairs identical; measured slower than the plain probe on MI355X, kept for A/B);
  * "group_lazy_keys" (1/0) == a run-numbered first batch keeps its group keys as (key columns, first rows) until somebody needs them stored (dfgpu_groups_emit_deferred);
  * "agg_order_inverse_map" (1/0) == first-seen order of millions of pre-aggregated partial rows through an inverse map over the input rows instead of sort passes (same order);
  * "sort_fused_small_passes" (1/0) == sorts below 2^20 rows fold every pass's offset scan into its scatter (identical indices);
  * "sort_packed_keys" (1/0) == let sort_to_indices sort large inputs over fixed-width keys through range-packed 64-bit keys (identical indices);
  * "sort_estimate_ranges" (1/0) == from 2^22 rows on, take those ranges from a sample and check them while packing (a miss repeats the step with exact ranges; identical indices);
+ * "sort_packed_min_rows" (default 2^20, at least 2) == smallest input that takes the packed keys (below: byte planes of the encoded keys; identical indices);
  * "sort_onesweep_rows" (16 / 8 / 0, default 16), "sort_onesweep_min_rows" (default 2^20), "sort_onesweep_fused_finish" (1/0) == packed-key sorts whose key and row number share
  * one 64-bit word run every LSD pass as ONE launch (tile offsets by look-back over the digit counts the tiles in front have published; histograms counted while the words are
  * encoded; tiles of 16 x 512 rows from 2 M rows on, else 8 x 512; 0 = the three-launch passes), the last pass writing row numbers and rebuilt key columns itself (identical indices);
  * "sort_topk_words_min_rows" (default 2^23) == a sort with fetch <= n / 16 over at least this many rows whose keys pack selects on the packed keys (radix select, then the
  * few candidates sorted) instead of on byte planes (identical indices); "sort_one_block_max_rows" (default 8192, 0 = off) == byte-plane sorts of at most this many rows run
- * every pass inside one launch of one workgroup (identical indices); "sort_payload_in_last_pass" (0/1, default 0) == dfgpu_sort_take gathers payload columns in the sort's last
- * pass (measured slower than the gather afterwards; kept for A/B);
- * "partition_two_round_staging" (0/1, default 0) == the radix partition into 513 .. 2048 partitions stages every column in two rounds of half a tile, two workgroups per CU
- * (same rows in the same partitions; measured slower, kept for A/B);
+ * every pass inside one launch of one workgroup (identical indices);
  * "memory_limit" (bytes, 0 = none) == live device memory this ctx may hold; an allocation beyond it fails with DFGPU_RESOURCES_EXHAUSTED and the
  * message of MemoryPool::try_grow (≙ RuntimeConfig::with_memory_limit, execution/src/runtime_env.rs); "live_bytes" / "cached_bytes" (read only);
+ * "trim_cache" (set only, value ignored) == wait for the ctx stream to drain, then give the freed blocks the ctx keeps for reuse back to the driver (≙ MemoryPool::shrink; cached_bytes = 0);
  * "agg_spill_state_bytes" (0 = never) == the state size (group table + accumulators) above which AggregateExec spills to host memory (non-Partial modes,
  * row_hash.rs:667-705) or emits early (Partial, :720-733) -- the reservation a MemoryPool would grant the operator; "agg_spill_ranges" (16) == key ranges a spill is cut into;
  * "sort_spill_bytes" (0 = never) == bytes of input SortExec keeps on the device before it sorts them and spills the sorted run to host memory (ExternalSorter,
@@ -430,14 +429,6 @@ DFGPU_API dfgpu_status dfgpu_sort_to_indices(dfgpu_ctx *ctx, const dfgpu_array *
  * packed keys -- fixed-width key columns without NULLs on the packed-key path -- else NULL; sort_batch's take() (sorts/sort.rs:598-603) of such a column is then free. */
 DFGPU_API dfgpu_status dfgpu_sort_to_indices_keys(dfgpu_ctx *ctx, const dfgpu_array *const *cols, const uint8_t *descending, const uint8_t *nulls_first, int32_t k, int64_t fetch,
                                                   dfgpu_array **out, dfgpu_array **out_sorted);
-/* sort_batch in one call (sorts/sort.rs:584-609: lexsort_to_indices, then take() of every column): dfgpu_sort_to_indices_keys plus the batch's other columns.
- * out_payload[c] (n_payload entries) = take(payload[c], *out) when the sort's last pass could gather it while it writes the result -- a fixed-width column of 4 / 8 / 16
- * bytes without NULLs, at most four of them, on the one-launch-per-pass path (keys and row number in one word, 2^20 rows or more) -- else NULL and the caller takes the
- * column through *out as before.  Context option "sort_payload_in_last_pass" (default 0): measured on MI355X the fused gather is slower than the separate one (100 M rows, one
- * 8-byte column: 6.36 ms for passes + gather against 3.89 + 2.13 ms), so by default every entry of out_payload is NULL; the entry point stays so that a caller states the
- * whole of sort_batch in one call. */
-DFGPU_API dfgpu_status dfgpu_sort_take(dfgpu_ctx *ctx, const dfgpu_array *const *cols, const uint8_t *descending, const uint8_t *nulls_first, int32_t k, int64_t fetch,
-                                       const dfgpu_array *const *payload, int32_t n_payload, dfgpu_array **out, dfgpu_array **out_sorted, dfgpu_array **out_payload);
 
 /* ------------------------------------------------------------------ a14: RepartitionExec */
 /* ≙ BatchPartitioner::partition_iter, Hash(exprs, n) (repartition/mod.rs:148-221): destination =

@@ -8,6 +8,15 @@ import pyarrow as pa
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
+def documented_options():
+    """The quoted names of the dfgpu_ctx_set_option documentation block in include/dfgpu.h: every context option."""
+    import re
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dfgpu.h")) as f:
+        text = f.read()
+    block = text[text.index("/* options:"):text.index("DFGPU_API dfgpu_status dfgpu_ctx_set_option(")]
+    return sorted(set(re.findall(r'"([a-z0-9_]+)"', block)))
+
+
 def load_golden(name):
     with open(os.path.join(GOLDEN, name)) as f:
         return json.load(f)

@@ -486,9 +486,9 @@ def test_chunked_probe_reads_back_once_per_probe_batch(ctx, jt):
 
 
 @pytest.mark.parametrize("shape", ["unclustered", "unclustered_masked_nullable", "clustered", "many_matches"])
-def test_bitmap_probe_by_key_range_of_unclustered_keys(ctx, shape):
-    """Probe keys in no order against a build whose membership bitmap is larger than an L2 (pjoin.hip bp_probe): the batch is split by key range and every partition tests its
-    slice of the bitmap; clustered keys and batches with many matches keep the streaming probe (the sample decides).  Pairs equal the oracle's, in order, either way."""
+def test_bitmap_probe_larger_than_l2(ctx, shape):
+    """A build whose membership bitmap (8.6 MB) is larger than an L2, probed by keys in no order (with a mask and NULLs), in key order, and with nearly every key a match:
+    the pairs equal the oracle's, in order."""
     import dfgpu
     rng = np.random.default_rng(len(shape))
     nb, step, npr = 4_300_000, 16, 3_000_000
@@ -504,14 +504,7 @@ def test_bitmap_probe_by_key_range_of_unclustered_keys(ctx, shape):
         mask = rng.random(npr) < 0.6; valid = rng.random(npr) < 0.9
     table = dfgpu.JoinTable(ctx, [ctx.from_arrow(pa.array(b))])
     pa_p = pa.array(p, mask=None if valid is None else ~valid)
-    ctx.set_option("join_bitmap_partitioned", 1); ctx.set_option("join_bitmap_partitioned_min_rows", 1 << 20)       # off by default (measured slower than the random probes at SF100)
-    ctx.profile_select(None); ctx.profile_enable(True); ctx.profile_read()
-    try:
-        bi, pi = table.probe([ctx.from_arrow(pa_p)], mask=None if mask is None else ctx.from_arrow(pa.array(mask)))
-        prof = ctx.profile_read()
-    finally:
-        ctx.profile_enable(False); ctx.set_option("join_bitmap_partitioned_min_rows", 1 << 24); ctx.set_option("join_bitmap_partitioned", 0)
-    assert ("bp_probe" in prof) == shape.startswith("unclustered"), sorted(prof)
+    bi, pi = table.probe([ctx.from_arrow(pa_p)], mask=None if mask is None else ctx.from_arrow(pa.array(mask)))
     ok = np.ones(npr, bool) if mask is None else (mask & valid)
     pos = np.searchsorted(b, p); pos[pos >= nb] = nb - 1
     hit = ok & (b[pos] == p)

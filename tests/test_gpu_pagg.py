@@ -554,10 +554,9 @@ def test_the_mark_stays_on_the_sorts_own_copy_of_the_aggregation(ctx):
     assert np.array_equal(ks, cat(plain, 0).to_numpy()[order]) and np.array_equal(ss, cat(plain, 1).to_numpy()[order])
 
 
-def test_many_partition_scatter_staged_in_two_rounds(ctx):
-    """513 .. 2048 partitions: the 8192-row tile's columns staged in two rounds of half a tile (two workgroups per CU; option partition_two_round_staging, off by default --
-    measured slower) give the same merged groups and states as the whole tile staged at once and as the oracle's row-by-row update; a Decimal128 argument (two 8-byte halves per row), a
-    nullable Int64 one (flag byte column) and an Int32 one cast on the way."""
+def test_many_partition_scatter(ctx):
+    """513 .. 2048 partitions (the 1024-thread scatter of an 8192-row tile): the merged groups and states equal the oracle's row-by-row update; a Decimal128 argument (two 8-byte
+    halves per row), a nullable Int64 one (flag byte column) and an Int32 one cast on the way."""
     import dfgpu
     from dfgpu import capi
     n, card = 3_000_000, 1_500_000
@@ -573,31 +572,20 @@ def test_many_partition_scatter_staged_in_two_rounds(ctx):
     # six accumulator cells leave 2048 table slots per partition: partitions flush before their end, a key comes back in several partial rows, and where the cuts fall
     # depends on the order the LDS-atomic ranks gave the rows -- so the comparison is made after intern + merge_batch (what the plan layer does), not on the partial rows
     in_types = [(capi.INT64, 0, 0), (capi.INT64, 0, 0), (capi.DECIMAL128, 30, 2), (capi.FLOAT64, 0, 0), (capi.INT64, 0, 0)]
-    out = []
-    for on in (1, 0):
-        ctx.set_option("partition_two_round_staging", on)
-        try:
-            with forced(ctx, force=1) as f:
-                pk, states = dfgpu.agg_preaggregate(ctx, kd, kinds, vals, casts=casts)
-                assert "pa_scatter" in f.kernels()
-        finally:
-            ctx.set_option("partition_two_round_staging", 0)
-        gv = dfgpu.GroupValues(ctx, 1); gids = gv.intern([pk]); res = []
-        for kind, (t, p_, s_), st in zip(kinds, in_types, states):
-            acc = dfgpu.GroupsAccumulator(ctx, kind, t, p_, s_); acc.merge_batch(st, gids, None, len(gv)); res.append(acc.evaluate().to_arrow())
-        out.append((gv.emit()[0].to_arrow(), res))
-    (k1, r1), (k0, r0) = out
-    o1, o0 = np.argsort(k1.to_numpy(), kind="stable"), np.argsort(k0.to_numpy(), kind="stable")          # group order follows the first partial row of a key: compare by key
-    assert np.array_equal(k1.to_numpy()[o1], k0.to_numpy()[o0]) and len(k1) == len(np.unique(k1.to_numpy()))
-    for a, b in zip(r1, r0):
-        x, y = a.take(pa.array(o1)), b.take(pa.array(o0))
-        if pa.types.is_floating(x.type):
-            assert x.is_null().equals(y.is_null()) and np.allclose(x.fill_null(0).to_numpy(), y.fill_null(0).to_numpy(), rtol=FLOAT_RTOL, atol=0.0)
-        else:
-            assert x.equals(y)
-    # against the oracle's row-by-row update: SUM / MAX of the nullable column and COUNT(*) exact
-    wk, want = run_oracle(key, [("SUM", vi), ("MAX", vi), ("COUNT", None)])
+    with forced(ctx, force=1) as f:
+        pk, states = dfgpu.agg_preaggregate(ctx, kd, kinds, vals, casts=casts)
+        assert "pa_scatter" in f.kernels()
+    gv = dfgpu.GroupValues(ctx, 1); gids = gv.intern([pk]); r1 = []
+    for kind, (t, p_, s_), st in zip(kinds, in_types, states):
+        acc = dfgpu.GroupsAccumulator(ctx, kind, t, p_, s_); acc.merge_batch(st, gids, None, len(gv)); r1.append(acc.evaluate().to_arrow())
+    k1 = gv.emit()[0].to_arrow()
+    o1 = np.argsort(k1.to_numpy(), kind="stable")          # group order follows the first partial row of a key: compare by key
+    assert len(k1) == len(np.unique(k1.to_numpy()))
+    # against the oracle's row-by-row update: SUM / MAX of the nullable column and COUNT(*) exact, the Decimal128 SUM exact
+    wk, want = run_oracle(key, [("SUM", vi), ("MAX", vi), ("COUNT", None), ("SUM", vd)])
     ow = np.argsort(wk.to_numpy(), kind="stable")
     assert np.array_equal(k1.to_numpy()[o1], wk.to_numpy()[ow])
     for got, w in zip((r1[0], r1[1], r1[4]), want):
         assert got.take(pa.array(o1)).cast(pa.int64()).equals(w.take(pa.array(ow)).cast(pa.int64()))
+    dec = pa.decimal128(38, 2)
+    assert r1[2].take(pa.array(o1)).cast(dec).equals(want[3].take(pa.array(ow)).cast(dec))

@@ -135,3 +135,26 @@ def test_read_backs_through_the_mailbox_and_through_a_copy_agree(ctx):
             ctx.set_option("mailbox_readback", 1)
     for x, y in zip(out[1], out[0]):
         assert np.array_equal(x, y)
+
+
+def test_every_documented_option_reads_back_what_it_holds(ctx):
+    """Every context option include/dfgpu.h documents can be read; writing back what it reads leaves it unchanged (the clamps and checks accept their own values), and
+    the read-only ones refuse a write.  trim_cache (an action) and defer_flag_checks (a nesting depth) are left out.  An unknown name is refused both ways."""
+    import dfgpu
+    from helpers import documented_options
+    read_only = {"live_bytes", "cached_bytes", "agg_preaggregate_distinct"}
+    names = [k for k in documented_options() if k not in ("trim_cache", "defer_flag_checks")]
+    assert read_only <= set(names) and len(names) > 40
+    for k in names:
+        v = ctx.get_option(k)
+        if k in read_only:
+            with pytest.raises(dfgpu.DfgpuError) as e:
+                ctx.set_option(k, v)
+            assert e.value.kind == "InvalidArgument", k
+        else:
+            ctx.set_option(k, v)
+            assert ctx.get_option(k) == v, k
+    for call in (lambda: ctx.get_option("no_such_option"), lambda: ctx.set_option("no_such_option", 1)):
+        with pytest.raises(dfgpu.DfgpuError) as e:
+            call()
+        assert e.value.kind == "InvalidArgument" and "unknown option 'no_such_option'" in str(e.value)
