@@ -219,6 +219,7 @@ __global__ void __launch_bounds__(BLOCK) k_arith(int op, Operand l, Operand r, i
       case DFGPU_OP_MUL: ok = mul128_checked(x, y, &v); break;
       default:
         if (y == 0) { raise(flags, DFGPU_FLAG_DIV_ZERO); v = 0; }
+        else if (y == -1 && x == I128_MIN) ok = false;           // checked_div / checked_rem: MIN / -1 and MIN % -1 overflow
         else { i128 rem; i128 q = sdiv128(x, y, &rem); v = op == DFGPU_OP_DIV ? q : rem; }
     }
     if (!ok) { raise(flags, DFGPU_FLAG_OVERFLOW); v = 0; }
@@ -257,6 +258,7 @@ __device__ inline bool dec_core(int op, i128 x, i128 y, DecRule dr, i128* v, uin
     case DFGPU_OP_MUL: ok = mul128_checked(x, y, v); break;
     default:
       if (y == 0) { raise(flags, DFGPU_FLAG_DIV_ZERO); *v = 0; }
+      else if (y == -1 && x == I128_MIN) ok = false;
       else { i128 rem; i128 q = sdiv128(x, y, &rem); *v = op == DFGPU_OP_DIV ? q : rem; }
   }
   if (!ok) { raise(flags, DFGPU_FLAG_OVERFLOW); *v = 0; }
@@ -291,20 +293,22 @@ __global__ void __launch_bounds__(BLOCK) k_cast(ColView c, int64_t n, int32_t to
     int from = c.type; bool err = false;
     bool from_int = from == DFGPU_BOOL || from == DFGPU_DATE32 || (from >= DFGPU_INT8 && from <= DFGPU_UINT64);
     bool to_int = to == DFGPU_DATE32 || (to >= DFGPU_INT8 && to <= DFGPU_UINT64);
-    i128 iv = 0; double fv = 0;
+    i128 iv = 0; double fv = 0; float ff = 0; bool f32_direct = false;     // f32_direct: ff is the Float32 result, rounded once
     if (ok) {
       if (from_int) {
         i128 v = cell_int(c, r);
         if (to_int) { iv = v; err = wrap_to(to, v) != v; }
-        else if (to == DFGPU_FLOAT64 || to == DFGPU_FLOAT32) fv = (double)(int64_t)v + (from == DFGPU_UINT64 && v > (i128)INT64_MAX ? 18446744073709551616.0 : 0.0);
+        else if (to == DFGPU_FLOAT64) fv = from == DFGPU_UINT64 ? (double)(uint64_t)v : (double)(int64_t)v;     // `v as f64`: one rounding
+        else if (to == DFGPU_FLOAT32) { ff = from == DFGPU_UINT64 ? (float)(uint64_t)v : (float)(int64_t)v; f32_direct = true; }   // `v as f32`, not via f64
         else if (to == DFGPU_DECIMAL128) { err = !mul128_checked(v, pow10_i128(s), &iv) || !decimal_fits(iv, p); }
         else if (to == DFGPU_BOOL) bit = v != 0;
       } else if (from == DFGPU_FLOAT32 || from == DFGPU_FLOAT64) {
         double f = cell_f64(c, r);
         if (to == DFGPU_FLOAT64 || to == DFGPU_FLOAT32) fv = f;
         else if (to_int) {
-          if (f != f || f <= -9.3e18 || f >= 1.85e19) err = true;
-          else { iv = f < 0 ? (i128)(int64_t)f : (i128)(uint64_t)f; err = wrap_to(to, iv) != iv; }
+          // NumCast: truncate toward zero, in range or an error.  [-2^63, 2^64) converts exactly (and defined) through int64 / uint64
+          if (!(f >= -9223372036854775808.0 && f < 18446744073709551616.0)) err = true;            // NaN fails the test too
+          else { iv = f < 9223372036854775808.0 ? (i128)(int64_t)f : (i128)(uint64_t)f; err = wrap_to(to, iv) != iv; }
         } else if (to == DFGPU_DECIMAL128) {
           double m = round(f * pow10_f64(s));
           if (m != m || fabs(m) >= 1.7e38) err = true;
@@ -319,14 +323,13 @@ __global__ void __launch_bounds__(BLOCK) k_cast(ColView c, int64_t n, int32_t to
                  if (v >= 0 && rem >= half) d += 1; else if (v < 0 && rem <= -half) d -= 1; iv = d; }
           if (!err) err = !decimal_fits(iv, p);
         } else if (to == DFGPU_FLOAT64 || to == DFGPU_FLOAT32) {
-          bool neg = v < 0; u128 u = neg ? (u128)0 - (u128)v : (u128)v;
-          double d = (double)(uint64_t)(u >> 64) * 18446744073709551616.0 + (double)(uint64_t)u; fv = (neg ? -d : d) / pow10_f64(fs);
+          fv = i128_to_f64(v) / pow10_f64(fs);                          // `x as f64 / 10^s` (Float32: that, then `as f32`)
         } else if (to_int) { iv = sdiv128(v, pow10_i128(fs), nullptr); err = wrap_to(to, iv) != iv; }
       }
-      if (err) { if (emask == nullptr || bit_get(emask, i)) atomicOr(flags, DFGPU_FLAG_CAST); iv = 0; fv = 0; }
+      if (err) { if (emask == nullptr || bit_get(emask, i)) atomicOr(flags, DFGPU_FLAG_CAST); iv = 0; fv = 0; ff = 0; }
     }
     if (to == DFGPU_FLOAT64) ((double*)out)[i] = fv;
-    else if (to == DFGPU_FLOAT32) ((float*)out)[i] = (float)fv;
+    else if (to == DFGPU_FLOAT32) ((float*)out)[i] = f32_direct ? ff : (float)fv;
     else if (to != DFGPU_BOOL) store_int(out, to, i, iv);
   }
   if (to == DFGPU_BOOL) { uint64_t m = ballot64(bit); if (lane_id() == 0 && (i >> 6) < ((n + 63) >> 6)) ((uint64_t*)out)[i >> 6] = m; }

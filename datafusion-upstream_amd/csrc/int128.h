@@ -9,6 +9,8 @@ __host__ __device__ inline i128 pow10_i128(int k) { i128 r = 1; for (int i = 0; 
 
 __host__ __device__ inline double pow10_f64(int k) { double r = 1.0; for (int i = 0; i < k; i++) r *= 10.0; return r; }
 
+constexpr i128 I128_MIN = (i128)((u128)1 << 127);
+
 __device__ inline int clz128(u128 x) { uint64_t hi = (uint64_t)(x >> 64), lo = (uint64_t)x; return hi ? __clzll(hi) : 64 + (lo ? __clzll(lo) : 64); }
 // unsigned 128 / 128 -> quotient, remainder (d != 0)
 __device__ inline u128 udivmod128(u128 n, u128 d, u128* rem) {
@@ -53,6 +55,17 @@ __device__ inline bool mul128_checked(i128 a, i128 b, i128* out) {
   else { if (r >> 127) return false; *out = (i128)r; }
   return true;
 }
+// u128 -> f64 rounded once to nearest-even, as Rust's `as f64`: the top 64 bits with the dropped bits folded into a sticky LSB
+// convert exactly where it matters (the sticky bit lies below f64's rounding position), then scale by a power of two
+__device__ inline double u128_to_f64(u128 u) {
+  const uint64_t hi = (uint64_t)(u >> 64), lo = (uint64_t)u;
+  if (!hi) return (double)lo;
+  const int sh = 64 - __clzll(hi);                                   // 1..64 low bits are dropped
+  const uint64_t top = (uint64_t)(u >> sh) | ((lo << (64 - sh)) != 0 ? 1u : 0u);
+  return ldexp((double)top, sh);
+}
+__device__ inline double i128_to_f64(i128 v) { return v < 0 ? -u128_to_f64((u128)0 - (u128)v) : u128_to_f64((u128)v); }
+
 __device__ inline bool decimal_fits(i128 v, int precision) { i128 lim = pow10_i128(precision); return v > -lim && v < lim; }
 
 __device__ inline i128 load_i128(const void* p, int64_t i) { const uint64_t* q = (const uint64_t*)p + 2 * i; return (i128)(((u128)q[1] << 64) | q[0]); }

@@ -119,7 +119,8 @@ int dfo_binary(int op, const dfo_array *l, int ls, const dfo_array *r, int rs, d
         default:
           ov = __builtin_mul_overflow(xv, lm, &xv) | __builtin_mul_overflow(yv, rm, &yv);
           if (!ov) { if (yv == 0) { dfo_builder_free(b); dfo_set_error("Divide by zero error"); return 1; }
-            res = op == DFO_OP_DIV ? xv / yv : xv % yv; }
+            if (yv == -1 && xv == (i128)((u128)1 << 127)) ov = 1;       /* i128::checked_div / checked_rem: MIN / -1 and MIN % -1 overflow */
+            else res = op == DFO_OP_DIV ? xv / yv : xv % yv; }
       }
       if (ov) { dfo_builder_free(b); dfo_set_error("Arithmetic overflow: decimal op %d", op); return 1; }
       append_int(b, res);
