@@ -53,7 +53,7 @@ struct TR {
 };
 
 enum { PT_BOOLEAN = 0, PT_INT32 = 1, PT_INT64 = 2, PT_INT96 = 3, PT_FLOAT = 4, PT_DOUBLE = 5, PT_BYTE_ARRAY = 6, PT_FLBA = 7 };
-enum { ENC_PLAIN = 0, ENC_PLAIN_DICT = 2, ENC_RLE = 3, ENC_BIT_PACKED = 4, ENC_RLE_DICT = 8 };
+enum { ENC_PLAIN = 0, ENC_PLAIN_DICT = 2, ENC_RLE = 3, ENC_BIT_PACKED = 4, ENC_DELTA_BP = 5, ENC_DELTA_LBA = 6, ENC_DELTA_BA = 7, ENC_RLE_DICT = 8, ENC_BSS = 9 };
 enum { CODEC_NONE = 0, CODEC_SNAPPY = 1, CODEC_ZSTD = 6, CODEC_LZ4_RAW = 7 };
 enum { PG_DATA = 0, PG_INDEX = 1, PG_DICT = 2, PG_DATA_V2 = 3 };
 
@@ -257,7 +257,8 @@ struct PqPage {
   int64_t row_start;
   uint32_t size; int32_t num_values; int32_t dict_enc; int32_t lvl_mode /*0 none, 1 u32-length prefixed (v1), 2 lvl_len bytes (v2)*/; int32_t lvl_len; int32_t decode_levels;
   int32_t dict_base, dict_count;
-  uint32_t str_base;                                  // PLAIN byte arrays: first slot of this page in PqCol::str_pos, its index in PqCol::str_cnt is the page's own
+  uint32_t str_base;                                  // PLAIN byte arrays: first slot of this page in PqCol::str_pos, its index in PqCol::str_cnt is the page's own; DELTA pages: first slot of the page's per-value scratch
+  int32_t enc;                                        // ENC_DELTA_* / ENC_BSS: the page goes to its encoding's own kernel; 0 otherwise (fills the struct's tail padding)
 };
 struct PqCol {
   int32_t mode, conv, wp, wo;
@@ -544,6 +545,347 @@ __global__ void __launch_bounds__(BLOCK) k_pq_bytes_to_bits(const uint8_t* in, i
   if (lane_id() == 0 && (i >> 6) < ((n + 63) >> 6)) bits[i >> 6] = m;
 }
 
+// ================================================================================ DELTA_BINARY_PACKED / DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY / BYTE_STREAM_SPLIT
+// Kernels of their own (k_pq_decode's registers stay what they are).  Every page kernel below decodes the definition levels of a tile with
+// rle_fill + block_exclusive_sum exactly as k_pq_decode does; the encoded streams hold the non-null values only.
+//
+// DELTA_BINARY_PACKED: header <block size> <miniblocks per block> <total count> <zigzag first value>, then blocks <zigzag min delta> <one bit
+// width per miniblock> <packed miniblocks>.  One lane walks the block headers into an LDS table of the miniblocks a tile needs (a varint and
+// M bytes per block, the bodies are skipped); every lane unpacks its deltas from the table with unaligned loads, adds the block's min delta,
+// and the tile is one workgroup inclusive scan in wrapping u64 arithmetic (truncated to u32 for INT32), carried from tile to tile.  Miniblocks
+// of the last block past the last value have no body and any bit width: the walk never reaches them.
+constexpr int DBP_MAXMB = 80;                   // a tile needs at most PQ_TILE / 32 + 1 miniblocks
+struct DbpState {
+  const uint8_t* p; const uint8_t* end; const uint8_t* widths; uint64_t first, blk_min, last_min; const uint8_t* last_ptr;
+  uint32_t vpm, M, total, maxw, mi, next_delta, last_first, last_w, bad;
+};
+struct DbpTable { uint64_t mind[DBP_MAXMB]; const uint8_t* ptr[DBP_MAXMB]; uint32_t w[DBP_MAXMB]; uint32_t first, n; };
+
+__device__ inline bool pq_uvarint(const uint8_t*& p, const uint8_t* end, uint64_t& v) {
+  v = 0;
+  for (int sh = 0; sh < 64; sh += 7) { if (p >= end) return false; const uint8_t b = *p++; v |= (uint64_t)(b & 0x7f) << sh; if (!(b & 0x80)) return true; }
+  return false;
+}
+__device__ inline uint64_t pq_unzig(uint64_t z) { return (z >> 1) ^ (0ull - (z & 1)); }
+// the stream header (one lane); a malformed header or a count above max_total sets bad
+__device__ inline void dbp_begin(DbpState& s, const uint8_t* p, const uint8_t* end, uint32_t maxw, uint32_t max_total) {
+  uint64_t bs, M, tot, fz; s.bad = 1; s.p = p; s.end = end;
+  if (!pq_uvarint(p, end, bs) || !pq_uvarint(p, end, M) || !pq_uvarint(p, end, tot) || !pq_uvarint(p, end, fz)) return;
+  if (bs == 0 || bs % 128 || bs > (1u << 24) || M == 0 || bs % M || (bs / M) % 32 || tot > max_total) return;
+  s.p = p; s.first = pq_unzig(fz); s.vpm = (uint32_t)(bs / M); s.M = (uint32_t)M; s.total = (uint32_t)tot; s.maxw = maxw;
+  s.mi = s.M; s.next_delta = 0; s.last_first = 0xFFFFFFFFu; s.bad = 0;
+}
+// the miniblocks that hold deltas [d0, d1) into t (one lane); the tiles ask for consecutive ranges
+__device__ inline void dbp_parse(DbpState& s, uint32_t d0, uint32_t d1, DbpTable& t) {
+  uint32_t n = 0; t.first = d0 - d0 % s.vpm;
+  if (s.last_first == t.first) { t.mind[0] = s.last_min; t.ptr[0] = s.last_ptr; t.w[0] = s.last_w; n = 1; }
+  else if (s.next_delta != t.first) { s.bad = 1; t.n = 0; return; }
+  while (s.next_delta < d1) {
+    if (n >= (uint32_t)DBP_MAXMB) { s.bad = 1; break; }
+    if (s.mi == s.M) {
+      uint64_t z; if (!pq_uvarint(s.p, s.end, z) || (uint64_t)(s.end - s.p) < s.M) { s.bad = 1; break; }
+      s.blk_min = pq_unzig(z); s.widths = s.p; s.p += s.M; s.mi = 0;
+    }
+    const uint32_t w = s.widths[s.mi++];
+    if (w > s.maxw) { s.bad = 1; break; }           // only miniblocks with values get here
+    t.mind[n] = s.blk_min; t.ptr[n] = s.p; t.w[n] = w; n++;
+    s.last_first = s.next_delta; s.last_min = s.blk_min; s.last_ptr = s.p; s.last_w = w;
+    const uint64_t bytes = (uint64_t)s.vpm * w / 8;
+    s.p = bytes > (uint64_t)(s.end - s.p) ? s.end : s.p + bytes;         // a body cut short: the lanes that need the missing bits flag the page
+    s.next_delta += s.vpm;
+  }
+  t.n = n;
+}
+// delta d (from the table): min delta + the w-bit field; widths reach 64, so the field may span 9 bytes
+__device__ inline uint64_t dbp_delta(const DbpState& s, const DbpTable& t, uint32_t d, bool& bad) {
+  const uint32_t r = d - t.first, k = r / s.vpm, j = r - k * s.vpm, w = t.w[k];
+  uint64_t x = 0;
+  if (w) {
+    const uint8_t* base = t.ptr[k]; const uint64_t bit = (uint64_t)j * w; const uint8_t* q = base + (bit >> 3); const uint32_t sh = (uint32_t)(bit & 7);
+    if (((bit + w + 7) >> 3) > (uint64_t)(s.end - base)) { bad = true; return 0; }
+    x = ld64u(q) >> sh;
+    if (sh + w > 64) x |= (uint64_t)q[8] << (64 - sh);
+    if (w < 64) x &= (1ull << w) - 1ull;
+  }
+  return t.mind[k] + x;
+}
+// values [c, c + nn) of the stream into out[0, nn): every lane takes 8 in a row; carry is value c - 1 (block-uniform).  Returns false on a malformed stream (block-uniform).
+__device__ inline bool dbp_tile(DbpState& s, DbpTable& t, uint32_t c, uint32_t nn, uint64_t* out, uint64_t* scan64, uint64_t& carry) {
+  if ((uint64_t)c + nn > s.total) return false;
+  if (nn == 0) return true;
+  const uint32_t d0 = c ? c - 1 : 0, d1 = c + nn - 1;
+  __syncthreads();
+  if (threadIdx.x == 0 && d1 > d0) dbp_parse(s, d0, d1, t);
+  __syncthreads();
+  if (s.bad) return false;
+  bool bad = false; uint64_t loc[8], sum = 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    const uint32_t idx = threadIdx.x * 8 + j, i = c + idx; uint64_t term = 0;
+    if (idx < nn) term = i == 0 ? s.first : dbp_delta(s, t, i - 1, bad);
+    loc[j] = term; sum += term;
+  }
+  uint64_t tot; uint64_t run = carry + block_exclusive_sum<uint64_t>(sum, scan64, &tot);
+#pragma unroll
+  for (int j = 0; j < 8; j++) { const uint32_t idx = threadIdx.x * 8 + j; run += loc[j]; if (idx < nn) out[idx] = run; }
+  carry += tot;
+  return !__syncthreads_or(bad ? 1 : 0);
+}
+
+// page prologue (one lane): the level stream and where the values start
+__device__ inline bool pq_page_start(const PqPage& pg, RleState& lv, const uint8_t*& vptr) {
+  const uint8_t* p = pg.data; lv.run_left = 0; lv.bad = 0; lv.bw = 1;
+  if (pg.lvl_mode == 1) {
+    if (pg.size < 4) return false;
+    const uint32_t L = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    if (L > pg.size - 4) return false;
+    lv.p = p + 4; lv.end = p + 4 + L; p += 4 + L;
+  } else if (pg.lvl_mode == 2) { if ((uint32_t)pg.lvl_len > pg.size) return false; lv.p = p; lv.end = p + pg.lvl_len; p += pg.lvl_len; }
+  vptr = p; return true;
+}
+// levels of one tile -> pos16 (index among the tile's non-null values, 0xFFFF = NULL) and the non-null count; false when the level stream ends early
+__device__ inline bool pq_tile_levels(RleState& lv, RunTable& rt, uint32_t tl, uint32_t* lvals, uint16_t* pos16, uint32_t* scan_lds, uint32_t& nn) {
+  if (!rle_fill(lv, rt, tl, lvals)) return false;
+  uint32_t cnt = 0, f8 = 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++) { uint32_t idx = threadIdx.x * 8 + j; if (idx < tl && lvals[idx] == 1u) { f8 |= 1u << j; cnt++; } }
+  uint32_t tot; uint32_t base = block_exclusive_sum<uint32_t>(cnt, scan_lds, &tot); nn = tot;
+#pragma unroll
+  for (int j = 0; j < 8; j++) { uint32_t idx = threadIdx.x * 8 + j; if (idx < tl) pos16[idx] = (f8 >> j) & 1 ? (uint16_t)base++ : (uint16_t)0xFFFF; }
+  __syncthreads();
+  return true;
+}
+
+// an integer of the page's physical width to the Arrow value (the CONV_* of store_fixed; 0 for a NULL slot)
+__device__ inline void store_int(const PqCol& c, int64_t row, uint64_t x) {
+  switch (c.conv) {
+    case CONV_COPY4: ((uint32_t*)c.out)[row] = (uint32_t)x; break;
+    case CONV_COPY8: ((uint64_t*)c.out)[row] = x; break;
+    case CONV_4TO1: ((uint8_t*)c.out)[row] = (uint8_t)x; break;
+    case CONV_4TO2: ((uint16_t*)c.out)[row] = (uint16_t)x; break;
+    case CONV_I32_DEC: { int64_t v = (int64_t)(int32_t)(uint32_t)x; ((uint64_t*)c.out)[2 * row] = (uint64_t)v; ((uint64_t*)c.out)[2 * row + 1] = (uint64_t)(v >> 63); break; }
+    case CONV_I64_DEC: case CONV_FLBA_DEC: { int64_t v = (int64_t)x; ((uint64_t*)c.out)[2 * row] = (uint64_t)v; ((uint64_t*)c.out)[2 * row + 1] = (uint64_t)(v >> 63); break; }
+    default: break;
+  }
+}
+
+// DELTA_BINARY_PACKED INT32 / INT64 pages: one workgroup per page
+__global__ void __launch_bounds__(PQ_NT) k_pq_delta(const PqPage* __restrict__ pages, PqCol col, uint32_t* flags) {
+  __shared__ RleState lv; __shared__ RunTable rt; __shared__ DbpState ds; __shared__ DbpTable dt;
+  __shared__ uint32_t lvals[PQ_TILE]; __shared__ uint16_t pos16[PQ_TILE]; __shared__ uint64_t v64[PQ_TILE];
+  __shared__ uint64_t scan64[4]; __shared__ uint32_t scan_lds[4]; __shared__ uint32_t s_bad;
+  const PqPage pg = pages[blockIdx.x]; const int tid = threadIdx.x;
+  if (tid == 0) {
+    const uint8_t* vptr; s_bad = 1;
+    if (pq_page_start(pg, lv, vptr)) { dbp_begin(ds, vptr, pg.data + pg.size, col.wp == 4 ? 32 : 64, (uint32_t)pg.num_values); s_bad = ds.bad; }
+  }
+  __syncthreads();
+  if (s_bad) { if (tid == 0) atomicOr(flags, DFGPU_FLAG_OOB); return; }
+  uint64_t carry = 0; uint32_t consumed = 0; bool bad = false;
+  for (uint32_t row0 = 0; row0 < (uint32_t)pg.num_values; row0 += PQ_TILE) {
+    const uint32_t tl = min((uint32_t)PQ_TILE, (uint32_t)pg.num_values - row0);
+    uint32_t nn = tl;
+    if (pg.decode_levels && !pq_tile_levels(lv, rt, tl, lvals, pos16, scan_lds, nn)) { bad = true; break; }
+    if (!dbp_tile(ds, dt, consumed, nn, v64, scan64, carry)) { bad = true; break; }
+    __syncthreads();
+    for (uint32_t i = tid; i < tl; i += PQ_NT) {
+      const int64_t row = pg.row_start + row0 + i;
+      const uint32_t p16 = pg.decode_levels ? (uint32_t)pos16[i] : i; const bool valid = p16 != 0xFFFFu;
+      if (col.vbytes) col.vbytes[row] = valid;
+      store_int(col, row, valid ? v64[p16] : 0ull);
+    }
+    consumed += nn;
+    __syncthreads();
+  }
+  if (bad || lv.bad) { if (tid == 0) atomicOr(flags, DFGPU_FLAG_OOB); }
+}
+
+// DELTA_LENGTH_BYTE_ARRAY (lengths, then the bytes back to back) and DELTA_BYTE_ARRAY (prefix lengths, then a DELTA_LENGTH_BYTE_ARRAY of the suffixes):
+// one workgroup per page.  The lengths stream is decoded whole into per-value scratch (slots from pg.str_base): len[v], pos[v] = where value v's
+// (suffix) bytes start in the page, from a scan carried over the tiles.  Then the rows: (length, source) for k_pq_chars (DELTA_LENGTH), or (prefix +
+// suffix length, value index) for k_pq_dba_chars (DELTA_BYTE_ARRAY).  The prefix lengths of a DELTA_BYTE_ARRAY page go to the leaves of a min tree
+// (pre[] below, 2P slots: P = the page's value count rounded up to a power of two), which k_pq_dba_chars searches.
+struct PqDeltaStr { uint32_t* len; uint32_t* pos; uint32_t* pre; };
+__device__ inline uint32_t pq_pow2(uint32_t n) { uint32_t P = 1; while (P < n) P <<= 1; return P; }
+
+template <bool PREFIX>
+__global__ void __launch_bounds__(PQ_NT) k_pq_delta_str(const PqPage* __restrict__ pages, PqCol col, PqDeltaStr sc, uint32_t* flags) {
+  __shared__ RleState lv; __shared__ RunTable rt; __shared__ DbpState ds; __shared__ DbpTable dt;
+  __shared__ uint32_t lvals[PQ_TILE]; __shared__ uint16_t pos16[PQ_TILE]; __shared__ uint64_t v64[PQ_TILE];
+  __shared__ uint64_t scan64[4]; __shared__ uint32_t scan_lds[4]; __shared__ uint32_t s_bad, s_total; __shared__ const uint8_t* s_vptr;
+  const PqPage pg = pages[blockIdx.x]; const int tid = threadIdx.x;
+  const uint8_t* const end = pg.data + pg.size; const uint32_t base = pg.str_base, P = pq_pow2((uint32_t)max(pg.num_values, 1));
+  uint32_t* const len = sc.len + base; uint32_t* const pos = sc.pos + base; uint32_t* const tree = PREFIX ? sc.pre + base : nullptr;
+  if (tid == 0) {
+    const uint8_t* vptr; s_bad = 1;
+    if (pq_page_start(pg, lv, vptr)) { dbp_begin(ds, vptr, end, 32, (uint32_t)pg.num_values); s_bad = ds.bad; s_total = ds.total; }
+  }
+  __syncthreads();
+  bool bad = s_bad != 0; const uint32_t total = s_total;
+  uint64_t carry = 0;
+  if (PREFIX && !bad) {                                     // prefix lengths -> tree leaves
+    for (uint32_t c = 0; c < total && !bad; c += PQ_TILE) {
+      const uint32_t nn = min((uint32_t)PQ_TILE, total - c);
+      if (!dbp_tile(ds, dt, c, nn, v64, scan64, carry)) { bad = true; break; }
+      bool b2 = false;
+      for (uint32_t i = tid; i < nn; i += PQ_NT) { const uint64_t x = v64[i]; if ((uint32_t)x >= 0x80000000u) b2 = true; tree[P + c + i] = (uint32_t)x; }
+      if (__syncthreads_or(b2 ? 1 : 0)) bad = true;
+    }
+    if (tid == 0 && !bad) { dbp_begin(ds, ds.p, end, 32, (uint32_t)pg.num_values); if (!ds.bad && ds.total != total) ds.bad = 1; s_bad = ds.bad; }
+    __syncthreads();
+    if (s_bad) bad = true;
+    carry = 0;
+  }
+  // lengths -> len[], pos[] relative to the first byte after the lengths stream
+  uint64_t bytes = 0;
+  for (uint32_t c = 0; c < total && !bad; c += PQ_TILE) {
+    const uint32_t nn = min((uint32_t)PQ_TILE, total - c);
+    if (!dbp_tile(ds, dt, c, nn, v64, scan64, carry)) { bad = true; break; }
+    __syncthreads();
+    uint64_t loc[8], sum = 0; bool b2 = false;
+#pragma unroll
+    for (int j = 0; j < 8; j++) { const uint32_t idx = tid * 8 + j; uint64_t L = idx < nn ? (uint32_t)v64[idx] : 0; if (L >= 0x80000000u) b2 = true; loc[j] = L; sum += L; }
+    uint64_t tot; uint64_t run = bytes + block_exclusive_sum<uint64_t>(sum, scan64, &tot);
+#pragma unroll
+    for (int j = 0; j < 8; j++) { const uint32_t idx = tid * 8 + j; if (idx < nn) { len[c + idx] = (uint32_t)loc[j]; pos[c + idx] = (uint32_t)min(run, (uint64_t)0xFFFFFFFFu); } run += loc[j]; }
+    bytes += tot;
+    if (__syncthreads_or(b2 ? 1 : 0)) bad = true;
+  }
+  if (!bad) {
+    if (tid == 0) s_vptr = ds.p;
+    __syncthreads();
+    if (bytes > (uint64_t)(end - s_vptr)) bad = true;       // lengths that reach past the page
+  }
+  const uint32_t data0 = bad ? 0u : (uint32_t)(s_vptr - pg.data);
+  if (PREFIX && !bad) {
+    // value v is the first pre[v] bytes of value v - 1 and its suffix: pre[0] = 0, pre[v] <= pre[v - 1] + len[v - 1]
+    bool b2 = false;
+    for (uint32_t v = tid; v < total; v += PQ_NT) {
+      const uint32_t pv = tree[P + v];
+      if (v == 0 ? pv != 0 : (uint64_t)pv > (uint64_t)tree[P + v - 1] + len[v - 1]) b2 = true;
+      if ((uint64_t)pv + len[v] >= 0x80000000ull) b2 = true;
+      if (col.mode == MODE_FIXED && pv + len[v] != (uint32_t)col.wp) b2 = true;
+    }
+    for (uint32_t v = total + tid; v < P; v += PQ_NT) tree[P + v] = 0xFFFFFFFFu;
+    if (__syncthreads_or(b2 ? 1 : 0)) bad = true;
+    else for (uint32_t L = P >> 1; L >= 1; L >>= 1) {      // min tree, level by level
+      for (uint32_t n = L + tid; n < 2 * L; n += PQ_NT) tree[n] = min(tree[2 * n], tree[2 * n + 1]);
+      __syncthreads();
+    }
+  }
+  // rows
+  uint32_t consumed = 0;
+  for (uint32_t row0 = 0; row0 < (uint32_t)pg.num_values && !bad; row0 += PQ_TILE) {
+    const uint32_t tl = min((uint32_t)PQ_TILE, (uint32_t)pg.num_values - row0);
+    uint32_t nn = tl;
+    if (pg.decode_levels && !pq_tile_levels(lv, rt, tl, lvals, pos16, scan_lds, nn)) { bad = true; break; }
+    if ((uint64_t)consumed + nn > total) { bad = true; break; }
+    for (uint32_t i = tid; i < tl; i += PQ_NT) {
+      const int64_t row = pg.row_start + row0 + i;
+      const uint32_t p16 = pg.decode_levels ? (uint32_t)pos16[i] : i; const bool valid = p16 != 0xFFFFu; const uint32_t v = consumed + p16;
+      if (col.vbytes) col.vbytes[row] = valid;
+      if (PREFIX) { if (col.slen) col.slen[row] = valid ? tree[P + v] + len[v] : 0u; col.ssrc[row] = valid ? (uint64_t)v : ~0ull; }
+      else { col.slen[row] = valid ? len[v] : 0u; col.ssrc[row] = valid ? (uint64_t)(uintptr_t)(pg.data + data0 + pos[v]) : 0ull; }
+    }
+    consumed += nn;
+    __syncthreads();
+  }
+  if (PREFIX) for (uint32_t v = tid; v < total && !bad; v += PQ_NT) pos[v] += data0;       // suffix starts as page offsets, for k_pq_dba_chars
+  if (bad || lv.bad) {                                      // the byte kernels behind this one follow no row of a malformed page
+    __syncthreads();
+    for (uint32_t i = tid; i < (uint32_t)pg.num_values; i += PQ_NT) { const int64_t row = pg.row_start + i; if (col.slen) col.slen[row] = 0; col.ssrc[row] = PREFIX ? ~0ull : 0ull; }
+    if (tid == 0) atomicOr(flags, DFGPU_FLAG_OOB);
+  }
+}
+
+// DELTA_BYTE_ARRAY bytes, one workgroup per page, 8 lanes per value.  Bytes [pre[v], pre[v] + len[v]) of value v are its suffix; bytes [pre[k], t) with t
+// the lower end of what is written so far come from the suffix of k = the last value before the current one whose prefix is below t (all nearest smaller
+// values: every value between them keeps those bytes).  The chain v -> k -> ... ends at a prefix of 0 and is at most as long as the value, so every
+// value costs its length plus one tree search of depth log P per link -- strictly decreasing or increasing prefixes included.  No lane walks the page.
+// String columns write to the chars buffer at the offsets finish_strings scanned; FLBA decimals to per-value scratch, then CONV_FLBA_DEC.
+__device__ inline uint32_t pq_last_below(const uint32_t* tree, uint32_t P, uint32_t k, uint32_t t) {
+  uint32_t node = P + k;
+  while (node > 1) {
+    if ((node & 1) && tree[node - 1] < t) { node--; while (node < P) node = tree[2 * node + 1] < t ? 2 * node + 1 : 2 * node; return node - P; }
+    node >>= 1;
+  }
+  return 0xFFFFFFFFu;
+}
+__global__ void __launch_bounds__(PQ_NT) k_pq_dba_chars(const PqPage* __restrict__ pages, PqCol col, PqDeltaStr sc, const int32_t* __restrict__ offsets, uint8_t* __restrict__ out, uint8_t* scratch) {
+  const PqPage pg = pages[blockIdx.x];
+  const uint32_t base = pg.str_base, P = pq_pow2((uint32_t)max(pg.num_values, 1));
+  const uint32_t* len = sc.len + base; const uint32_t* pos = sc.pos + base; const uint32_t* tree = sc.pre + base;
+  const uint32_t sub = threadIdx.x & 7;
+  for (uint32_t i = threadIdx.x >> 3; i < (uint32_t)pg.num_values; i += PQ_NT / 8) {
+    const int64_t row = pg.row_start + i; const uint64_t vv = col.ssrc[row];
+    if (vv == ~0ull) continue;
+    const uint32_t v = (uint32_t)vv;
+    uint8_t* dst = col.mode == MODE_FIXED ? scratch + (size_t)(base + v) * col.wp : out + offsets[row];
+    uint32_t t = tree[P + v], k = v;
+    for (uint32_t b = sub; b < len[v]; b += 8) dst[t + b] = pg.data[pos[v] + b];
+    while (t > 0) {
+      const uint32_t q = pq_last_below(tree, P, k, t);
+      if (q == 0xFFFFFFFFu) break;                            // not reached: pre[0] = 0 was checked
+      const uint32_t pq0 = tree[P + q];
+      for (uint32_t b = sub; b < t - pq0; b += 8) dst[pq0 + b] = pg.data[pos[q] + b];
+      t = pq0; k = q;
+    }
+  }
+  if (col.mode != MODE_FIXED) return;
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < (uint32_t)pg.num_values; i += PQ_NT) {
+    const int64_t row = pg.row_start + i; const uint64_t vv = col.ssrc[row];
+    store_fixed(col, row, vv == ~0ull ? scratch : scratch + (size_t)(base + (uint32_t)vv) * col.wp, vv != ~0ull);
+  }
+}
+
+// BYTE_STREAM_SPLIT: byte b of non-null value i at data[b * n + i], n = the page's non-null count = its value bytes / width.  Pages without levels:
+// (page, slice) grid as k_pq_plain; a page with levels is one workgroup (its slice starts at 0xFFFFFFFF), levels decoded per tile.
+__device__ inline void bss_store(const PqCol& c, int64_t row, const uint8_t* v, uint32_t n, uint32_t i, bool valid) {
+  if (!valid) { store_int(c, row, 0); return; }
+  if (c.conv == CONV_FLBA_DEC) {                              // big-endian two's complement of wp bytes
+    const bool neg = v[i] & 0x80; uint64_t lo = neg ? ~0ull : 0ull, hi = lo;
+    for (int b = 0; b < c.wp; b++) { hi = (hi << 8) | (lo >> 56); lo = (lo << 8) | v[(size_t)b * n + i]; }
+    ((uint64_t*)c.out)[2 * row] = lo; ((uint64_t*)c.out)[2 * row + 1] = hi; return;
+  }
+  uint64_t x = 0;
+  for (int b = 0; b < c.wp; b++) x |= (uint64_t)v[(size_t)b * n + i] << (8 * b);
+  store_int(c, row, x);
+}
+__global__ void __launch_bounds__(PQ_NT) k_pq_bss(const PqPage* __restrict__ pages, const PqSlice* __restrict__ slices, PqCol col, uint32_t* flags) {
+  __shared__ RleState lv; __shared__ RunTable rt; __shared__ uint32_t lvals[PQ_TILE]; __shared__ uint16_t pos16[PQ_TILE]; __shared__ uint32_t scan_lds[4];
+  __shared__ uint32_t s_bad; __shared__ const uint8_t* s_vptr;
+  const PqSlice sl = slices[blockIdx.x]; const PqPage pg = pages[sl.page]; const int tid = threadIdx.x;
+  if (tid == 0) { const uint8_t* vptr = nullptr; s_bad = pq_page_start(pg, lv, vptr) ? 0u : 1u; s_vptr = vptr; }
+  __syncthreads();
+  if (s_bad) { if (tid == 0) atomicOr(flags, DFGPU_FLAG_OOB); return; }
+  const uint8_t* vptr = s_vptr; const uint32_t avail = pg.size - (uint32_t)(vptr - pg.data), n = avail / (uint32_t)col.wp;
+  if (avail % (uint32_t)col.wp || (!pg.decode_levels && n != (uint32_t)pg.num_values)) { if (tid == 0) atomicOr(flags, DFGPU_FLAG_OOB); return; }
+  if (!pg.decode_levels) {
+    const uint32_t last = min(sl.first + (uint32_t)PQ_SLICE, (uint32_t)pg.num_values);
+    for (uint32_t i = sl.first + tid; i < last; i += PQ_NT) {
+      const int64_t row = pg.row_start + i;
+      if (col.vbytes) col.vbytes[row] = 1;
+      bss_store(col, row, vptr, n, i, true);
+    }
+    return;
+  }
+  uint32_t consumed = 0; bool bad = false;
+  for (uint32_t row0 = 0; row0 < (uint32_t)pg.num_values; row0 += PQ_TILE) {
+    const uint32_t tl = min((uint32_t)PQ_TILE, (uint32_t)pg.num_values - row0);
+    uint32_t nn;
+    if (!pq_tile_levels(lv, rt, tl, lvals, pos16, scan_lds, nn) || (uint64_t)consumed + nn > n) { bad = true; break; }
+    for (uint32_t i = tid; i < tl; i += PQ_NT) {
+      const int64_t row = pg.row_start + row0 + i; const uint32_t p16 = pos16[i]; const bool valid = p16 != 0xFFFFu;
+      if (col.vbytes) col.vbytes[row] = valid;
+      bss_store(col, row, vptr, n, valid ? consumed + p16 : 0, valid);
+    }
+    consumed += nn;
+    __syncthreads();
+  }
+  if (bad || lv.bad || consumed != n) { if (tid == 0) atomicOr(flags, DFGPU_FLAG_OOB); }
+}
+
 // ---- Snappy (raw format): one wave per page.  The element chain is inherently serial (a tag's position follows from the tag before it, a copy may
 // read what the element before it wrote), so the loop keeps that chain short: tags are decoded on the scalar unit from an LDS window of the input, the
 // next tag's bytes are requested before the current element's bytes move, output goes to an LDS ring that holds the last 64 KB (every reference of
@@ -791,9 +1133,12 @@ template <typename T> static BufferPtr upload(dfgpu_ctx* ctx, const std::vector<
   return b;
 }
 
+// DELTA_BYTE_ARRAY pages of a string column: their bytes are written by k_pq_dba_chars once the offsets are known (finish_strings), not by k_pq_chars
+struct DbaPending { std::vector<PqPage> pages; BufferPtr dpages, len, pos, pre; PqCol col{}; };
+
 // decode PLAIN / dictionary string pages into a Utf8 array (values + int32 offsets [+ validity bytes])
 struct StrOut { BufferPtr offsets, chars; int64_t chars_bytes = 0; };
-static StrOut finish_strings(dfgpu_ctx* ctx, int64_t n, BufferPtr offsets, BufferPtr ssrc) {
+static StrOut finish_strings(dfgpu_ctx* ctx, int64_t n, BufferPtr offsets, BufferPtr ssrc, const DbaPending* dba = nullptr) {
   StrOut o; o.offsets = offsets;
   uint64_t* d_total = ctx->d_scratch64 + 40;
   exclusive_scan_u32_inplace32(ctx, (uint32_t*)offsets->ptr, n, d_total);
@@ -802,13 +1147,80 @@ static StrOut finish_strings(dfgpu_ctx* ctx, int64_t n, BufferPtr offsets, Buffe
   if (total > 0x7FFFFFFFull) fail(DFGPU_EXECUTION, "Parquet error: a Utf8 column of one read holds %llu bytes, more than int32 offsets address -- read fewer row groups per call", (unsigned long long)total);
   hipLaunchKernelGGL(k_pq_set_i32, dim3(1), dim3(1), 0, ctx->stream, (int32_t*)offsets->ptr + n, (int32_t)total);
   o.chars = alloc_buffer(ctx, std::max<size_t>((size_t)total, 16)); o.chars_bytes = (int64_t)total;
-  if (n && total) { KernelTimer kt(ctx, "pq_chars"); hipLaunchKernelGGL(k_pq_chars, dim3(grid_for(n * 8, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)ssrc->ptr, (const int32_t*)offsets->ptr, n, (uint8_t*)o.chars->ptr); }
+  if (n && total && (!dba || dba->pages.empty())) { KernelTimer kt(ctx, "pq_chars"); hipLaunchKernelGGL(k_pq_chars, dim3(grid_for(n * 8, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)ssrc->ptr, (const int32_t*)offsets->ptr, n, (uint8_t*)o.chars->ptr); }
+  else if (n && total) {
+    // k_pq_chars over the row ranges between the DELTA_BYTE_ARRAY pages, k_pq_dba_chars for those
+    std::vector<std::pair<int64_t, int64_t>> own; for (const PqPage& p : dba->pages) own.push_back({p.row_start, p.row_start + p.num_values});
+    std::sort(own.begin(), own.end());
+    int64_t at = 0;
+    auto chars = [&](int64_t r0, int64_t r1) { if (r1 <= r0) return; KernelTimer kt(ctx, "pq_chars"); hipLaunchKernelGGL(k_pq_chars, dim3(grid_for((r1 - r0) * 8, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)ssrc->ptr + r0, (const int32_t*)offsets->ptr + r0, r1 - r0, (uint8_t*)o.chars->ptr); };
+    for (auto& r : own) { chars(at, r.first); at = std::max(at, r.second); }
+    chars(at, n);
+    PqDeltaStr sc{(uint32_t*)dba->len->ptr, (uint32_t*)dba->pos->ptr, (uint32_t*)dba->pre->ptr};
+    KernelTimer kt(ctx, "pq_dba_chars");
+    hipLaunchKernelGGL(k_pq_dba_chars, dim3((unsigned)dba->pages.size()), dim3(PQ_NT), 0, ctx->stream, (const PqPage*)dba->dpages->ptr, dba->col, sc, (const int32_t*)offsets->ptr, (uint8_t*)o.chars->ptr, (uint8_t*)nullptr);
+  }
   KERNEL_CHECK();
   return o;
 }
 
-static void launch_decode(dfgpu_ctx* ctx, const std::vector<PqPage>& pages, const PqCol& col, bool wide_ok) {
+// pages of the DELTA_* / BYTE_STREAM_SPLIT encodings, each encoding to its own kernel.  DELTA_BYTE_ARRAY string pages leave their bytes to finish_strings (dba).
+static void launch_encoded(dfgpu_ctx* ctx, const std::vector<PqPage>& pages, const PqCol& col, DbaPending* dba) {
+  std::vector<PqPage> dbp, dlba, dbav, bss; int64_t rows_end = 0;
+  for (const PqPage& p : pages) { (p.enc == ENC_DELTA_BP ? dbp : p.enc == ENC_DELTA_LBA ? dlba : p.enc == ENC_DELTA_BA ? dbav : bss).push_back(p); rows_end = std::max(rows_end, p.row_start + p.num_values); }
+  if (!dbp.empty()) {
+    BufferPtr d = upload(ctx, dbp); KernelTimer kt(ctx, "pq_delta");
+    hipLaunchKernelGGL(k_pq_delta, dim3((unsigned)dbp.size()), dim3(PQ_NT), 0, ctx->stream, (const PqPage*)d->ptr, col, ctx->d_flags); KERNEL_CHECK();
+  }
+  if (!bss.empty()) {
+    std::vector<PqSlice> slices;
+    for (size_t i = 0; i < bss.size(); i++) {
+      if (bss[i].decode_levels) slices.push_back({(uint32_t)i, 0u});          // levels: the whole page in one workgroup
+      else for (uint32_t f = 0; f < (uint32_t)bss[i].num_values; f += PQ_SLICE) slices.push_back({(uint32_t)i, f});
+    }
+    if (!slices.empty()) {
+      BufferPtr d = upload(ctx, bss), ds = upload(ctx, slices); KernelTimer kt(ctx, "pq_bss");
+      hipLaunchKernelGGL(k_pq_bss, dim3((unsigned)slices.size()), dim3(PQ_NT), 0, ctx->stream, (const PqPage*)d->ptr, (const PqSlice*)ds->ptr, col, ctx->d_flags); KERNEL_CHECK();
+    }
+  }
+  auto slots = [&](std::vector<PqPage>& pg, bool tree) {          // per-value scratch: value count per page (DELTA_LENGTH), 2P (DELTA_BYTE_ARRAY: the min tree)
+    uint64_t n = 0;
+    for (auto& p : pg) { p.str_base = (uint32_t)n; uint64_t c = (uint64_t)std::max(p.num_values, 1); if (tree) { uint64_t P = 1; while (P < c) P <<= 1; c = 2 * P; } n += c; }
+    if (n > 0xFFFFFFF0ull) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: more than 2^32 DELTA byte-array values in one Parquet read");
+    return n;
+  };
+  if (!dlba.empty()) {
+    const uint64_t n = slots(dlba, false);
+    BufferPtr d = upload(ctx, dlba), len = alloc_buffer(ctx, n * 4 + 16), pos = alloc_buffer(ctx, n * 4 + 16);
+    PqDeltaStr sc{(uint32_t*)len->ptr, (uint32_t*)pos->ptr, nullptr};
+    KernelTimer kt(ctx, "pq_delta_str");
+    hipLaunchKernelGGL(k_pq_delta_str<false>, dim3((unsigned)dlba.size()), dim3(PQ_NT), 0, ctx->stream, (const PqPage*)d->ptr, col, sc, ctx->d_flags); KERNEL_CHECK();
+  }
+  if (!dbav.empty()) {
+    const uint64_t n = slots(dbav, true);
+    DbaPending own; DbaPending& q = dba && col.mode == MODE_STRING ? *dba : own;
+    q.pages = dbav; q.dpages = upload(ctx, dbav); q.len = alloc_buffer(ctx, n * 4 + 16); q.pos = alloc_buffer(ctx, n * 4 + 16); q.pre = alloc_buffer(ctx, n * 4 + 16);
+    q.col = col;
+    BufferPtr rowv, scratch;
+    if (col.mode == MODE_FIXED) { rowv = alloc_buffer(ctx, (size_t)rows_end * 8 + 16); q.col.ssrc = (uint64_t*)rowv->ptr; q.col.slen = nullptr; scratch = alloc_buffer(ctx, (size_t)n * (size_t)col.wp + 16); }
+    PqDeltaStr sc{(uint32_t*)q.len->ptr, (uint32_t*)q.pos->ptr, (uint32_t*)q.pre->ptr};
+    { KernelTimer kt(ctx, "pq_delta_str");
+      hipLaunchKernelGGL(k_pq_delta_str<true>, dim3((unsigned)dbav.size()), dim3(PQ_NT), 0, ctx->stream, (const PqPage*)q.dpages->ptr, q.col, sc, ctx->d_flags); KERNEL_CHECK(); }
+    if (col.mode == MODE_FIXED) {
+      KernelTimer kt(ctx, "pq_dba_chars");
+      hipLaunchKernelGGL(k_pq_dba_chars, dim3((unsigned)dbav.size()), dim3(PQ_NT), 0, ctx->stream, (const PqPage*)q.dpages->ptr, q.col, sc, (const int32_t*)nullptr, (uint8_t*)nullptr, (uint8_t*)scratch->ptr); KERNEL_CHECK();
+    }
+  }
+}
+
+static void launch_decode(dfgpu_ctx* ctx, const std::vector<PqPage>& pages, const PqCol& col, bool wide_ok, DbaPending* dba = nullptr) {
   if (pages.empty()) return;
+  if (std::any_of(pages.begin(), pages.end(), [](const PqPage& p) { return p.enc != 0; })) {          // one chunk may hold dictionary, PLAIN and DELTA pages
+    std::vector<PqPage> rest, enc; for (const PqPage& p : pages) (p.enc ? enc : rest).push_back(p);
+    launch_encoded(ctx, enc, col, dba);
+    launch_decode(ctx, rest, col, wide_ok);
+    return;
+  }
   if (col.mode == MODE_STRING) {                 // every page goes through k_pq_decode; the PLAIN ones get their values' positions from k_pq_str_walk first
     std::vector<PqPage> pg(pages); uint64_t slots = 0; bool any_plain = false;
     for (auto& p : pg) { p.str_base = (uint32_t)slots; if (!p.dict_enc) { slots += (uint64_t)std::max(p.num_values, 0); any_plain = true; } }
@@ -933,7 +1345,10 @@ static void plan_column(dfgpu_ctx* ctx, dfgpu_parquet* f, int leaf_idx, int rg0,
       if (h.enc == ENC_PLAIN) { d.dict_enc = 0; all_dict = false; }
       else if (h.enc == ENC_RLE && leaf.phys == PT_BOOLEAN) { d.dict_enc = 2; all_dict = false; }
       else if (h.enc == ENC_RLE_DICT || h.enc == ENC_PLAIN_DICT) { d.dict_enc = 1; if (!dict_data && h.nvals) fail(DFGPU_EXECUTION, "Parquet error: dictionary-encoded page of '%s' without a dictionary page", leaf.name.c_str()); }
-      else fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: Parquet encoding %d of column '%s' (PLAIN, RLE_DICTIONARY and RLE Booleans are decoded on the device)", h.enc, leaf.name.c_str());
+      else if ((h.enc == ENC_DELTA_BP && (leaf.phys == PT_INT32 || leaf.phys == PT_INT64)) || (h.enc == ENC_DELTA_LBA && leaf.phys == PT_BYTE_ARRAY) ||
+               (h.enc == ENC_DELTA_BA && (leaf.phys == PT_BYTE_ARRAY || leaf.phys == PT_FLBA)) ||
+               (h.enc == ENC_BSS && leaf.phys != PT_BOOLEAN && leaf.phys != PT_BYTE_ARRAY)) { d.dict_enc = 0; d.enc = h.enc; all_dict = false; }
+      else fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: Parquet encoding %d of column '%s' (PLAIN, RLE_DICTIONARY, RLE Booleans, DELTA_BINARY_PACKED, DELTA_LENGTH_BYTE_ARRAY, DELTA_BYTE_ARRAY and BYTE_STREAM_SPLIT are decoded on the device)", h.enc, leaf.name.c_str());
       if (leaf.phys == PT_BOOLEAN && d.dict_enc == 1) fail(DFGPU_EXECUTION, "Parquet error: dictionary-encoded Boolean page");
       d.dict_data = dict_data; d.dict_count = dict_count; d.dict_base = dict_base;
       if (max_def) {
@@ -990,8 +1405,9 @@ static dfgpu_array* decode_column(dfgpu_ctx* ctx, dfgpu_parquet* f, ColumnRead& 
       BufferPtr off = alloc_buffer(ctx, (size_t)(total_rows + 1) * 4 + 16), ssrc = alloc_buffer(ctx, std::max<size_t>((size_t)total_rows * 8, 16));
       col.mode = MODE_STRING; col.slen = (uint32_t*)off->ptr; col.ssrc = (uint64_t*)ssrc->ptr;
       if (dict.get()) { col.dict_offsets = (const int32_t*)dso.offsets->ptr; col.dict_chars = (const uint8_t*)dso.chars->ptr; }
-      launch_decode(ctx, pages, col, false);
-      StrOut so = finish_strings(ctx, total_rows, off, ssrc);
+      DbaPending dba;
+      launch_decode(ctx, pages, col, false, &dba);
+      StrOut so = finish_strings(ctx, total_rows, off, ssrc, &dba);
       ArrayHolder a(new_array(ctx, DFGPU_UTF8, total_rows)); a.get()->offsets = so.offsets; a.get()->values = so.chars; a.get()->values_bytes = so.chars_bytes;
       if (vbytes) { a.get()->validity = bytes_to_validity(ctx, vbytes, total_rows); a.get()->null_count = -1; } else a.get()->null_count = 0;
       if (f->utf8_dictionary) {           // schema stability: the column is Dictionary(Int32, Utf8) in every batch; a chunk that fell back to PLAIN pages gets identity keys
