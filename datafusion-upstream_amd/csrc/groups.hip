@@ -9,7 +9,6 @@
 // Ids must come out in FIRST-SEEN order (primitive.rs:137-141): every new slot keeps
 // atomicMin(first row); rows that are "first of their group" are flagged in a bitmap, compacted in
 // row order (ballot + scan), and their rank is the new id -- O(rows) streaming work, no sort.
-#include <new>
 #include "device_utils.h"
 #include <algorithm>
 
@@ -21,39 +20,48 @@ constexpr uint64_t GROUP_SEED = 0x5851f42d4c957f2dULL;
 }
 using namespace dfgpu;
 
+// The representation that numbered the last batch (groups_intern_impl tries them in this order).  NONE: no batch yet.  A masked-out
+// batch still picks one, so a representation may hold no groups.  Buffers another representation left behind are kept where noted.
+enum class GroupRep : uint8_t { NONE, RUNS, PRIMITIVE, DENSE, DIRECT_MAP, HASHED };
+
 struct dfgpu_groups {
   dfgpu_ctx* ctx = nullptr; int32_t nkeys = 0;
   int64_t n_groups = 0;
+  GroupRep rep = GroupRep::NONE;
   std::vector<dfgpu_array*> keys;     // stored key columns, one row per group (null until first batch)
-  uint64_t capacity = 0;
   int64_t size_hint = 0;               // upper bound / expectation of the number of groups when the caller knows one (0 = none)
-  BufferPtr slots, first_row;          // u64[capacity], u32[capacity]
+  // RUNS: every batch so far arrived with its keys clustered (first key column non-decreasing, the other columns constant within
+  // equal first keys), so group ids are run numbers and no hash table exists yet; ghash is filled only if a later batch breaks the order.
+  // First batch: the stored keys are take(lazy_src[c], lazy_rows) -- the batch's key columns at the first row of every run -- and are not gathered until somebody
+  // needs them here (a second batch, emit).  dfgpu_groups_emit_deferred hands (columns, rows) to a caller that gathers lazily itself: TPC-H Q18's HAVING keeps a few thousand
+  // of 150 M groups, and only their keys are ever read.
+  std::vector<dfgpu_array*> lazy_src; dfgpu_array* lazy_rows = nullptr;
+  // PRIMITIVE: the primitive-key table (≙ GroupValuesPrimitive, group_values/primitive.rs): ONE 4- or 8-byte integer key column without NULLs.  A slot is
+  // 16 bytes {key, group id, first row}: find-or-insert touches one sector per row (the general table needs the slot, its first-row
+  // word and the representative key behind a matching tag: three), and no stored-key column is consulted.  prim_banned: a key equalled
+  // the empty marker, so this column takes the general table from then on.
+  BufferPtr pslots; uint64_t pcap = 0; bool prim_banned = false;
+  // HASHED: the general table, open addressing over u64 slots (u32 first_row beside them); ghash = the hash of every stored group, so
+  // a grown table is refilled without key comparisons.  Left behind when the direct map takes over.
+  uint64_t capacity = 0; BufferPtr slots, first_row;          // u64[capacity], u32[capacity]
   BufferPtr ghash; int64_t ghash_cap = 0;   // u64 per group
-  // run mode: every batch so far arrived with its keys clustered (first key column non-decreasing, the other columns constant within
-  // equal first keys), so group ids are run numbers and no hash table exists yet; ghash is filled only if a later batch breaks the order
-  bool run_mode = false;
-  // canon mode: dictionary key columns are interned through a de-duplicated dictionary -- canon[code] = id of the distinct dictionary
-  // VALUE (so codes with equal values stay one group) -- and rows are hashed / compared as u32 tuples instead of strings.  Valid while
-  // every batch brings the same dictionary arrays; another dictionary drops back to value keys (stored groups are re-hashed).
+  // canon mode (a key encoding, not a representation: DENSE, DIRECT_MAP and HASHED use it): dictionary key columns are interned through
+  // a de-duplicated dictionary -- canon[code] = id of the distinct dictionary VALUE (so codes with equal values stay one group) -- and
+  // rows are hashed / compared as u32 tuples instead of strings.  Valid while every batch brings the same dictionary arrays; another
+  // dictionary drops back to value keys (stored groups are re-hashed).
   bool canon_mode = false;
   struct Canon { dfgpu_array* dict = nullptr; BufferPtr ids; int64_t n_ids = 0; };
   std::vector<Canon> canon;               // per key column (dict == null: not a dictionary column)
   std::vector<dfgpu_array*> canon_keys;   // per key column: u32 canon id per group (dictionary columns) or null (use keys[c])
-  // dense canon mode: every key column is a dictionary column and the product of the canonical domains is <= 4096 (TPC-H Q1: 4 x 3):
+  // DENSE: every key column is a dictionary column and the product of the canonical domains is <= 4096 (TPC-H Q1: 4 x 3):
   // the composite canonical id indexes dense_map (-> group id or none) directly -- no hashing, no table, two streaming passes
   BufferPtr dense_map; int64_t dense_size = 0; std::vector<uint32_t> dense_host;
-  // direct map: ONE dictionary key column with a larger canonical domain: dmap[canonical id] = group id (or none) replaces the hash table
+  // DIRECT_MAP: ONE dictionary key column with a larger canonical domain: dmap[canonical id] = group id (or none) replaces the hash table
   // altogether -- the ids are dense in [0, n_ids], so "find or insert" is an array access
   BufferPtr dmap; int64_t dmap_size = 0;
-  // primitive-key table (≙ GroupValuesPrimitive, group_values/primitive.rs): ONE 8-byte integer key column without NULLs.  A slot is
-  // 16 bytes {key, group id, first row}: find-or-insert touches one sector per row (the general table needs the slot, its first-row
-  // word and the representative key behind a matching tag: three), and no stored-key column is consulted.
-  BufferPtr pslots; uint64_t pcap = 0; bool prim_mode = false, prim_banned = false;
-  // run mode, first batch: the stored keys are take(lazy_src[c], lazy_rows) -- the batch's key columns at the first row of every run -- and are not gathered until somebody
-  // needs them here (a second batch, emit).  dfgpu_groups_emit_deferred hands (columns, rows) to a caller that gathers lazily itself: TPC-H Q18's HAVING keeps a few thousand
-  // of 150 M groups, and only their keys are ever read.
-  std::vector<dfgpu_array*> lazy_src; dfgpu_array* lazy_rows = nullptr;
-  ~dfgpu_groups() { for (auto* a : lazy_src) if (a) dfgpu_array_release(a); if (lazy_rows) dfgpu_array_release(lazy_rows); for (auto* a : keys) if (a) dfgpu_array_release(a); for (auto* a : canon_keys) if (a) dfgpu_array_release(a); for (auto& c : canon) if (c.dict) dfgpu_array_release(c.dict); }
+  void release_arrays() { for (auto* a : lazy_src) if (a) dfgpu_array_release(a); if (lazy_rows) dfgpu_array_release(lazy_rows); for (auto* a : keys) if (a) dfgpu_array_release(a); for (auto* a : canon_keys) if (a) dfgpu_array_release(a); for (auto& c : canon) if (c.dict) dfgpu_array_release(c.dict); }
+  ~dfgpu_groups() { release_arrays(); }
+  void reset() { release_arrays(); dfgpu_ctx* c = ctx; const int32_t nk = nkeys; *this = dfgpu_groups(); ctx = c; nkeys = nk; keys.assign((size_t)nk, nullptr); }      // as dfgpu_groups_new left it
 };
 
 namespace dfgpu {
@@ -442,6 +450,14 @@ __global__ void __launch_bounds__(BLOCK) k_dm_seed(const uint32_t* group_cid, in
   int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x; if (g < n_groups) dmap[group_cid[g]] = (uint32_t)g;
 }
 
+// f(DenseShape<K, NC, MASK>{}) for the shape of the k_dense_*_fast kernels: code type K (Int8, Int16, else Int32), NC = 1 or 2 key columns, a mask or none
+template <typename K, int NC, bool MASK> struct DenseShape { using Key = K; static constexpr int nc = NC; static constexpr bool mask = MASK; };
+template <typename F> static void dense_fast_dispatch(int32_t key_type, int32_t nc, bool masked, F&& f) {
+  auto by_count = [&](auto k) { using K = decltype(k); if (nc == 1) { if (masked) f(DenseShape<K, 1, true>{}); else f(DenseShape<K, 1, false>{}); }
+                                                       else if (masked) f(DenseShape<K, 2, true>{}); else f(DenseShape<K, 2, false>{}); };
+  if (key_type == DFGPU_INT8) by_count(int8_t{}); else if (key_type == DFGPU_INT16) by_count(int16_t{}); else by_count(int32_t{});
+}
+
 void materialize_ids(dfgpu_ctx* ctx, const dfgpu_array* ids_c) {
   if (!ids_c || !ids_c->deferred_ids) return;
   dfgpu_array* ids = const_cast<dfgpu_array*>(ids_c); std::shared_ptr<DeferredIds> d = ids->deferred_ids;
@@ -451,16 +467,10 @@ void materialize_ids(dfgpu_ctx* ctx, const dfgpu_array* ids_c) {
     hipLaunchKernelGGL(k_run_ids, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)d->heads->ptr, (const uint32_t*)d->prefix->ptr, n, d->base, (uint32_t*)ids->values->ptr);
     KERNEL_CHECK(); ids->deferred_ids.reset(); return;
   }
-  dim3 grid(grid_for(n, BLOCK * DENSE_ROWS)), block(BLOCK);
   KernelTimer kt_(ctx, "k_groups_dense");
-#define IDS(K, NC) do { if (mk) hipLaunchKernelGGL((k_dense_ids_fast<K, NC, true>), grid, block, 0, ctx->stream, d->dc, n, mk, (const uint32_t*)d->dense_map->ptr, (uint32_t*)ids->values->ptr); \
-                        else hipLaunchKernelGGL((k_dense_ids_fast<K, NC, false>), grid, block, 0, ctx->stream, d->dc, n, mk, (const uint32_t*)d->dense_map->ptr, (uint32_t*)ids->values->ptr); } while (0)
-  if (d->key_type == DFGPU_INT8) { if (d->dc.n == 1) IDS(int8_t, 1); else IDS(int8_t, 2); }
-  else if (d->key_type == DFGPU_INT16) { if (d->dc.n == 1) IDS(int16_t, 1); else IDS(int16_t, 2); }
-  else { if (d->dc.n == 1) IDS(int32_t, 1); else IDS(int32_t, 2); }
-#undef IDS
-  KERNEL_CHECK();
-  ids->deferred_ids.reset();
+  dense_fast_dispatch(d->key_type, d->dc.n, mk != nullptr, [&](auto s) { using S = decltype(s);
+    hipLaunchKernelGGL((k_dense_ids_fast<typename S::Key, S::nc, S::mask>), dim3(grid_for(n, BLOCK * DENSE_ROWS)), dim3(BLOCK), 0, ctx->stream, d->dc, n, mk, (const uint32_t*)d->dense_map->ptr, (uint32_t*)ids->values->ptr); });
+  KERNEL_CHECK(); ids->deferred_ids.reset();
 }
 
 static void groups_alloc_table(dfgpu_groups* g, uint64_t cap) {
@@ -492,6 +502,13 @@ int64_t dfgpu_groups_size(const dfgpu_groups* g) {
   return b;
 }
 
+// dst = dst ++ part (part is consumed; a null dst takes part as it is)
+static void append_column(dfgpu_ctx* ctx, dfgpu_array*& dst, ArrayHolder& part) {
+  if (!dst) { dst = part.release(); return; }
+  const dfgpu_array* parts[2] = { dst, part.get() }; dfgpu_array* cat = nullptr;
+  dfgpu_status st = dfgpu_concat(ctx, parts, 2, &cat); if (st != DFGPU_OK) fail(st, "%s", ctx->err.c_str());
+  dfgpu_array_release(dst); dst = cat;
+}
 // append the key values of the new groups (first-seen rows, in id order) to the stored key columns
 static void groups_append_keys(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_array* const* cols, int32_t nkeys, const dfgpu_array* firsts, int64_t n_new) {
   for (int c = 0; c < nkeys; c++) {
@@ -503,9 +520,7 @@ static void groups_append_keys(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_arra
         ArrayHolder w(wide); ArrayHolder dec(take_impl(ctx, k->dictionary, w.get()->values->ptr, 8, w.get()->validity ? (const uint64_t*)w.get()->validity->ptr : nullptr, k->length)); dfgpu_array_release(nk.release()); nk.a = dec.release(); }
       else { ArrayHolder dec(take_impl(ctx, k->dictionary, k->values->ptr, kw, k->validity ? (const uint64_t*)k->validity->ptr : nullptr, k->length)); dfgpu_array_release(nk.release()); nk.a = dec.release(); }
     }
-    if (!g->keys[c]) g->keys[c] = nk.release();
-    else { const dfgpu_array* parts[2] = { g->keys[c], nk.get() }; dfgpu_array* cat = nullptr; dfgpu_status st = dfgpu_concat(ctx, parts, 2, &cat); if (st != DFGPU_OK) fail(st, "%s", ctx->err.c_str());
-           dfgpu_array_release(g->keys[c]); g->keys[c] = cat; }
+    append_column(ctx, g->keys[c], nk);
   }
 }
 static void groups_resolve_keys(dfgpu_ctx* ctx, dfgpu_groups* g) {        // the pending gather of a first run-mode batch's keys, now
@@ -522,14 +537,44 @@ static void groups_reserve_ghash(dfgpu_ctx* ctx, dfgpu_groups* g, int64_t need, 
   if (keep && g->ghash) HIP_CHECK(hipMemcpyAsync(nh->ptr, g->ghash->ptr, (size_t)keep * 8, hipMemcpyDeviceToDevice, ctx->stream));
   g->ghash = nh; g->ghash_cap = nc;
 }
+// the stored groups as the general table compares them: canonical ids for the dictionary columns in canon mode, values otherwise
+static KeySet stored_keyset(const dfgpu_groups* g) {
+  std::vector<const dfgpu_array*> sk(g->keys.begin(), g->keys.end());
+  if (g->canon_mode) for (int c = 0; c < g->nkeys; c++) if (g->canon_keys[(size_t)c]) sk[(size_t)c] = g->canon_keys[(size_t)c];
+  return make_keyset(sk.data(), g->nkeys);
+}
+// first size of a table (general or primitive): room for the stored groups and twice the new ones this batch may bring (<= 2^22 unless size_hint says more)
+static uint64_t groups_first_capacity(const dfgpu_groups* g, int64_t n) {
+  uint64_t expect = (uint64_t)(n < (1 << 22) ? n : (1 << 22));
+  if (g->size_hint > 0) { uint64_t h = std::min((uint64_t)g->size_hint, (uint64_t)n); if (h > expect) expect = h; }
+  uint64_t want = 1ull << 16; while (want < (uint64_t)g->n_groups * 4 + 2 * expect) want <<= 1;
+  return want;
+}
+// capacity_for: cap doubled until the groups fill at most a quarter of it (at most 2^31 slots).  regrow: keeps the load factor <= 1/2 for
+// the next batch -- the grown capacity, or 0 if the table is fine as it is.  overflow: a batch overfilled the table, it is redone on one 8x larger.
+static uint64_t groups_capacity_for(uint64_t cap, int64_t n_groups) { while (cap < (uint64_t)n_groups * 4) cap <<= 1; return std::min<uint64_t>(cap, 1ull << 31); }
+static uint64_t groups_regrow(uint64_t cap, int64_t n_groups) { return (uint64_t)n_groups * 2 > cap ? groups_capacity_for(cap, n_groups) : 0; }
+static uint64_t groups_overflow_capacity(uint64_t cap) { if (cap >= (1ull << 31)) fail(DFGPU_RESOURCES_EXHAUSTED, "group table would exceed 2^31 slots"); return std::min<uint64_t>(cap << 3, 1ull << 31); }
+// The general table takes the stored groups over from another representation: the primitive table goes, ghash gets every stored group's
+// hash (stored_keyset), and an existing table is rebuilt with room for all of them (groups numbered by the direct map never entered it).
+static void groups_hash_stored(dfgpu_ctx* ctx, dfgpu_groups* g) {
+  g->pslots.reset(); g->pcap = 0; g->rep = GroupRep::HASHED;
+  if (!g->n_groups) return;
+  const KeySet stored = stored_keyset(g); groups_reserve_ghash(ctx, g, g->n_groups, 0);
+  hipLaunchKernelGGL(k_groups_hash_stored, dim3(grid_for(g->n_groups, BLOCK)), dim3(BLOCK), 0, ctx->stream, stored, g->n_groups, ctx->force_hash_collisions ? 1 : 0, (uint64_t*)g->ghash->ptr);
+  KERNEL_CHECK();
+  if (g->capacity) groups_alloc_table(g, groups_capacity_for(g->capacity, g->n_groups));
+}
 static bool run_key_type(const dfgpu_array* a) {
   if (a->type == DFGPU_DICTIONARY || a->validity) return false;
   switch (a->type) { case DFGPU_INT8: case DFGPU_INT16: case DFGPU_INT32: case DFGPU_INT64: case DFGPU_DATE32: case DFGPU_UINT8: case DFGPU_UINT16: case DFGPU_UINT32: case DFGPU_UINT64: return true; default: return false; }
 }
-// Clustered batch -> ids by run number.  Returns false (nothing changed) when the batch is not clustered.
-static bool groups_intern_runs(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_array* const* cols, int32_t nkeys, const KeySet& bk, int64_t n, dfgpu_array* ids, bool allow_deferred) {
+// RUNS: clustered keys (the shape of GROUP BY over a fact table stored in key order) -> ids by run number, no hash table.  Declines
+// (nothing changed) when the batch does not qualify or is not clustered.
+static bool groups_intern_runs(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_array* const* cols, int32_t nkeys, const KeySet& bk, int64_t n, const uint64_t* mk, dfgpu_array* ids, bool allow_deferred) {
   const dfgpu_array* k0 = cols[0];
-  if (g->n_groups && logical_type(k0) != g->keys[0]->type) return false;
+  if (!ctx->group_run_detection || ctx->force_hash_collisions || mk || g->capacity != 0 || !(g->n_groups == 0 || g->rep == GroupRep::RUNS) || !run_key_type(k0) ||
+      (g->n_groups && logical_type(k0) != g->keys[0]->type)) return false;
   KernelTimer kt_(ctx, "k_groups_runs");
   BufferPtr heads = alloc_buffer(ctx, bitmap_bytes(n));
   zero_scratch(ctx);
@@ -560,17 +605,247 @@ static bool groups_intern_runs(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_arra
     for (int c = 0; c < nkeys; c++) { g->lazy_src.push_back(const_cast<dfgpu_array*>(cols[c])); dfgpu_array_retain(g->lazy_src.back()); }
     g->lazy_rows = firsts.release();
   } else if (n_new) groups_append_keys(ctx, g, cols, nkeys, firsts.get(), n_new);
-  g->n_groups += n_new; g->run_mode = true;
+  g->n_groups += n_new; g->rep = GroupRep::RUNS;
   return true;
 }
+static bool prim_key_type(const dfgpu_array* a) { return a && (a->type == DFGPU_INT64 || a->type == DFGPU_UINT64 || a->type == DFGPU_INT32 || a->type == DFGPU_UINT32 || a->type == DFGPU_DATE32) && !a->validity; }
+// a primitive table of cap slots holding the numbered groups
+static void prim_rebuild(dfgpu_ctx* ctx, dfgpu_groups* g, uint64_t cap, bool key4) {
+  g->pslots = alloc_buffer(ctx, (size_t)cap * sizeof(PSlot)); g->pcap = cap; HIP_CHECK(hipMemsetAsync(g->pslots->ptr, 0xFF, (size_t)cap * sizeof(PSlot), ctx->stream));
+  if (!g->n_groups) return;
+  if (key4) hipLaunchKernelGGL((k_prim_insert<uint32_t>), dim3(grid_for(g->n_groups, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)g->keys[0]->values->ptr, g->n_groups, (PSlot*)g->pslots->ptr, cap - 1);
+  else hipLaunchKernelGGL((k_prim_insert<unsigned long long>), dim3(grid_for(g->n_groups, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const unsigned long long*)g->keys[0]->values->ptr, g->n_groups, (PSlot*)g->pslots->ptr, cap - 1);
+  KERNEL_CHECK();
+}
+// PRIMITIVE: one 8- or 4-byte integer key column without NULLs.  Declines when the batch does not qualify, and when a key equals the
+// empty marker: the column is then banned from this table, and the caller moves the stored groups to the general table.
+static bool groups_intern_primitive(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_array* const* cols, int32_t nkeys, int64_t n, const uint64_t* mk, dfgpu_array* ids) {
+  if (nkeys != 1 || ctx->force_hash_collisions || g->prim_banned || g->canon_mode || g->capacity != 0 || !prim_key_type(cols[0]) ||
+      !(g->n_groups == 0 || (prim_key_type(g->keys[0]) && g->keys[0]->type == cols[0]->type))) return false;
+  const bool key4 = type_width(cols[0]->type) == 4; const void* kp = cols[0]->values->ptr;
+  const uint64_t want = groups_first_capacity(g, n);
+  if (g->pcap < want || g->rep != GroupRep::PRIMITIVE) prim_rebuild(ctx, g, std::max(g->pcap, want), key4);     // a table left behind lacks the groups numbered since
+  g->rep = GroupRep::PRIMITIVE;
+  BufferPtr tmp = alloc_buffer(ctx, (size_t)n * 4);
+  for (;;) {
+    zero_scratch(ctx);
+    { KernelTimer kt_(ctx, "k_groups_find");
+      dim3 fg(grid_for(n, BLOCK * PF_ROWS));
+#define PFIND(KT, HM) hipLaunchKernelGGL((k_prim_find<KT, HM>), fg, dim3(BLOCK), 0, ctx->stream, (const KT*)kp, n, mk, (PSlot*)g->pslots->ptr, g->pcap - 1, (uint32_t*)tmp->ptr, (unsigned long long*)ctx->d_scratch64, (uint64_t)256)
+      if (key4) { if (mk) PFIND(uint32_t, true); else PFIND(uint32_t, false); } else { if (mk) PFIND(unsigned long long, true); else PFIND(unsigned long long, false); }
+#undef PFIND
+    }
+    KERNEL_CHECK();
+    ctx->count_sync("sync:group_table"); fetch_to_pinned(ctx, 0, ctx->d_scratch64, 32);
+    if (ctx->h_pinned[3]) { g->prim_banned = true; return false; }
+    if (ctx->h_pinned[1] == 0) break;
+    prim_rebuild(ctx, g, groups_overflow_capacity(g->pcap), key4);       // the claims of the overfull pass go with the old table
+  }
+  BufferPtr bits = alloc_buffer(ctx, bitmap_bytes((int64_t)g->pcap));
+  hipLaunchKernelGGL(k_prim_new_bits, dim3(grid_for((int64_t)g->pcap, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const PSlot*)g->pslots->ptr, (int64_t)g->pcap, (uint64_t*)bits->ptr);
+  KERNEL_CHECK();
+  ArrayHolder new_slots(mask_to_indices_impl(ctx, (const uint64_t*)bits->ptr, (int64_t)g->pcap));
+  int64_t n_new = new_slots.get()->length;
+  if (g->n_groups + n_new >= (int64_t)G_NEW) fail(DFGPU_RESOURCES_EXHAUSTED, "more than 2^31 groups");
+  if (n_new) {
+    ArrayHolder firsts(new_fixed(ctx, DFGPU_UINT32, n_new));
+    hipLaunchKernelGGL(k_prim_first_of, dim3(grid_for(n_new, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)new_slots.get()->values->ptr, n_new, (const PSlot*)g->pslots->ptr, (uint32_t*)firsts.get()->values->ptr);
+    KERNEL_CHECK();
+    int bitsn = 1; while ((1ll << bitsn) < n) bitsn++;
+    radix_sort_pairs_u32(ctx, (uint32_t*)firsts.get()->values->ptr, (uint32_t*)new_slots.get()->values->ptr, n_new, bitsn);      // first-seen order
+    hipLaunchKernelGGL(k_prim_assign, dim3(grid_for(n_new, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)new_slots.get()->values->ptr, n_new, (uint32_t)g->n_groups, (PSlot*)g->pslots->ptr);
+    KERNEL_CHECK();
+    groups_append_keys(ctx, g, cols, nkeys, firsts.get(), n_new);
+    check_flags(ctx, "groups_intern");
+  }
+  hipLaunchKernelGGL(k_prim_ids, dim3(grid_for(n, BLOCK * PF_ROWS)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)tmp->ptr, n, (const PSlot*)g->pslots->ptr, (uint32_t*)ids->values->ptr);
+  KERNEL_CHECK();
+  g->n_groups += n_new;
+  if (uint64_t ncap = groups_regrow(g->pcap, g->n_groups)) prim_rebuild(ctx, g, ncap, key4);
+  return true;
+}
+// Canon mode on or off for this batch: entered by a first batch with dictionary key columns, kept while batches bring the same
+// dictionaries, left on any other batch (the stored groups go to the general table by value).  Returns canon_mode.
+static bool groups_canon_setup(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_array* const* cols, int32_t nkeys) {
+  bool any_dict = false; for (int c = 0; c < nkeys; c++) any_dict |= cols[c]->type == DFGPU_DICTIONARY && cols[c]->dictionary != nullptr;
+  bool want_canon = ctx->group_dictionary_canon && !ctx->force_hash_collisions && any_dict && (g->n_groups == 0 || g->canon_mode);
+  if (want_canon && g->canon_mode)
+    for (int c = 0; c < nkeys; c++) { const dfgpu_array* d = cols[c]->type == DFGPU_DICTIONARY ? cols[c]->dictionary : nullptr; if (d != g->canon[(size_t)c].dict) want_canon = false; }
+  if (g->canon_mode && !want_canon) {
+    for (auto*& a : g->canon_keys) { if (a) dfgpu_array_release(a); a = nullptr; }
+    for (auto& cc : g->canon) { if (cc.dict) dfgpu_array_release(cc.dict); cc = dfgpu_groups::Canon{}; }
+    g->canon_mode = false; g->dense_size = 0; g->dense_map.reset(); g->dense_host.clear(); g->dmap.reset(); g->dmap_size = 0;
+    groups_hash_stored(ctx, g);
+  }
+  if (want_canon && !g->canon_mode) {
+    g->canon.assign((size_t)nkeys, dfgpu_groups::Canon{}); g->canon_keys.assign((size_t)nkeys, nullptr);
+    for (int c = 0; c < nkeys; c++) {
+      if (cols[c]->type != DFGPU_DICTIONARY) continue;
+      const dfgpu_array* dict = cols[c]->dictionary;
+      dfgpu_groups tmp; tmp.ctx = ctx; tmp.nkeys = 1; tmp.keys.assign(1, nullptr); tmp.size_hint = dict->length;
+      dfgpu_array* dids = nullptr; dfgpu_status st = dfgpu_groups_intern(ctx, &tmp, &dict, 1, nullptr, &dids);
+      if (st != DFGPU_OK) fail(st, "%s", ctx->err.c_str());
+      ArrayHolder hold(dids);
+      auto& cc = g->canon[(size_t)c]; cc.dict = const_cast<dfgpu_array*>(dict); dfgpu_array_retain(cc.dict); cc.ids = dids->values; cc.n_ids = tmp.n_groups;
+    }
+    g->canon_mode = true;
+  }
+  return want_canon;
+}
+// DENSE (canon mode): every key column a dictionary column and a composite domain of at most DENSE_MAX: a small map is indexed directly
+static bool groups_intern_dense(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_array* const* cols, int32_t nkeys, int64_t n, const BufferPtr& mask, dfgpu_array* ids, bool allow_deferred) {
+  bool all_dict = true; int64_t dsize = 1;
+  for (int c = 0; c < nkeys; c++) { if (!g->canon[(size_t)c].dict) { all_dict = false; break; } dsize *= g->canon[(size_t)c].n_ids + 1; if (dsize > DENSE_MAX) break; }
+  if (!all_dict || dsize > DENSE_MAX || !(g->rep == GroupRep::DENSE || g->n_groups == 0)) {        // a dense map keeps fitting while the dictionaries stay
+    if (g->rep == GroupRep::DENSE) fail(DFGPU_INTERNAL, "dense dictionary group map changed size"); return false; }
+  KernelTimer kt_(ctx, "k_groups_dense");
+  if (g->dense_size != dsize) { g->dense_size = dsize; g->dense_host.assign((size_t)dsize, G_NONE); g->dense_map = alloc_buffer(ctx, (size_t)dsize * 4); HIP_CHECK(hipMemsetAsync(g->dense_map->ptr, 0xFF, (size_t)dsize * 4, ctx->stream)); }
+  DenseCols dc{}; dc.n = nkeys; uint32_t stride = 1;
+  for (int c = nkeys - 1; c >= 0; c--) {
+    auto& cc = g->canon[(size_t)c]; DenseCol& d = dc.c[c];
+    d.keys = cols[c]->values->ptr; d.key_valid = cols[c]->validity ? (const uint64_t*)cols[c]->validity->ptr : nullptr; d.key_type = cols[c]->key_type;
+    d.canon = (const uint32_t*)cc.ids->ptr; d.dict_valid = cc.dict->validity ? (const uint64_t*)cc.dict->validity->ptr : nullptr; d.dict_len = cc.dict->length;
+    d.n_ids = (uint32_t)cc.n_ids; d.stride = stride; stride *= (uint32_t)cc.n_ids + 1;
+  }
+  BufferPtr first = alloc_buffer(ctx, (size_t)dsize * 4); HIP_CHECK(hipMemsetAsync(first->ptr, 0xFF, (size_t)dsize * 4, ctx->stream));
+  const uint64_t* mk = mask ? (const uint64_t*)mask->ptr : nullptr; const uint32_t* dmp = (const uint32_t*)g->dense_map->ptr; dim3 block(BLOCK);
+  // straight-line kernels when every code column has the same integer type and nothing is nullable (codes must then be in range:
+  // Arrow requires valid dictionary codes; the generic kernels also tolerate out-of-range codes as NULL)
+  bool fast = nkeys <= 2; int kt0 = cols[0]->key_type;
+  for (int c = 0; c < nkeys; c++) fast = fast && cols[c]->key_type == kt0 && !dc.c[c].key_valid && !dc.c[c].dict_valid;
+  fast = fast && (kt0 == DFGPU_INT8 || kt0 == DFGPU_INT16 || kt0 == DFGPU_INT32);
+  const int fgrid = grid_for(n, BLOCK * DENSE_ROWS, ctx->num_cus * 8); const int64_t len1 = nkeys == 2 ? dc.c[1].dict_len : 1;
+  bool tab = fast && dc.c[0].dict_len * len1 <= DENSE_MAX && dsize <= 65535;
+  for (int c = 0; c < nkeys && tab; c++) tab = (((uintptr_t)dc.c[c].keys) & 15) == 0;
+  if (fast) dense_fast_dispatch(kt0, nkeys, mk != nullptr, [&](auto s) { using S = decltype(s);
+    if (tab) hipLaunchKernelGGL((k_dense_first_tab<typename S::Key, S::nc, S::mask>), dim3(grid_for(n, BLOCK * 4, ctx->num_cus * 8)), block, 0, ctx->stream, dc, n, mk, dmp, (uint32_t*)first->ptr, (int)dsize, (int)len1);
+    else hipLaunchKernelGGL((k_dense_first_fast<typename S::Key, S::nc, S::mask>), dim3(fgrid), block, 0, ctx->stream, dc, n, mk, dmp, (uint32_t*)first->ptr, (int)dsize); });
+  else hipLaunchKernelGGL(k_dense_first, dim3(fgrid), block, 0, ctx->stream, dc, n, mk, dmp, (uint32_t*)first->ptr, (int)dsize);
+  KERNEL_CHECK();
+  std::vector<uint32_t> fh((size_t)dsize);
+  ctx->count_sync("sync:dense_groups"); fetch_to_host(ctx, fh.data(), first->ptr, (size_t)dsize * 4);
+  std::vector<std::pair<uint32_t, uint32_t>> fresh;             // (first row, composite) of the composites met for the first time
+  for (int64_t comp = 0; comp < dsize; comp++) if (fh[(size_t)comp] != G_NONE) fresh.emplace_back(fh[(size_t)comp], (uint32_t)comp);
+  std::sort(fresh.begin(), fresh.end());                        // first-seen order
+  int64_t n_new = (int64_t)fresh.size();
+  if (n_new) {
+    std::vector<uint32_t> rows((size_t)n_new);
+    for (int64_t k2 = 0; k2 < n_new; k2++) { g->dense_host[fresh[(size_t)k2].second] = (uint32_t)(g->n_groups + k2); rows[(size_t)k2] = fresh[(size_t)k2].first; }
+    HIP_CHECK(hipMemcpyAsync(g->dense_map->ptr, g->dense_host.data(), (size_t)dsize * 4, hipMemcpyHostToDevice, ctx->stream));
+    ArrayHolder firsts(new_fixed(ctx, DFGPU_UINT32, n_new));
+    HIP_CHECK(hipMemcpyAsync(firsts.get()->values->ptr, rows.data(), (size_t)n_new * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));               // rows / dense_host are host vectors
+    groups_append_keys(ctx, g, cols, nkeys, firsts.get(), n_new);
+  }
+  if (fast && allow_deferred) {       // the ids are a pure function of the code columns and the map: the consumer computes them in its own pass
+    auto d = std::make_shared<DeferredIds>(); d->dc = dc; d->key_type = kt0; d->mask = mask; d->dense_map = g->dense_map;
+    for (int c = 0; c < nkeys; c++) { d->keep.push_back(cols[c]->values); d->keep.push_back(g->canon[(size_t)c].ids); }
+    ids->deferred_ids = d;
+  }
+  else if (fast) dense_fast_dispatch(kt0, nkeys, mk != nullptr, [&](auto s) { using S = decltype(s);
+    hipLaunchKernelGGL((k_dense_ids_fast<typename S::Key, S::nc, S::mask>), dim3(grid_for(n, BLOCK * DENSE_ROWS)), block, 0, ctx->stream, dc, n, mk, dmp, (uint32_t*)ids->values->ptr); });
+  else hipLaunchKernelGGL(k_dense_ids, dim3(grid_for(n, BLOCK * DENSE_ROWS)), block, 0, ctx->stream, dc, n, mk, dmp, (uint32_t*)ids->values->ptr);
+  KERNEL_CHECK();
+  g->n_groups += n_new; g->rep = GroupRep::DENSE;
+  return true;
+}
+// canon mode: sub[c] = the canonical id of every row of dictionary key column c (other columns: null)
+static void groups_canon_lookup(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_array* const* cols, int32_t nkeys, int64_t n, std::vector<ArrayHolder>& sub) {
+  for (int c = 0; c < nkeys; c++) {
+    if (cols[c]->type != DFGPU_DICTIONARY) continue;
+    auto& cc = g->canon[(size_t)c];
+    sub[(size_t)c].a = new_fixed(ctx, DFGPU_UINT32, n);
+    KernelTimer kt_(ctx, "k_canon_lookup");
+    hipLaunchKernelGGL(k_canon_lookup, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, cols[c]->values->ptr, cols[c]->key_type, cols[c]->validity ? (const uint64_t*)cols[c]->validity->ptr : nullptr, n,
+                       (const uint32_t*)cc.ids->ptr, cc.dict->validity ? (const uint64_t*)cc.dict->validity->ptr : nullptr, cc.dict->length, (uint32_t)cc.n_ids, (uint32_t*)sub[(size_t)c].get()->values->ptr);
+    KERNEL_CHECK();
+  }
+}
+// DIRECT_MAP (canon mode, one dictionary key column, cids = its rows' canonical ids): the ids are dense, so a direct map replaces the hash
+// table (find, first-row marking, numbering).  Taken from 2^16 rows on; a small first batch goes to the general table and seeds the map.
+static bool groups_intern_direct(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_array* const* cols, int32_t nkeys, int64_t n, const uint64_t* mk, const dfgpu_array* cids, dfgpu_array* ids) {
+  if (!g->canon_mode || nkeys != 1 || !cids || !(g->rep == GroupRep::DIRECT_MAP || n >= (1 << 16)) || g->canon[0].n_ids + 1 > (1ll << 28)) return false;
+  KernelTimer kt_(ctx, "k_groups_dmap");
+  const int64_t dom = g->canon[0].n_ids + 1; const uint32_t* cid = (const uint32_t*)cids->values->ptr;
+  if (!g->dmap) {
+    g->dmap = alloc_buffer(ctx, (size_t)dom * 4); g->dmap_size = dom;
+    HIP_CHECK(hipMemsetAsync(g->dmap->ptr, 0xFF, (size_t)dom * 4, ctx->stream));
+    if (g->n_groups) { hipLaunchKernelGGL(k_dm_seed, dim3(grid_for(g->n_groups, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)g->canon_keys[0]->values->ptr, g->n_groups, (uint32_t*)g->dmap->ptr); KERNEL_CHECK(); }
+  }
+  if (g->dmap_size != dom) fail(DFGPU_INTERNAL, "dictionary group map changed size");
+  BufferPtr first = alloc_buffer(ctx, (size_t)dom * 4), heads = alloc_buffer(ctx, bitmap_bytes(n));
+  HIP_CHECK(hipMemsetAsync(first->ptr, 0xFF, (size_t)dom * 4, ctx->stream));
+  dim3 rgrid(grid_for(n, BLOCK * DM_ROWS)), block(BLOCK);
+  hipLaunchKernelGGL(k_dm_first, rgrid, block, 0, ctx->stream, cid, n, mk, (const uint32_t*)g->dmap->ptr, (uint32_t*)first->ptr);
+  hipLaunchKernelGGL(k_dm_heads, rgrid, block, 0, ctx->stream, cid, n, mk, (const uint32_t*)g->dmap->ptr, (const uint32_t*)first->ptr, (uint64_t*)heads->ptr);
+  KERNEL_CHECK();
+  ArrayHolder firsts(mask_to_indices_impl(ctx, (const uint64_t*)heads->ptr, n));
+  int64_t n_new = firsts.get()->length;
+  if (g->n_groups + n_new >= (int64_t)G_NEW) fail(DFGPU_RESOURCES_EXHAUSTED, "more than 2^31 groups");
+  if (n_new) {
+    ArrayHolder nc(new_fixed(ctx, DFGPU_UINT32, n_new));
+    hipLaunchKernelGGL(k_dm_assign, dim3(grid_for(n_new, BLOCK)), block, 0, ctx->stream, (const uint32_t*)firsts.get()->values->ptr, n_new, cid, (uint32_t)g->n_groups, (uint32_t*)g->dmap->ptr, (uint32_t*)nc.get()->values->ptr);
+    KERNEL_CHECK();
+    groups_append_keys(ctx, g, cols, nkeys, firsts.get(), n_new);
+    append_column(ctx, g->canon_keys[0], nc);             // the groups' canonical ids, should a later batch fall back to the table
+    check_flags(ctx, "groups_intern");
+  }
+  hipLaunchKernelGGL(k_dm_ids, rgrid, block, 0, ctx->stream, cid, n, mk, (const uint32_t*)g->dmap->ptr, (uint32_t*)ids->values->ptr);
+  KERNEL_CHECK();
+  g->n_groups += n_new; g->rep = GroupRep::DIRECT_MAP;
+  return true;
+}
+// HASHED: the general table over the key columns, or over the canonical ids sub[c] of the dictionary columns in canon mode
+static void groups_intern_hashed(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_array* const* cols, int32_t nkeys, int64_t n, const uint64_t* mk, const std::vector<ArrayHolder>& sub, dfgpu_array* ids) {
+  std::vector<const dfgpu_array*> eff(cols, cols + nkeys);
+  for (int c = 0; c < nkeys; c++) if (sub[(size_t)c].get()) eff[(size_t)c] = sub[(size_t)c].get();
+  KeySet hk = make_keyset(eff.data(), nkeys);
+  const int has_stored = g->n_groups ? 1 : 0; const KeySet stored = has_stored ? stored_keyset(g) : KeySet{};
+  BufferPtr tmp = alloc_buffer(ctx, (size_t)n * 4);
+  // Known bounds beat the optimism of the first size: a dictionary is interned whole (its entries are mostly distinct: that is what it is
+  // for), and canonical-id tuples cannot form more groups than the product of their domains.
+  if (g->canon_mode) { uint64_t dom = 1; for (int c = 0; c < nkeys && dom < (1ull << 31); c++) dom *= g->canon[(size_t)c].dict ? (uint64_t)g->canon[(size_t)c].n_ids + 1 : (1ull << 31); g->size_hint = (int64_t)(dom < (1ull << 31) ? dom : (1ull << 31)); }
+  const uint64_t want = groups_first_capacity(g, n);
+  if (g->capacity < want) groups_alloc_table(g, want);
+  for (;;) {
+    // a probe sequence this long means the table is ~95 % full (linear probing: ~1 / (2 (1 - load)^2) steps): stop and grow now rather
+    // than crawl to 4096-step sequences first.  Forced collisions put every key in one sequence: its length says nothing there.
+    uint64_t step_cap = ctx->force_hash_collisions ? 4096 : 256, max_steps = g->capacity - 1 < step_cap ? g->capacity - 1 : step_cap;
+    zero_scratch(ctx);
+    { KernelTimer kt_(ctx, "k_groups_find");
+    hipLaunchKernelGGL(k_groups_find, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, hk, stored, has_stored, n, mk,
+                       ctx->force_hash_collisions ? 1 : 0, (uint64_t*)g->slots->ptr, g->capacity - 1, (uint32_t*)g->first_row->ptr, (uint32_t*)tmp->ptr,
+                       (unsigned long long*)ctx->d_scratch64, max_steps); }
+    KERNEL_CHECK();
+    if (read_scratch(ctx, 1) == 0) break;
+    groups_alloc_table(g, groups_overflow_capacity(g->capacity));
+  }
+  BufferPtr bits = alloc_buffer(ctx, bitmap_bytes(n));
+  hipLaunchKernelGGL(k_groups_mark_first, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)tmp->ptr, (const uint32_t*)g->first_row->ptr, n, (uint64_t*)bits->ptr);
+  KERNEL_CHECK();
+  ArrayHolder firsts(mask_to_indices_impl(ctx, (const uint64_t*)bits->ptr, n));
+  int64_t n_new = firsts.get()->length;
+  if (g->n_groups + n_new >= (int64_t)G_NEW) fail(DFGPU_RESOURCES_EXHAUSTED, "more than 2^31 groups");
+  if (n_new) {
+    groups_reserve_ghash(ctx, g, g->n_groups + n_new, g->n_groups);
+    hipLaunchKernelGGL(k_groups_assign, dim3(grid_for(n_new, BLOCK)), dim3(BLOCK), 0, ctx->stream, hk, (const uint32_t*)firsts.get()->values->ptr, n_new, (const uint32_t*)tmp->ptr,
+                       (uint64_t*)g->slots->ptr, (uint32_t*)g->first_row->ptr, (uint32_t)g->n_groups, ctx->force_hash_collisions ? 1 : 0, (uint64_t*)g->ghash->ptr);
+    KERNEL_CHECK();
+    groups_append_keys(ctx, g, cols, nkeys, firsts.get(), n_new);
+    for (int c = 0; c < nkeys; c++) {          // the new groups' canon tuples, for comparisons in later batches
+      if (!sub[(size_t)c].get()) continue;
+      ArrayHolder nk(take_impl(ctx, sub[(size_t)c].get(), firsts.get()->values->ptr, 4, nullptr, n_new));
+      append_column(ctx, g->canon_keys[(size_t)c], nk);
+    }
+    check_flags(ctx, "groups_intern");
+  }
+  hipLaunchKernelGGL(k_groups_finalize, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)tmp->ptr, (const uint64_t*)g->slots->ptr, n, (uint32_t*)ids->values->ptr);
+  KERNEL_CHECK();
+  g->n_groups += n_new; g->rep = GroupRep::HASHED;
+  if (uint64_t ncap = groups_regrow(g->capacity, g->n_groups)) groups_alloc_table(g, ncap);      // rehash of the numbered groups only: no key comparisons
+}
 
-static dfgpu_status groups_intern_impl(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_array* const* cols, int32_t nkeys, const dfgpu_array* opt_mask, dfgpu_array** out_group_ids, bool allow_deferred);
-dfgpu_status dfgpu_groups_intern(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_array* const* cols, int32_t nkeys, const dfgpu_array* opt_mask, dfgpu_array** out_group_ids) {
-  return groups_intern_impl(ctx, g, cols, nkeys, opt_mask, out_group_ids, false);
-}
-dfgpu_status dfgpu_groups_intern_deferred(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_array* const* cols, int32_t nkeys, const dfgpu_array* opt_mask, dfgpu_array** out_group_ids) {
-  return groups_intern_impl(ctx, g, cols, nkeys, opt_mask, out_group_ids, true);
-}
+// The representations are tried in order; each takes the batch or declines.  The general table takes what the others decline.
 static dfgpu_status groups_intern_impl(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_array* const* cols, int32_t nkeys, const dfgpu_array* opt_mask, dfgpu_array** out_group_ids, bool allow_deferred) {
   return guard(ctx, [&] {
     if (!g || !cols || !out_group_ids) fail(DFGPU_INVALID_ARGUMENT, "groups_intern: null argument");
@@ -580,297 +855,22 @@ static dfgpu_status groups_intern_impl(dfgpu_ctx* ctx, dfgpu_groups* g, const df
     int64_t n = cols[0]->length;
     if (n >= (int64_t)G_NEW) fail(DFGPU_NOT_IMPLEMENTED, "intern batches above 2^31 rows; split the batch");
     for (int c = 0; c < nkeys; c++) if (g->keys[c] && logical_type(cols[c]) != g->keys[c]->type) fail(DFGPU_INVALID_ARGUMENT, "groups_intern: key %d changed type", c);
-    BufferPtr mask = effective_mask(ctx, opt_mask, n);
+    BufferPtr mask = effective_mask(ctx, opt_mask, n); const uint64_t* mk = mask ? (const uint64_t*)mask->ptr : nullptr;
     ArrayHolder ids(new_fixed(ctx, DFGPU_UINT32, n));
-    if (n == 0) { *out_group_ids = ids.release(); return; }
-    // clustered keys: group ids are run numbers, no hash table (the shape of GROUP BY over a fact table stored in key order)
-    if (ctx->group_run_detection && !ctx->force_hash_collisions && !mask && g->capacity == 0 && (g->n_groups == 0 || g->run_mode) && run_key_type(cols[0]) &&
-        groups_intern_runs(ctx, g, cols, nkeys, bk, n, ids.get(), allow_deferred)) { *out_group_ids = ids.release(); return; }
-    // one 8-byte integer key column without NULLs: the primitive-key table
-    auto plain8 = [](const dfgpu_array* a) { return a && (a->type == DFGPU_INT64 || a->type == DFGPU_UINT64 || a->type == DFGPU_INT32 || a->type == DFGPU_UINT32 || a->type == DFGPU_DATE32) && !a->validity; };
-    const bool prim_ok = nkeys == 1 && !ctx->force_hash_collisions && !g->prim_banned && !g->canon_mode && g->capacity == 0 && plain8(cols[0]) && (g->n_groups == 0 || (plain8(g->keys[0]) && g->keys[0]->type == cols[0]->type));
-    const bool key4 = prim_ok && type_width(cols[0]->type) == 4;
-    if (g->prim_mode && !prim_ok) { g->prim_mode = false; g->pslots.reset(); g->pcap = 0; g->run_mode = g->n_groups > 0; }      // NULLs / another type arrived: re-hash the stored groups below
-    if (prim_ok) {
-      const uint64_t* mk = mask ? (const uint64_t*)mask->ptr : nullptr;
-      const void* kp = cols[0]->values->ptr;
-      auto rebuild = [&](uint64_t cap) {
-        g->pslots = alloc_buffer(ctx, (size_t)cap * sizeof(PSlot)); g->pcap = cap;
-        HIP_CHECK(hipMemsetAsync(g->pslots->ptr, 0xFF, (size_t)cap * sizeof(PSlot), ctx->stream));
-        if (g->n_groups) {
-          if (key4) hipLaunchKernelGGL((k_prim_insert<uint32_t>), dim3(grid_for(g->n_groups, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)g->keys[0]->values->ptr, g->n_groups, (PSlot*)g->pslots->ptr, cap - 1);
-          else hipLaunchKernelGGL((k_prim_insert<unsigned long long>), dim3(grid_for(g->n_groups, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const unsigned long long*)g->keys[0]->values->ptr, g->n_groups, (PSlot*)g->pslots->ptr, cap - 1);
-          KERNEL_CHECK();
-        }
-      };
-      uint64_t expect = (uint64_t)(n < (1 << 22) ? n : (1 << 22));
-      if (g->size_hint > 0) { uint64_t h = (uint64_t)g->size_hint < (uint64_t)n ? (uint64_t)g->size_hint : (uint64_t)n; if (h > expect) expect = h; }
-      uint64_t want = 1ull << 16; while (want < (uint64_t)g->n_groups * 4 + 2 * expect) want <<= 1;
-      if (g->pcap < want) rebuild(want);
-      g->prim_mode = true; g->run_mode = false;
-      BufferPtr tmp = alloc_buffer(ctx, (size_t)n * 4);
-      bool banned = false;
-      for (;;) {
-        zero_scratch(ctx);
-        { KernelTimer kt_(ctx, "k_groups_find");
-          dim3 fg(grid_for(n, BLOCK * PF_ROWS));
-#define PFIND(KT, HM) hipLaunchKernelGGL((k_prim_find<KT, HM>), fg, dim3(BLOCK), 0, ctx->stream, (const KT*)kp, n, mk, (PSlot*)g->pslots->ptr, g->pcap - 1, (uint32_t*)tmp->ptr, (unsigned long long*)ctx->d_scratch64, (uint64_t)256)
-          if (key4) { if (mk) PFIND(uint32_t, true); else PFIND(uint32_t, false); } else { if (mk) PFIND(unsigned long long, true); else PFIND(unsigned long long, false); }
-#undef PFIND
-        }
-        KERNEL_CHECK();
-        ctx->count_sync("sync:group_table"); fetch_to_pinned(ctx, 0, ctx->d_scratch64, 32);
-        if (ctx->h_pinned[3]) { banned = true; break; }
-        if (ctx->h_pinned[1] == 0) break;
-        if (g->pcap >= (1ull << 31)) fail(DFGPU_RESOURCES_EXHAUSTED, "group table would exceed 2^31 slots");
-        uint64_t ncap = g->pcap << 3; if (ncap > (1ull << 31)) ncap = 1ull << 31;
-        rebuild(ncap);                                            // the claims of the overfull pass go with the old table
+    if (n > 0 && !groups_intern_runs(ctx, g, cols, nkeys, bk, n, mk, ids.get(), allow_deferred) && !groups_intern_primitive(ctx, g, cols, nkeys, n, mk, ids.get())) {
+      if (g->rep == GroupRep::RUNS || g->rep == GroupRep::PRIMITIVE) groups_hash_stored(ctx, g);       // a batch broke the order / left the primitive table
+      std::vector<ArrayHolder> sub((size_t)nkeys); bool done = false;      // sub: canonical ids of the dictionary key columns (canon mode)
+      if (groups_canon_setup(ctx, g, cols, nkeys)) {
+        done = groups_intern_dense(ctx, g, cols, nkeys, n, mask, ids.get(), allow_deferred);
+        if (!done) groups_canon_lookup(ctx, g, cols, nkeys, n, sub);
       }
-      if (banned) {                                               // a key equals the empty marker: this column takes the general table from now on
-        g->prim_banned = true; g->prim_mode = false; g->pslots.reset(); g->pcap = 0; g->run_mode = g->n_groups > 0;
-      } else {
-        BufferPtr bits = alloc_buffer(ctx, bitmap_bytes((int64_t)g->pcap));
-        hipLaunchKernelGGL(k_prim_new_bits, dim3(grid_for((int64_t)g->pcap, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const PSlot*)g->pslots->ptr, (int64_t)g->pcap, (uint64_t*)bits->ptr);
-        KERNEL_CHECK();
-        ArrayHolder new_slots(mask_to_indices_impl(ctx, (const uint64_t*)bits->ptr, (int64_t)g->pcap));
-        int64_t n_new = new_slots.get()->length;
-        if (g->n_groups + n_new >= (int64_t)G_NEW) fail(DFGPU_RESOURCES_EXHAUSTED, "more than 2^31 groups");
-        if (n_new) {
-          ArrayHolder firsts(new_fixed(ctx, DFGPU_UINT32, n_new));
-          hipLaunchKernelGGL(k_prim_first_of, dim3(grid_for(n_new, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)new_slots.get()->values->ptr, n_new, (const PSlot*)g->pslots->ptr, (uint32_t*)firsts.get()->values->ptr);
-          KERNEL_CHECK();
-          int bitsn = 1; while ((1ll << bitsn) < n) bitsn++;
-          radix_sort_pairs_u32(ctx, (uint32_t*)firsts.get()->values->ptr, (uint32_t*)new_slots.get()->values->ptr, n_new, bitsn);      // first-seen order
-          hipLaunchKernelGGL(k_prim_assign, dim3(grid_for(n_new, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)new_slots.get()->values->ptr, n_new, (uint32_t)g->n_groups, (PSlot*)g->pslots->ptr);
-          KERNEL_CHECK();
-          groups_append_keys(ctx, g, cols, nkeys, firsts.get(), n_new);
-          check_flags(ctx, "groups_intern");
-        }
-        hipLaunchKernelGGL(k_prim_ids, dim3(grid_for(n, BLOCK * PF_ROWS)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)tmp->ptr, n, (const PSlot*)g->pslots->ptr, (uint32_t*)ids.get()->values->ptr);
-        KERNEL_CHECK();
-        g->n_groups += n_new;
-        if ((uint64_t)g->n_groups * 2 > g->pcap) { uint64_t ncap = g->pcap; while (ncap < (uint64_t)g->n_groups * 4) ncap <<= 1; if (ncap > (1ull << 31)) ncap = 1ull << 31; rebuild(ncap); }
-        *out_group_ids = ids.release();
-        return;
-      }
+      if (!done && !groups_intern_direct(ctx, g, cols, nkeys, n, mk, sub[0].get(), ids.get())) groups_intern_hashed(ctx, g, cols, nkeys, n, mk, sub, ids.get());
     }
-    if (g->run_mode) {          // a batch broke the order: hash the groups numbered so far, the table is built below
-      std::vector<const dfgpu_array*> sk(g->keys.begin(), g->keys.end()); KeySet stored_ks = make_keyset(sk.data(), nkeys);
-      groups_reserve_ghash(ctx, g, g->n_groups, 0);
-      hipLaunchKernelGGL(k_groups_hash_stored, dim3(grid_for(g->n_groups, BLOCK)), dim3(BLOCK), 0, ctx->stream, stored_ks, g->n_groups, ctx->force_hash_collisions ? 1 : 0, (uint64_t*)g->ghash->ptr);
-      KERNEL_CHECK();
-      g->run_mode = false;
-    }
-    // dictionary key columns: intern u32 canonical ids of the dictionary VALUES instead of hashing / comparing the values per row
-    std::vector<const dfgpu_array*> eff(cols, cols + nkeys); std::vector<ArrayHolder> sub((size_t)nkeys);
-    bool any_dict = false; for (int c = 0; c < nkeys; c++) any_dict |= cols[c]->type == DFGPU_DICTIONARY && cols[c]->dictionary != nullptr;
-    bool want_canon = ctx->group_dictionary_canon && !ctx->force_hash_collisions && any_dict && (g->n_groups == 0 || g->canon_mode);
-    if (want_canon && g->canon_mode)
-      for (int c = 0; c < nkeys; c++) { const dfgpu_array* d = cols[c]->type == DFGPU_DICTIONARY ? cols[c]->dictionary : nullptr; if (d != g->canon[(size_t)c].dict) want_canon = false; }
-    if (g->canon_mode && !want_canon) {       // another dictionary (or none): back to value keys; the numbered groups are re-hashed by value
-      for (auto*& a : g->canon_keys) { if (a) dfgpu_array_release(a); a = nullptr; }
-      for (auto& cc : g->canon) { if (cc.dict) dfgpu_array_release(cc.dict); cc = dfgpu_groups::Canon{}; }
-      g->canon_mode = false; g->dense_size = 0; g->dense_map.reset(); g->dense_host.clear(); g->dmap.reset(); g->dmap_size = 0;
-      if (g->n_groups) {
-        std::vector<const dfgpu_array*> sk(g->keys.begin(), g->keys.end()); KeySet stored_ks = make_keyset(sk.data(), nkeys);
-        groups_reserve_ghash(ctx, g, g->n_groups, 0);
-        hipLaunchKernelGGL(k_groups_hash_stored, dim3(grid_for(g->n_groups, BLOCK)), dim3(BLOCK), 0, ctx->stream, stored_ks, g->n_groups, 0, (uint64_t*)g->ghash->ptr);
-        KERNEL_CHECK();
-        if (g->capacity) { uint64_t cap = g->capacity; while (cap < (uint64_t)g->n_groups * 4) cap <<= 1; groups_alloc_table(g, cap); }     // groups numbered through the direct map never entered the table
-      }
-    }
-    if (want_canon) {
-      if (!g->canon_mode) {
-        g->canon.assign((size_t)nkeys, dfgpu_groups::Canon{}); g->canon_keys.assign((size_t)nkeys, nullptr);
-        for (int c = 0; c < nkeys; c++) {
-          if (cols[c]->type != DFGPU_DICTIONARY) continue;
-          const dfgpu_array* dict = cols[c]->dictionary;
-          dfgpu_groups tmp; tmp.ctx = ctx; tmp.nkeys = 1; tmp.keys.assign(1, nullptr); tmp.size_hint = dict->length;
-          dfgpu_array* dids = nullptr; dfgpu_status st = dfgpu_groups_intern(ctx, &tmp, &dict, 1, nullptr, &dids);
-          if (st != DFGPU_OK) fail(st, "%s", ctx->err.c_str());
-          ArrayHolder hold(dids);
-          auto& cc = g->canon[(size_t)c]; cc.dict = const_cast<dfgpu_array*>(dict); dfgpu_array_retain(cc.dict); cc.ids = dids->values; cc.n_ids = tmp.n_groups;
-        }
-        g->canon_mode = true;
-      }
-      // dense composite domain: index a small map directly
-      bool all_dict = true; int64_t dsize = 1;
-      for (int c = 0; c < nkeys; c++) { if (!g->canon[(size_t)c].dict) { all_dict = false; break; } dsize *= g->canon[(size_t)c].n_ids + 1; if (dsize > DENSE_MAX) break; }
-      if (all_dict && dsize <= DENSE_MAX && (g->dense_size == dsize || g->n_groups == 0)) {
-        KernelTimer kt_(ctx, "k_groups_dense");
-        if (g->dense_size != dsize) { g->dense_size = dsize; g->dense_host.assign((size_t)dsize, G_NONE); g->dense_map = alloc_buffer(ctx, (size_t)dsize * 4); HIP_CHECK(hipMemsetAsync(g->dense_map->ptr, 0xFF, (size_t)dsize * 4, ctx->stream)); }
-        DenseCols dc{}; dc.n = nkeys; uint32_t stride = 1;
-        for (int c = nkeys - 1; c >= 0; c--) {
-          auto& cc = g->canon[(size_t)c]; DenseCol& d = dc.c[c];
-          d.keys = cols[c]->values->ptr; d.key_valid = cols[c]->validity ? (const uint64_t*)cols[c]->validity->ptr : nullptr; d.key_type = cols[c]->key_type;
-          d.canon = (const uint32_t*)cc.ids->ptr; d.dict_valid = cc.dict->validity ? (const uint64_t*)cc.dict->validity->ptr : nullptr; d.dict_len = cc.dict->length;
-          d.n_ids = (uint32_t)cc.n_ids; d.stride = stride; stride *= (uint32_t)cc.n_ids + 1;
-        }
-        BufferPtr first = alloc_buffer(ctx, (size_t)dsize * 4);
-        HIP_CHECK(hipMemsetAsync(first->ptr, 0xFF, (size_t)dsize * 4, ctx->stream));
-        const uint64_t* mk = mask ? (const uint64_t*)mask->ptr : nullptr;
-        dim3 grid(grid_for(n, BLOCK)), block(BLOCK);
-        // straight-line kernels when every code column has the same integer type and nothing is nullable (codes must then be in range:
-        // Arrow requires valid dictionary codes; the generic kernels also tolerate out-of-range codes as NULL)
-        bool fast = nkeys <= 2; int kt0 = cols[0]->key_type;
-        for (int c = 0; c < nkeys; c++) fast = fast && cols[c]->key_type == kt0 && !dc.c[c].key_valid && !dc.c[c].dict_valid;
-        fast = fast && (kt0 == DFGPU_INT8 || kt0 == DFGPU_INT16 || kt0 == DFGPU_INT32);
-        int fgrid = grid_for(n, BLOCK * DENSE_ROWS, ctx->num_cus * 8);
-#define DENSE_FAST(K, NC, WHICH, GRID, ...) do { if (mk) hipLaunchKernelGGL((WHICH<K, NC, true>), dim3(GRID), block, 0, ctx->stream, __VA_ARGS__); else hipLaunchKernelGGL((WHICH<K, NC, false>), dim3(GRID), block, 0, ctx->stream, __VA_ARGS__); } while (0)
-#define DENSE_DISPATCH(WHICH, GRID, ...) do { \
-          if (kt0 == DFGPU_INT8) { if (nkeys == 1) DENSE_FAST(int8_t, 1, WHICH, GRID, __VA_ARGS__); else DENSE_FAST(int8_t, 2, WHICH, GRID, __VA_ARGS__); } \
-          else if (kt0 == DFGPU_INT16) { if (nkeys == 1) DENSE_FAST(int16_t, 1, WHICH, GRID, __VA_ARGS__); else DENSE_FAST(int16_t, 2, WHICH, GRID, __VA_ARGS__); } \
-          else { if (nkeys == 1) DENSE_FAST(int32_t, 1, WHICH, GRID, __VA_ARGS__); else DENSE_FAST(int32_t, 2, WHICH, GRID, __VA_ARGS__); } } while (0)
-        const int64_t len1 = nkeys == 2 ? dc.c[1].dict_len : 1;
-        bool tab = fast && dc.c[0].dict_len * len1 <= DENSE_MAX && dsize <= 65535;
-        for (int c = 0; c < nkeys && tab; c++) tab = (((uintptr_t)dc.c[c].keys) & 15) == 0;
-        if (tab) DENSE_DISPATCH(k_dense_first_tab, grid_for(n, BLOCK * 4, ctx->num_cus * 8), dc, n, mk, (const uint32_t*)g->dense_map->ptr, (uint32_t*)first->ptr, (int)dsize, (int)len1);
-        else if (fast) DENSE_DISPATCH(k_dense_first_fast, fgrid, dc, n, mk, (const uint32_t*)g->dense_map->ptr, (uint32_t*)first->ptr, (int)dsize);
-        else hipLaunchKernelGGL(k_dense_first, dim3(fgrid), block, 0, ctx->stream, dc, n, mk, (const uint32_t*)g->dense_map->ptr, (uint32_t*)first->ptr, (int)dsize);
-        KERNEL_CHECK();
-        std::vector<uint32_t> fh((size_t)dsize);
-        ctx->count_sync("sync:dense_groups"); fetch_to_host(ctx, fh.data(), first->ptr, (size_t)dsize * 4);
-        std::vector<std::pair<uint32_t, uint32_t>> fresh;             // (first row, composite) of the composites met for the first time
-        for (int64_t comp = 0; comp < dsize; comp++) if (fh[(size_t)comp] != G_NONE) fresh.emplace_back(fh[(size_t)comp], (uint32_t)comp);
-        std::sort(fresh.begin(), fresh.end());                        // first-seen order
-        int64_t n_new = (int64_t)fresh.size();
-        if (n_new) {
-          std::vector<uint32_t> rows((size_t)n_new);
-          for (int64_t k2 = 0; k2 < n_new; k2++) { g->dense_host[fresh[(size_t)k2].second] = (uint32_t)(g->n_groups + k2); rows[(size_t)k2] = fresh[(size_t)k2].first; }
-          HIP_CHECK(hipMemcpyAsync(g->dense_map->ptr, g->dense_host.data(), (size_t)dsize * 4, hipMemcpyHostToDevice, ctx->stream));
-          ArrayHolder firsts(new_fixed(ctx, DFGPU_UINT32, n_new));
-          HIP_CHECK(hipMemcpyAsync(firsts.get()->values->ptr, rows.data(), (size_t)n_new * 4, hipMemcpyHostToDevice, ctx->stream));
-          HIP_CHECK(hipStreamSynchronize(ctx->stream));               // rows / dense_host are host vectors
-          groups_append_keys(ctx, g, cols, nkeys, firsts.get(), n_new);
-        }
-        if (fast && allow_deferred) {       // the ids are a pure function of the code columns and the map: the consumer computes them in its own pass
-          auto d = std::make_shared<DeferredIds>(); d->dc = dc; d->key_type = kt0; d->mask = mask; d->dense_map = g->dense_map;
-          for (int c = 0; c < nkeys; c++) { d->keep.push_back(cols[c]->values); d->keep.push_back(g->canon[(size_t)c].ids); }
-          ids.get()->deferred_ids = d;
-        }
-        else if (fast) DENSE_DISPATCH(k_dense_ids_fast, grid_for(n, BLOCK * DENSE_ROWS), dc, n, mk, (const uint32_t*)g->dense_map->ptr, (uint32_t*)ids.get()->values->ptr);
-        else hipLaunchKernelGGL(k_dense_ids, dim3(grid_for(n, BLOCK * DENSE_ROWS)), block, 0, ctx->stream, dc, n, mk, (const uint32_t*)g->dense_map->ptr, (uint32_t*)ids.get()->values->ptr);
-#undef DENSE_DISPATCH
-#undef DENSE_FAST
-        KERNEL_CHECK();
-        g->n_groups += n_new;
-        *out_group_ids = ids.release();
-        return;
-      }
-      if (g->dense_size) {           // the composite domain outgrew the dense map (cannot happen with unchanged dictionaries); safest: value keys
-        fail(DFGPU_INTERNAL, "dense dictionary group map changed size");
-      }
-      for (int c = 0; c < nkeys; c++) {
-        if (cols[c]->type != DFGPU_DICTIONARY) continue;
-        auto& cc = g->canon[(size_t)c];
-        sub[(size_t)c].a = new_fixed(ctx, DFGPU_UINT32, n);
-        KernelTimer kt_(ctx, "k_canon_lookup");
-        hipLaunchKernelGGL(k_canon_lookup, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, cols[c]->values->ptr, cols[c]->key_type, cols[c]->validity ? (const uint64_t*)cols[c]->validity->ptr : nullptr, n,
-                           (const uint32_t*)cc.ids->ptr, cc.dict->validity ? (const uint64_t*)cc.dict->validity->ptr : nullptr, cc.dict->length, (uint32_t)cc.n_ids, (uint32_t*)sub[(size_t)c].get()->values->ptr);
-        KERNEL_CHECK();
-        eff[(size_t)c] = sub[(size_t)c].get();
-      }
-    }
-    // one dictionary key column: the canonical ids are dense, so a direct map replaces the hash table (find, first-row marking, numbering)
-    if (g->canon_mode && nkeys == 1 && sub[0].get() && (g->dmap || n >= (1 << 16)) && g->canon[0].n_ids + 1 <= (1ll << 28)) {
-      KernelTimer kt_(ctx, "k_groups_dmap");
-      const int64_t dom = g->canon[0].n_ids + 1;
-      const uint32_t* cid = (const uint32_t*)sub[0].get()->values->ptr;
-      const uint64_t* mk = mask ? (const uint64_t*)mask->ptr : nullptr;
-      if (!g->dmap) {
-        g->dmap = alloc_buffer(ctx, (size_t)dom * 4); g->dmap_size = dom;
-        HIP_CHECK(hipMemsetAsync(g->dmap->ptr, 0xFF, (size_t)dom * 4, ctx->stream));
-        if (g->n_groups) { hipLaunchKernelGGL(k_dm_seed, dim3(grid_for(g->n_groups, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)g->canon_keys[0]->values->ptr, g->n_groups, (uint32_t*)g->dmap->ptr); KERNEL_CHECK(); }
-      }
-      if (g->dmap_size != dom) fail(DFGPU_INTERNAL, "dictionary group map changed size");
-      BufferPtr first = alloc_buffer(ctx, (size_t)dom * 4), heads = alloc_buffer(ctx, bitmap_bytes(n));
-      HIP_CHECK(hipMemsetAsync(first->ptr, 0xFF, (size_t)dom * 4, ctx->stream));
-      dim3 rgrid(grid_for(n, BLOCK * DM_ROWS)), block(BLOCK);
-      hipLaunchKernelGGL(k_dm_first, rgrid, block, 0, ctx->stream, cid, n, mk, (const uint32_t*)g->dmap->ptr, (uint32_t*)first->ptr);
-      hipLaunchKernelGGL(k_dm_heads, rgrid, block, 0, ctx->stream, cid, n, mk, (const uint32_t*)g->dmap->ptr, (const uint32_t*)first->ptr, (uint64_t*)heads->ptr);
-      KERNEL_CHECK();
-      ArrayHolder firsts(mask_to_indices_impl(ctx, (const uint64_t*)heads->ptr, n));
-      int64_t n_new = firsts.get()->length;
-      if (g->n_groups + n_new >= (int64_t)G_NEW) fail(DFGPU_RESOURCES_EXHAUSTED, "more than 2^31 groups");
-      if (n_new) {
-        ArrayHolder nc(new_fixed(ctx, DFGPU_UINT32, n_new));
-        hipLaunchKernelGGL(k_dm_assign, dim3(grid_for(n_new, BLOCK)), block, 0, ctx->stream, (const uint32_t*)firsts.get()->values->ptr, n_new, cid, (uint32_t)g->n_groups, (uint32_t*)g->dmap->ptr, (uint32_t*)nc.get()->values->ptr);
-        KERNEL_CHECK();
-        groups_append_keys(ctx, g, cols, nkeys, firsts.get(), n_new);
-        dfgpu_array*& dst = g->canon_keys[0];             // the groups' canonical ids, should a later batch fall back to the table
-        if (!dst) dst = nc.release();
-        else { const dfgpu_array* parts[2] = { dst, nc.get() }; dfgpu_array* cat = nullptr; dfgpu_status st = dfgpu_concat(ctx, parts, 2, &cat); if (st != DFGPU_OK) fail(st, "%s", ctx->err.c_str()); dfgpu_array_release(dst); dst = cat; }
-        check_flags(ctx, "groups_intern");
-      }
-      hipLaunchKernelGGL(k_dm_ids, rgrid, block, 0, ctx->stream, cid, n, mk, (const uint32_t*)g->dmap->ptr, (uint32_t*)ids.get()->values->ptr);
-      KERNEL_CHECK();
-      g->n_groups += n_new;
-      *out_group_ids = ids.release();
-      return;
-    }
-    KeySet hk = make_keyset(eff.data(), nkeys);
-    KeySet stored{}; int has_stored = 0;
-    if (g->n_groups) {
-      std::vector<const dfgpu_array*> sk(g->keys.begin(), g->keys.end());
-      if (g->canon_mode) for (int c = 0; c < nkeys; c++) if (g->canon_keys[(size_t)c]) sk[(size_t)c] = g->canon_keys[(size_t)c];
-      stored = make_keyset(sk.data(), nkeys); has_stored = 1;
-    }
-    BufferPtr tmp = alloc_buffer(ctx, (size_t)n * 4);
-    // optimistic table size (at most 2^23 slots up front); a batch that overfills it is redone on a table 8x larger
-    // Known bounds beat the optimism: a dictionary is interned whole (its entries are mostly distinct: that is what it is for), and
-    // canonical-id tuples cannot form more groups than the product of their domains.
-    uint64_t expect = (uint64_t)(n < (1 << 22) ? n : (1 << 22));
-    if (g->canon_mode) { uint64_t dom = 1; for (int c = 0; c < nkeys && dom < (1ull << 31); c++) dom *= g->canon[(size_t)c].dict ? (uint64_t)g->canon[(size_t)c].n_ids + 1 : (1ull << 31); g->size_hint = (int64_t)(dom < (1ull << 31) ? dom : (1ull << 31)); }
-    if (g->size_hint > 0) { uint64_t h = (uint64_t)g->size_hint < (uint64_t)n ? (uint64_t)g->size_hint : (uint64_t)n; if (h > expect) expect = h; }
-    uint64_t guess = (uint64_t)g->n_groups * 4 + 2 * expect;
-    uint64_t want = 1ull << 16; while (want < guess) want <<= 1;
-    if (g->capacity < want) groups_alloc_table(g, want);
-    int64_t n_new = 0;
-    for (;;) {
-      // a probe sequence this long means the table is ~95 % full (linear probing: ~1 / (2 (1 - load)^2) steps): stop and grow now rather
-      // than crawl to 4096-step sequences first.  Forced collisions put every key in one sequence: its length says nothing there.
-      uint64_t step_cap = ctx->force_hash_collisions ? 4096 : 256;
-      uint64_t max_steps = g->capacity - 1 < step_cap ? g->capacity - 1 : step_cap;
-      zero_scratch(ctx);
-      { KernelTimer kt_(ctx, "k_groups_find");
-      hipLaunchKernelGGL(k_groups_find, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, hk, stored, has_stored, n, mask ? (const uint64_t*)mask->ptr : nullptr,
-                         ctx->force_hash_collisions ? 1 : 0, (uint64_t*)g->slots->ptr, g->capacity - 1, (uint32_t*)g->first_row->ptr, (uint32_t*)tmp->ptr,
-                         (unsigned long long*)ctx->d_scratch64, max_steps); }
-      KERNEL_CHECK();
-      if (read_scratch(ctx, 1) == 0) break;
-      if (g->capacity >= (1ull << 31)) fail(DFGPU_RESOURCES_EXHAUSTED, "group table would exceed 2^31 slots");
-      uint64_t ncap = g->capacity << 3; if (ncap > (1ull << 31)) ncap = 1ull << 31;
-      groups_alloc_table(g, ncap);
-    }
-    BufferPtr bits = alloc_buffer(ctx, bitmap_bytes(n));
-    hipLaunchKernelGGL(k_groups_mark_first, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)tmp->ptr, (const uint32_t*)g->first_row->ptr, n, (uint64_t*)bits->ptr);
-    KERNEL_CHECK();
-    ArrayHolder firsts(mask_to_indices_impl(ctx, (const uint64_t*)bits->ptr, n));
-    n_new = firsts.get()->length;
-    if (g->n_groups + n_new >= (int64_t)G_NEW) fail(DFGPU_RESOURCES_EXHAUSTED, "more than 2^31 groups");
-    if (n_new) {
-      groups_reserve_ghash(ctx, g, g->n_groups + n_new, g->n_groups);
-      hipLaunchKernelGGL(k_groups_assign, dim3(grid_for(n_new, BLOCK)), dim3(BLOCK), 0, ctx->stream, hk, (const uint32_t*)firsts.get()->values->ptr, n_new, (const uint32_t*)tmp->ptr,
-                         (uint64_t*)g->slots->ptr, (uint32_t*)g->first_row->ptr, (uint32_t)g->n_groups, ctx->force_hash_collisions ? 1 : 0, (uint64_t*)g->ghash->ptr);
-      KERNEL_CHECK();
-      groups_append_keys(ctx, g, cols, nkeys, firsts.get(), n_new);
-      if (g->canon_mode) for (int c = 0; c < nkeys; c++) {          // the new groups' canon tuples, for comparisons in later batches
-        if (!sub[(size_t)c].get()) continue;
-        ArrayHolder nk(take_impl(ctx, sub[(size_t)c].get(), firsts.get()->values->ptr, 4, nullptr, n_new));
-        dfgpu_array*& dst = g->canon_keys[(size_t)c];
-        if (!dst) dst = nk.release();
-        else { const dfgpu_array* parts[2] = { dst, nk.get() }; dfgpu_array* cat = nullptr; dfgpu_status st = dfgpu_concat(ctx, parts, 2, &cat); if (st != DFGPU_OK) fail(st, "%s", ctx->err.c_str()); dfgpu_array_release(dst); dst = cat; }
-      }
-      check_flags(ctx, "groups_intern");
-    }
-    hipLaunchKernelGGL(k_groups_finalize, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)tmp->ptr, (const uint64_t*)g->slots->ptr, n, (uint32_t*)ids.get()->values->ptr);
-    KERNEL_CHECK();
-    g->n_groups += n_new;
-    // keep the load factor <= 1/2 for the next batch (rehash of the numbered groups only: no key comparisons)
-    if ((uint64_t)g->n_groups * 2 > g->capacity) { uint64_t ncap = g->capacity; while (ncap < (uint64_t)g->n_groups * 4) ncap <<= 1; if (ncap > (1ull << 31)) ncap = 1ull << 31; groups_alloc_table(g, ncap); }
     *out_group_ids = ids.release();
   });
 }
+dfgpu_status dfgpu_groups_intern(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_array* const* cols, int32_t nkeys, const dfgpu_array* opt_mask, dfgpu_array** out_group_ids) { return groups_intern_impl(ctx, g, cols, nkeys, opt_mask, out_group_ids, false); }
+dfgpu_status dfgpu_groups_intern_deferred(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_array* const* cols, int32_t nkeys, const dfgpu_array* opt_mask, dfgpu_array** out_group_ids) { return groups_intern_impl(ctx, g, cols, nkeys, opt_mask, out_group_ids, true); }
 
 dfgpu_status dfgpu_groups_emit(dfgpu_ctx* ctx, dfgpu_groups* g, dfgpu_array** out_cols) {
   return guard(ctx, [&] {
@@ -905,7 +905,7 @@ dfgpu_status dfgpu_groups_emit_first(dfgpu_ctx* ctx, dfgpu_groups* g, int64_t n,
     }
     // the remaining groups are renumbered from 0 (EmitTo::take_needed, expr/src/groups_accumulator.rs:44-57; GroupValuesRows::emit First(n) rebuilds its map the same way,
     // group_values/row.rs:176-212): a fresh table over the remaining keys -- distinct, interned in order, so they get ids 0 .. total - k - 1
-    g->~dfgpu_groups(); new (g) dfgpu_groups(); g->ctx = ctx; g->nkeys = nkeys; g->keys.assign((size_t)nkeys, nullptr);
+    g->reset();
     if (k < total) {
       std::vector<const dfgpu_array*> rp; for (auto& h : rest) rp.push_back(h.get());
       dfgpu_array* ids = nullptr; dfgpu_status st = dfgpu_groups_intern(ctx, g, rp.data(), nkeys, nullptr, &ids); if (st != DFGPU_OK) fail(st, "%s", ctx->err.c_str());

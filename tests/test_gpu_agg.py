@@ -661,3 +661,90 @@ def test_run_mode_group_keys_stay_ungathered_until_needed(ctx):
         assert gv2.emit_deferred() is None and np.array_equal(gv2.emit()[0].to_numpy(), k0[::4])
     finally:
         ctx.set_option("group_lazy_keys", 1)
+
+
+def _groups_path(prof):
+    """the GroupValues representation that numbered a batch, from its profile (dictionary interning for canon mode shows as k_groups_find)"""
+    for name, path in (("k_groups_dmap", "direct"), ("k_groups_dense", "dense"), ("sync:group_table", "primitive"), ("k_groups_find", "hashed"), ("k_groups_runs", "runs")):
+        if name in prof:
+            return path
+
+
+def _representation_sequence(name):
+    """(key columns of the whole sequence, steps): a step is (lo, hi, mask, expected path) -- rows lo:hi of every column as one batch --
+    or ("emit_first", k).  Dictionary columns are sliced from one device array, so every batch brings the same dictionary; the other
+    columns are copied per batch (a batch without NULLs has no validity bitmap)."""
+    rng = np.random.default_rng(33)
+    off = lambda n: np.zeros(n, dtype=bool)
+    if name == "masked_primitive_runs_unclustered":          # the primitive table of an all-masked batch must learn the groups numbered by runs
+        k = np.concatenate([rng.integers(0, 10**6, 100000), np.arange(1000), rng.permutation(1000)])
+        return [pa.array(k)], [(0, 100000, off(100000), "primitive"), (100000, 101000, None, "runs"), (101000, 102000, None, "primitive")]
+    if name in ("runs_then_masked_one_key", "runs_then_masked_two_keys"):
+        k = np.concatenate([np.repeat(np.arange(3000), 3), rng.integers(0, 6000, 20000), rng.integers(0, 9000, 20000)])
+        cols = [pa.array(k)] if name.endswith("one_key") else [pa.array(k), pa.array((k % 7).astype(np.int32))]
+        path = "primitive" if name.endswith("one_key") else "hashed"
+        return cols, [(0, 9000, None, "runs"), ("emit_first", 100), (9000, 29000, rng.random(20000) < 0.5, path), (29000, 49000, None, path)]
+    if name == "runs_then_unordered_multi_key":               # clustered, but starting below the last group: the order breaks
+        k = np.concatenate([np.repeat(np.arange(1000, 4000), 2), np.repeat(np.arange(0, 2000), 2), np.repeat(np.arange(5000, 6000), 2)])
+        return [pa.array(k), pa.array((k % 5).astype(np.int32))], [(0, 6000, None, "runs"), (6000, 10000, None, "hashed"), ("emit_first", 2500), (10000, 12000, None, "hashed")]
+    if name in ("masked_hashed_then_runs", "masked_hashed_then_primitive"):
+        k = np.concatenate([rng.integers(0, 5000, 8000), np.repeat(np.arange(2000), 2), rng.integers(0, 5000, 8000)])
+        if name.endswith("runs"):                              # two keys: the general table; then a clustered batch
+            return [pa.array(k), pa.array((k % 3).astype(np.int32))], [(0, 8000, off(8000), "hashed"), (8000, 12000, None, "hashed"), ("emit_first", 1000), (12000, 20000, None, "hashed")]
+        nulls = np.concatenate([rng.random(8000) < 0.1, off(12000)])       # NULLs in the masked first batch only: then primitive-shaped batches
+        return [pa.array(k, mask=nulls)], [(0, 8000, off(8000), "hashed"), (12000, 20000, None, "hashed"), ("emit_first", 1000), (8000, 12000, None, "primitive")]
+    if name == "masked_dense_then_dense":
+        w1, w2 = pa.array(["A", "N", "R", "A"]), pa.array(["F", "O"])
+        c1 = pa.DictionaryArray.from_arrays(pa.array(rng.integers(0, 4, 30000).astype(np.int8)), w1)
+        c2 = pa.DictionaryArray.from_arrays(pa.array(rng.integers(0, 2, 30000).astype(np.int8)), w2)
+        return [c1, c2], [(0, 10000, off(10000), "dense"), (10000, 20000, None, "dense"), ("emit_first", 2), (20000, 30000, None, "hashed")]
+    if name == "masked_direct_then_direct":
+        words = pa.array([f"w{v:05d}" for v in range(6000)])
+        c = pa.DictionaryArray.from_arrays(pa.array(rng.integers(0, 6000, 180000).astype(np.int32)), words)
+        return [c], [(0, 70000, off(70000), "direct"), (70000, 70300, None, "direct"), (70300, 140000, None, "direct"), ("emit_first", 1000), (140000, 180000, None, "hashed")]
+    raise KeyError(name)
+
+
+@pytest.mark.parametrize("name", ["masked_primitive_runs_unclustered", "runs_then_masked_one_key", "runs_then_masked_two_keys", "runs_then_unordered_multi_key",
+                                  "masked_hashed_then_runs", "masked_hashed_then_primitive", "masked_dense_then_dense", "masked_direct_then_direct"])
+def test_group_values_moves_between_representations_like_the_oracle(ctx, name):
+    """GroupValues numbers a batch by runs, the primitive table, the dense or direct dictionary maps, or the general table, and a later batch
+    may need another one.  Over batch sequences that move between them (an all-masked first batch included: it picks a representation
+    but numbers no group), every batch must give the oracle's first-seen ids and len(), and EmitTo::First must hand out the oracle's first
+    keys and renumber the rest from 0.  The profile tells which representation took each batch."""
+    import dfgpu
+    cols, steps = _representation_sequence(name)
+    dev = [ctx.from_arrow(c) if pa.types.is_dictionary(c.type) else None for c in cols]
+    gv = dfgpu.GroupValues(ctx, len(cols))
+    og = po.Groups([c.type for c in cols])
+    ctx.profile_select(None); ctx.profile_enable(True); ctx.profile_read()
+    try:
+        for step in steps:
+            if step[0] == "emit_first":
+                k = step[1]
+                want = og.emit()
+                got = gv.emit_first(k)
+                for a, w in zip(got, want):
+                    assert a.to_arrow().equals(w.slice(0, k))
+                og = po.Groups([c.type for c in cols])       # the rest, renumbered from 0 in their order
+                if len(want[0]) > k:
+                    og.intern([w.slice(k) for w in want])
+                assert len(gv) == len(og)
+                ctx.profile_read()
+                continue
+            lo, hi, m, path = step
+            batch = [c.slice(lo, hi - lo) if d is not None or c.slice(lo, hi - lo).null_count else pa.array(c.slice(lo, hi - lo).to_numpy()) for c, d in zip(cols, dev)]
+            dbatch = [d.slice(lo, hi - lo) if d is not None else ctx.from_arrow(b) for b, d in zip(batch, dev)]
+            got = gv.intern(dbatch, mask=ctx.from_arrow(pa.array(m)) if m is not None else None).to_numpy()
+            prof = ctx.profile_read()
+            if m is None:
+                assert np.array_equal(got.astype(np.int64), og.intern(batch)), f"{name}: rows {lo}:{hi}"
+            else:
+                want = og.intern([c.filter(pa.array(m)) for c in batch]) if m.any() else np.zeros(0, np.int64)
+                assert np.array_equal(got[m].astype(np.int64), want) and (got[~m] == 0xFFFFFFFF).all(), f"{name}: rows {lo}:{hi}"
+            assert len(gv) == len(og), f"{name}: rows {lo}:{hi}"
+            assert _groups_path(prof) == path, f"{name}: rows {lo}:{hi} took {_groups_path(prof)}"
+    finally:
+        ctx.profile_enable(False)
+    for a, w in zip(gv.emit(), og.emit()):
+        assert a.to_arrow().equals(w)
