@@ -241,7 +241,7 @@ __global__ void __launch_bounds__(BLOCK) k_probe_expand(const uint32_t* rows, co
 #pragma unroll
     for (int step = 0; step < 6; step++) { const int mid = (lo + hi + 1) >> 1; const uint64_t r = (uint64_t)__shfl((long long)rel, mid, 64); if (r <= k) lo = mid; else hi = mid - 1; }
     const uint64_t r0 = (uint64_t)__shfl((long long)rel, lo, 64); const uint32_t s0 = (uint32_t)__shfl((int)st, lo, 64), p0 = (uint32_t)__shfl((int)j, lo, 64);
-    if (k < total) { const uint32_t at = s0 + (uint32_t)(k - r0); out_build[base + k] = csr_rows ? csr_rows[at] : at; out_probe[base + k] = p0; }      // csr_rows == null: the run is contiguous (rank_runs)
+    if (k < total) { const uint32_t at = s0 + (uint32_t)(k - r0); out_build[base + k] = csr_rows ? csr_rows[at] : at; out_probe[base + k] = p0; }      // csr_rows == null: the run is contiguous (RANK_RUNS)
   }
 }
 // ---- membership bitmap of the build keys
@@ -308,7 +308,7 @@ __global__ void __launch_bounds__(BLOCK) k_key_run_heads(const T* keys, int64_t 
   uint64_t m = ballot64(h);
   if (lane_id() == 0 && (i >> 6) < ((n + 63) >> 6)) heads[i >> 6] = m;
 }
-// matched probe rows of a rank_runs build: rank of the key -> (run id, run length)
+// matched probe rows of a RANK_RUNS build: rank of the key -> (run id, run length)
 template <typename T>
 __global__ void __launch_bounds__(BLOCK) k_probe_lookup_runs(const T* pkeys, const uint32_t* rows, int64_t m, int64_t kmin, const uint64_t* bitmap, const uint32_t* prefix,
                                                              const uint32_t* run_starts, int64_t n_runs, int64_t n_build, uint32_t* out_run, uint32_t* out_cnt) {
@@ -436,6 +436,19 @@ __global__ void k_add_u32(uint32_t* v, int64_t n, uint32_t add) {
   if (i < n) v[i] += add;
 }
 
+// Key ranges through the device: the (min, max) word pairs d_scratch64[slot + 2 c], [slot + 2 c + 1] of ncols columns start at (INT64_MAX, INT64_MIN), launch(words) folds
+// the keys in, and the pairs come back in one read-back, counted as `sync` (null: not counted).  Returns them (lo > hi: no key), valid until the next read-back.
+template <typename F>
+static const long long* key_ranges(dfgpu_ctx* ctx, int slot, int ncols, const char* sync, F&& launch) {
+  std::vector<long long> init((size_t)2 * ncols); for (int c = 0; c < ncols; c++) { init[(size_t)2 * c] = INT64_MAX; init[(size_t)2 * c + 1] = INT64_MIN; }
+  HIP_CHECK(hipMemcpyAsync(ctx->d_scratch64 + slot, init.data(), init.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  launch((long long*)(ctx->d_scratch64 + slot));
+  KERNEL_CHECK();
+  if (sync) ctx->count_sync(sync);
+  fetch_to_pinned(ctx, slot, ctx->d_scratch64 + slot, init.size() * 8);
+  return (const long long*)(ctx->h_pinned + slot);
+}
+
 // ---- key packing
 struct PackCols { int32_t n; const void* v[MAX_KEYS]; const uint64_t* valid[MAX_KEYS]; int32_t type[MAX_KEYS]; int64_t mn[MAX_KEYS]; uint64_t range[MAX_KEYS], stride[MAX_KEYS]; };
 __global__ void __launch_bounds__(BLOCK) k_cols_minmax(PackCols pc, int64_t n, long long* out /* [2c] min, [2c+1] max */) {
@@ -479,6 +492,28 @@ static dfgpu_array* pack_key_array(dfgpu_ctx* ctx, const dfgpu_join_table* t, co
   h.get()->null_count = need_valid ? -1 : 0;
   return h.release();
 }
+// the build's packed key column, or null (t->pack_n = 0) when the key columns do not pack
+static dfgpu_array* pack_build_keys(dfgpu_ctx* ctx, dfgpu_join_table* t, const dfgpu_array* const* keys, int32_t nkeys) {
+  const int64_t n = keys[0]->length;
+  bool packable = ctx->join_key_packing && nkeys >= 2 && nkeys <= 4 && !t->null_equals_null && !ctx->force_hash_collisions && n > 0;
+  for (int c = 0; c < nkeys && packable; c++) packable = keys[c]->type != DFGPU_DICTIONARY && int_key_type(keys[c]->type) && keys[c]->length == n;
+  if (!packable) return nullptr;
+  t->pack_n = nkeys; for (int c = 0; c < nkeys; c++) t->pack_types[c] = logical_type(keys[c]);
+  const PackCols pc = pack_cols(t, keys);
+  const long long* mm = key_ranges(ctx, 16, nkeys, "sync:key_packing_ranges", [&](long long* w) {
+    hipLaunchKernelGGL(k_cols_minmax, dim3(grid_for(n, BLOCK * 8, ctx->num_cus * 4)), dim3(BLOCK), 0, ctx->stream, pc, n, w); });
+  unsigned __int128 prod = 1; bool nullable = false;
+  for (int c = nkeys - 1; c >= 0; c--) {
+    long long lo = mm[2 * c], hi = mm[2 * c + 1];
+    if (lo > hi) lo = hi = 0;                                                // a column of NULLs only: nothing can match
+    t->pack_min[c] = lo; t->pack_range[c] = (uint64_t)hi - (uint64_t)lo + 1; t->pack_stride[c] = (uint64_t)prod;
+    if (t->pack_range[c] == 0) { prod = (unsigned __int128)1 << 100; break; }
+    prod *= t->pack_range[c]; nullable = nullable || keys[c]->validity != nullptr;
+    if (prod > ((unsigned __int128)1 << 40)) break;
+  }
+  if (prod > ((unsigned __int128)1 << 40)) { t->pack_n = 0; return nullptr; }
+  return pack_key_array(ctx, t, keys, nullable);
+}
 
 static void check_key_types(const dfgpu_join_table* t, const dfgpu_array* const* pk, int32_t nkeys) {
   if (t->pack_n) {
@@ -492,8 +527,8 @@ static void check_key_types(const dfgpu_join_table* t, const dfgpu_array* const*
 }
 
 // The general table: open addressing over all key types (and the CSR of repeated keys), plus the membership bitmap when the
-// key is one integer column with a dense domain.
-static void build_hash_table(dfgpu_ctx* ctx, dfgpu_join_table* t, bool with_bitmap) {
+// key is one integer column with a dense domain.  with_bitmap = false: a probe's fallback table (the fields it writes are mutable).
+static void build_hash_table(dfgpu_ctx* ctx, const dfgpu_join_table* t, bool with_bitmap) {
   int64_t n = t->n_build; const bool null_equals_null = t->null_equals_null;
   uint64_t cap = 64; int bits = 6; while (cap < (uint64_t)n * 2) { cap <<= 1; bits++; }
   if (cap > (1ull << 31)) fail(DFGPU_RESOURCES_EXHAUSTED, "build side of %lld rows exceeds the 2^30-row hash table limit", (long long)n);
@@ -510,14 +545,10 @@ static void build_hash_table(dfgpu_ctx* ctx, dfgpu_join_table* t, bool with_bitm
   const dfgpu_array* key0 = t->keys[0];
   if (with_bitmap && n && t->nkeys == 1 && !null_equals_null && key0->type != DFGPU_DICTIONARY && int_key_type(key0->type)) {
     KernelTimer kt_(ctx, "join_build_bitmap");
-    long long init[2] = { INT64_MAX, INT64_MIN };
-    HIP_CHECK(hipMemcpyAsync(ctx->d_scratch64 + 4, init, 16, hipMemcpyHostToDevice, ctx->stream));
     const void* kv = key0->values->ptr; const uint32_t* rs = (const uint32_t*)row_slot->ptr;
-    DFGPU_INT_KEY_DISPATCH(key0->type, hipLaunchKernelGGL((k_key_minmax<T>), dim3(grid_for(n, BLOCK * 8, ctx->num_cus * 2)), dim3(BLOCK), 0, ctx->stream, (const T*)kv, rs, n,
-                                                          (long long*)(ctx->d_scratch64 + 4), (long long*)(ctx->d_scratch64 + 5)));
-    KERNEL_CHECK();
-    fetch_to_pinned(ctx, 4, ctx->d_scratch64 + 4, 16);
-    long long lo = (long long)ctx->h_pinned[4], hi = (long long)ctx->h_pinned[5];
+    const long long* mm = key_ranges(ctx, 4, 1, nullptr, [&](long long* w) {
+      DFGPU_INT_KEY_DISPATCH(key0->type, hipLaunchKernelGGL((k_key_minmax<T>), dim3(grid_for(n, BLOCK * 8, ctx->num_cus * 2)), dim3(BLOCK), 0, ctx->stream, (const T*)kv, rs, n, w, w + 1)); });
+    const long long lo = mm[0], hi = mm[1];
     if (lo <= hi) {
       uint64_t range = (uint64_t)hi - (uint64_t)lo + 1;
       if (range != 0 && range <= (1ull << 32) && range <= (uint64_t)n * 4096 + 65536) {      // <= 512 MB and not absurdly sparse
@@ -525,8 +556,8 @@ static void build_hash_table(dfgpu_ctx* ctx, dfgpu_join_table* t, bool with_bitm
         DFGPU_INT_KEY_DISPATCH(key0->type, hipLaunchKernelGGL((k_key_setbits<T>), dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const T*)kv, rs, n, (int64_t)lo, (uint64_t*)t->bitmap->ptr));
         KERNEL_CHECK();
         t->mem += (int64_t)bitmap_bytes((int64_t)range);
-      } else if (range != 0 && range <= (1ull << 32)) {     // too sparse to pay for up front; a probe batch large enough to amortise it builds it (join_probe)
-        t->lazy_bitmap = true; t->key_min = lo; t->range = range;
+      } else if (range != 0 && range <= (1ull << 32)) {     // too sparse to pay for up front; a probe batch large enough to amortise it builds it (match_bits_by_bitmap)
+        t->key_min = lo; t->range = range;
         t->lazy_row_slot = alloc_buffer(ctx, (size_t)(n + 1) * 4);
         HIP_CHECK(hipMemcpyAsync(t->lazy_row_slot->ptr, row_slot->ptr, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
       }
@@ -583,7 +614,7 @@ static bool build_rank_index(dfgpu_ctx* ctx, dfgpu_join_table* t) {
   const uint64_t* mk = t->build_mask ? (const uint64_t*)t->build_mask->ptr : nullptr;
   int64_t nw = (int64_t)((range + 63) / 64);
   t->key_min = lo; t->range = range;
-  t->rank_mode = true; t->unique = !runs; t->rank_runs = runs; t->rank_identity = !runs && range == (uint64_t)n;
+  t->rep = runs ? JoinRep::RANK_RUNS : JoinRep::RANK; t->unique = !runs; t->rank_identity = !runs && range == (uint64_t)n;
   BufferPtr heads;
   if (runs) {             // one bit per run head: it is the selection for the key bitmap, and its indices are the run starts
     heads = alloc_buffer(ctx, bitmap_bytes(n));
@@ -617,8 +648,8 @@ static bool build_rank_index(dfgpu_ctx* ctx, dfgpu_join_table* t) {
   return true;
 }
 
-// The partitioned join (pjoin.hip) is for key domains the membership bitmap cannot prefilter: min / max of the selected build keys in one
-// streaming pass.  true = range beyond 256 x rows (or beyond 2^32): a bitmap over it would be mostly empty lines.
+// min / max of the selected, non-NULL build keys in one streaming pass (selected_key_range: the domain of the rank index over unsorted keys, and
+// the partitioned join's test for a domain too sparse for the membership bitmap)
 template <typename T>
 __global__ void __launch_bounds__(BLOCK) k_key_minmax_masked(const T* keys, const uint64_t* valid, const uint64_t* mask, int64_t n, long long* mn, long long* mx, const uint32_t* rows = nullptr, const unsigned long long* d_count = nullptr) {
   long long lo = INT64_MAX, hi = INT64_MIN;
@@ -675,25 +706,21 @@ static bool build_rank_index_unsorted(dfgpu_ctx* ctx, dfgpu_join_table* t) {
   ArrayHolder list; const uint32_t* rl = nullptr; const unsigned long long* dcount = (const unsigned long long*)(ctx->d_scratch64 + 15);
   if (mk) { list.a = mask_to_indices_uncounted(ctx, mk, n, ctx->d_scratch64 + 15); rl = (const uint32_t*)list.get()->values->ptr; }
   const int lgrid = grid_for(n, BLOCK, ctx->num_cus * 16);
-  long long init[2] = { INT64_MAX, INT64_MIN };
-  HIP_CHECK(hipMemcpyAsync(ctx->d_scratch64 + 4, init, 16, hipMemcpyHostToDevice, ctx->stream));
   // masked: the selected keys are gathered ONCE (with their min / max) into a compact column; setting the bits and ranking the rows then read it in order instead of
   // gathering the same scattered 8 bytes two more times (three random passes over 15 M of 150 M orders cost 0.8 ms, one costs 0.27)
   BufferPtr ck; const void* ckp = nullptr;
+  long long lo, hi;
   if (rl) {
     ck = alloc_buffer(ctx, (size_t)n * type_width(key0->type) + 16); ckp = ck->ptr;
-    DFGPU_INT_KEY_DISPATCH(key0->type, hipLaunchKernelGGL((k_key_gather_minmax<T>), dim3(grid_for(n, BLOCK * 4, ctx->num_cus * 4)), dim3(BLOCK), 0, ctx->stream, (const T*)key0->values->ptr, rl, dcount, (T*)ck->ptr,
-                                                          (long long*)(ctx->d_scratch64 + 4), (long long*)(ctx->d_scratch64 + 5)));
-  } else
-  DFGPU_INT_KEY_DISPATCH(key0->type, hipLaunchKernelGGL((k_key_minmax_masked<T>), dim3(grid_for(n, BLOCK * 8, ctx->num_cus * 4)), dim3(BLOCK), 0, ctx->stream, (const T*)key0->values->ptr,
-                                                        (const uint64_t*)nullptr, mk, n, (long long*)(ctx->d_scratch64 + 4), (long long*)(ctx->d_scratch64 + 5), rl, dcount));
-  KERNEL_CHECK();
-  ctx->count_sync("sync:rank_index_range"); fetch_to_pinned(ctx, 4, ctx->d_scratch64 + 4, 16);
-  const long long lo = (long long)ctx->h_pinned[4], hi = (long long)ctx->h_pinned[5];
+    const long long* mm = key_ranges(ctx, 4, 1, "sync:rank_index_range", [&](long long* w) {
+      DFGPU_INT_KEY_DISPATCH(key0->type, hipLaunchKernelGGL((k_key_gather_minmax<T>), dim3(grid_for(n, BLOCK * 4, ctx->num_cus * 4)), dim3(BLOCK), 0, ctx->stream, (const T*)key0->values->ptr, rl, dcount, (T*)ck->ptr,
+                                                            w, w + 1)); });
+    lo = mm[0]; hi = mm[1];
+  } else selected_key_range(ctx, t, "sync:rank_index_range", &lo, &hi);      // no selection, no NULLs: every key
   t->have_minmax = true; t->sel_min = lo; t->sel_max = hi;
   if (lo > hi) return false;                               // no selected row
   const uint64_t range = (uint64_t)hi - (uint64_t)lo + 1;
-  if (range == 0 || range > (1ull << 32) || range > (uint64_t)n * 256 + 65536) return false;       // sparser domains are the partitioned join's (pj_domain_is_sparse draws the same line)
+  if (range == 0 || range > (1ull << 32) || range > (uint64_t)n * 256 + 65536) return false;       // sparser domains are the partitioned join's (pj_domain_is_sparse, pjoin.hip, draws the same line)
   const int64_t nw = (int64_t)((range + 63) / 64);
   BufferPtr bitmap = alloc_buffer(ctx, bitmap_bytes((int64_t)range));
   HIP_CHECK(hipMemsetAsync(bitmap->ptr, 0, bitmap_bytes((int64_t)range), ctx->stream));
@@ -712,33 +739,133 @@ static bool build_rank_index_unsorted(dfgpu_ctx* ctx, dfgpu_join_table* t) {
   DFGPU_INT_KEY_DISPATCH(key0->type, hipLaunchKernelGGL((k_rank_rows<T>), dim3(lgrid), dim3(BLOCK), 0, ctx->stream, (const T*)key0->values->ptr, mk, rl, dcount, n, (int64_t)lo, (const uint64_t*)bitmap->ptr,
                                                         (const uint32_t*)prefix->ptr, (uint32_t*)rows.get()->values->ptr, (const T*)ckp));
   KERNEL_CHECK();
-  t->key_min = lo; t->range = range; t->rank_mode = true; t->unique = true; t->rank_runs = false; t->rank_identity = false;
+  t->key_min = lo; t->range = range; t->rep = JoinRep::RANK; t->unique = true; t->rank_identity = false;
   t->bitmap = bitmap; t->rank_prefix = prefix; t->sel_rows = rows.release();
   t->mem += (int64_t)bitmap_bytes((int64_t)range) + nw * 4 + nsel * 4;
   return true;
 }
-static bool pj_domain_is_sparse(dfgpu_ctx* ctx, dfgpu_join_table* t) {
-  int64_t n = t->n_build;
-  if (!ctx->join_partitioned || ctx->force_hash_collisions || t->nkeys != 1 || t->null_equals_null || n < ctx->join_partitioned_min_build) return false;
-  const dfgpu_array* key0 = t->keys[0];
-  if (key0->type == DFGPU_UINT64) return true;
-  if (key0->type == DFGPU_DICTIONARY || !int_key_type(key0->type)) return false;
-  if (t->have_minmax && !key0->validity) {                 // build_rank_index_unsorted has been here (it takes columns without NULLs only)
-    if (t->sel_min > t->sel_max) return false;
-    const uint64_t range = (uint64_t)t->sel_max - (uint64_t)t->sel_min + 1;
-    return range == 0 || range > (1ull << 32) || range > (uint64_t)n * 256;
-  }
-  long long init[2] = { INT64_MAX, INT64_MIN };
-  HIP_CHECK(hipMemcpyAsync(ctx->d_scratch64 + 4, init, 16, hipMemcpyHostToDevice, ctx->stream));
-  DFGPU_INT_KEY_DISPATCH(key0->type, hipLaunchKernelGGL((k_key_minmax_masked<T>), dim3(grid_for(n, BLOCK * 8, ctx->num_cus * 4)), dim3(BLOCK), 0, ctx->stream, (const T*)key0->values->ptr,
-                                                        key0->validity ? (const uint64_t*)key0->validity->ptr : nullptr, t->build_mask ? (const uint64_t*)t->build_mask->ptr : nullptr, n,
-                                                        (long long*)(ctx->d_scratch64 + 4), (long long*)(ctx->d_scratch64 + 5)));
+void selected_key_range(dfgpu_ctx* ctx, const dfgpu_join_table* t, const char* sync, long long* lo, long long* hi) {
+  const dfgpu_array* key0 = t->keys[0]; const int64_t n = t->n_build;
+  const long long* mm = key_ranges(ctx, 4, 1, sync, [&](long long* w) {
+    DFGPU_INT_KEY_DISPATCH(key0->type, hipLaunchKernelGGL((k_key_minmax_masked<T>), dim3(grid_for(n, BLOCK * 8, ctx->num_cus * 4)), dim3(BLOCK), 0, ctx->stream, (const T*)key0->values->ptr,
+                                                          key0->validity ? (const uint64_t*)key0->validity->ptr : nullptr, t->build_mask ? (const uint64_t*)t->build_mask->ptr : nullptr, n, w, w + 1)); });
+  *lo = mm[0]; *hi = mm[1];
+}
+
+// ---- probe
+// A unique rank index that one integer probe column of the build's type, without NULLs, can be looked up in (a packed table's keys are packed tuples): the tables
+// whose probe may leave the build rows for later (dfgpu_join_probe_deferred, dfgpu_join_lookup) or answer as a selection (dfgpu_join_probe_selection)
+static bool rank_lookup_ok(const dfgpu_join_table* t, const dfgpu_array* const* probe_keys, int32_t nkeys) {
+  return t->rep == JoinRep::RANK && !t->pack_n && nkeys == 1 && probe_keys[0]->type == t->keys[0]->type && !probe_keys[0]->validity;
+}
+// build rows of m matched probe rows of a rank index: rows[0..m) (all = they are 0 .. m-1, not read); rows_valid = NULL entries of a lookup's row list
+static void lookup_rank(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* pk, const uint32_t* rows, const uint64_t* rows_valid, int64_t m, bool all, uint64_t* out_build) {
+  if (!m) return;
+  KernelTimer kt_(ctx, "k_probe_lookup_rank");
+  const bool sel = t->sel_rows != nullptr;
+#define LR(ALL, SEL) DFGPU_INT_KEY_DISPATCH(pk->type, hipLaunchKernelGGL((k_probe_lookup_rank<T, ALL, SEL>), dim3(grid_for(m, BLOCK * LR_ROWS)), dim3(BLOCK), 0, ctx->stream, (const T*)pk->values->ptr, rows, m, t->key_min, \
+                                                          (const uint64_t*)t->bitmap->ptr, t->rank_prefix ? (const uint32_t*)t->rank_prefix->ptr : nullptr, \
+                                                          sel ? (const uint32_t*)t->sel_rows->values->ptr : nullptr, t->rank_identity ? 1 : 0, out_build, rows_valid, pk->length))
+  if (all && sel) { LR(true, true); } else if (all) { LR(true, false); } else if (sel) { LR(false, true); } else { LR(false, false); }
+#undef LR
   KERNEL_CHECK();
-  ctx->count_sync("sync:pj_key_range"); fetch_to_pinned(ctx, 4, ctx->d_scratch64 + 4, 16);
-  long long lo = (long long)ctx->h_pinned[4], hi = (long long)ctx->h_pinned[5];
-  if (lo > hi) return false;
-  uint64_t range = (uint64_t)hi - (uint64_t)lo + 1;
-  return range == 0 || range > (1ull << 32) || range > (uint64_t)n * 256;
+}
+// pass 1 (one match bit per probe row) by the membership bitmap; a lazy one is built here by the first probe batch large enough to pay for it.
+// false = no bitmap this probe column can use: nothing launched.
+static bool match_bits_by_bitmap(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* pk, int64_t n, const uint64_t* mk, uint64_t* match_bits) {
+  const dfgpu_array* key0 = t->keys[0];
+  if (pk->type != key0->type) return false;      // same physical integer type, no dictionary
+  if (t->lazy_row_slot && t->range <= (uint64_t)n * 16) {
+    KernelTimer kt_(ctx, "join_build_bitmap");
+    t->bitmap = alloc_buffer(ctx, bitmap_bytes((int64_t)t->range), true); t->mem += (int64_t)bitmap_bytes((int64_t)t->range);
+    DFGPU_INT_KEY_DISPATCH(key0->type, hipLaunchKernelGGL((k_key_setbits<T>), dim3(grid_for(t->n_build, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const T*)key0->values->ptr,
+                                                          (const uint32_t*)t->lazy_row_slot->ptr, t->n_build, t->key_min, (uint64_t*)t->bitmap->ptr));
+    KERNEL_CHECK();
+    t->lazy_row_slot.reset();
+  }
+  if (!t->bitmap) return false;
+  KernelTimer kt_(ctx, "k_probe_match_bitmap");
+  int64_t rows_per_block = (int64_t)BLOCK * PM_ROWS;
+  const uint64_t* kvp = pk->validity ? (const uint64_t*)pk->validity->ptr : nullptr;
+  // the kernel reads two keys per load (2 x sizeof(T) aligned): a zero-copy slice at an odd row offset (dfgpu_array_slice) is copied once
+  const void* kptr = pk->values->ptr; BufferPtr aligned_keys; const size_t kw = (size_t)type_width(pk->type);
+  if ((uintptr_t)kptr % (2 * kw)) { aligned_keys = alloc_buffer(ctx, (size_t)n * kw); HIP_CHECK(hipMemcpyAsync(aligned_keys->ptr, kptr, (size_t)n * kw, hipMemcpyDeviceToDevice, ctx->stream)); kptr = aligned_keys->ptr; }
+#define PM_LAUNCH(HM, HV) DFGPU_INT_KEY_DISPATCH(pk->type, hipLaunchKernelGGL((k_probe_match_bitmap<T, HM, HV>), dim3(grid_for(n, (int)rows_per_block)), dim3(BLOCK), 0, ctx->stream, (const T*)kptr, \
+                                                          kvp, mk, n, t->key_min, t->range, (const uint64_t*)t->bitmap->ptr, match_bits))
+  if (mk && kvp) { PM_LAUNCH(true, true); } else if (mk) { PM_LAUNCH(true, false); } else if (kvp) { PM_LAUNCH(false, true); } else { PM_LAUNCH(false, false); }
+#undef PM_LAUNCH
+  return true;
+}
+// pass 1 by the hash table, built here first when the table's representation cannot serve this probe.  Returns the slot of every match when the kernel for
+// plain 8-byte integer keys ran (pass 2 gathers through it instead of probing again), else null.
+static BufferPtr match_bits_by_hash(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* const* probe_keys, int32_t nkeys, const KeySet& pks, int64_t n, const uint64_t* mk, uint64_t* match_bits) {
+  if (!t->slots) build_hash_table(ctx, t, false);
+  KernelTimer kt_(ctx, "k_probe_match_hash");
+  auto plain8 = [](const dfgpu_array* a) { return (a->type == DFGPU_INT64 || a->type == DFGPU_UINT64) && !a->validity; };
+  bool fast_hash = (nkeys == 1 || nkeys == 2) && !t->null_equals_null && !ctx->force_hash_collisions && t->n_build > 0;
+  for (int c = 0; c < nkeys && fast_hash; c++) fast_hash = plain8(probe_keys[c]) && plain8(t->keys[(size_t)c]);
+  BufferPtr found_slot;
+  if (fast_hash) {
+    found_slot = alloc_buffer(ctx, (size_t)n * 4);
+    const uint64_t *b0 = (const uint64_t*)t->keys[0]->values->ptr, *b1 = nkeys == 2 ? (const uint64_t*)t->keys[1]->values->ptr : nullptr;
+    const uint64_t *p0 = (const uint64_t*)probe_keys[0]->values->ptr, *p1 = nkeys == 2 ? (const uint64_t*)probe_keys[1]->values->ptr : nullptr;
+    dim3 hgrid(grid_for(n, BLOCK * HP_ROWS));
+#define HP(NK, HM) hipLaunchKernelGGL((k_probe_hash_i64<NK, HM>), hgrid, dim3(BLOCK), 0, ctx->stream, b0, b1, p0, p1, n, mk, (const uint64_t*)t->slots->ptr, t->capacity - 1, match_bits, (uint32_t*)found_slot->ptr)
+    if (nkeys == 1) { if (mk) HP(1, true); else HP(1, false); } else { if (mk) HP(2, true); else HP(2, false); }
+#undef HP
+  } else
+  hipLaunchKernelGGL(k_probe_match_hash, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, t->ks, pks, n, mk, t->null_equals_null ? 1 : 0, ctx->force_hash_collisions ? 1 : 0,
+                     (const uint64_t*)t->slots->ptr, t->capacity - 1, match_bits);
+  return found_slot;
+}
+// pass 2 of a rank index: the build row of every matched probe row, or (defer) none -- the caller asks dfgpu_join_lookup for the rows it still holds then
+static void rank_pairs(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* pk, ArrayHolder& rows, int64_t n, bool defer, ArrayHolder& ob, ArrayHolder& op) {
+  if (!defer) {
+    const int64_t m = rows.get()->length;
+    ob.a = new_fixed(ctx, DFGPU_UINT64, m);
+    lookup_rank(ctx, t, pk, (const uint32_t*)rows.get()->values->ptr, nullptr, m, rows.get()->identity && m == n, (uint64_t*)ob.get()->values->ptr);
+  }
+  op.a = rows.release();
+}
+// pass 2 of a rank index with runs (sorted build key with repeats): every match emits its contiguous run
+static void rank_runs_pairs(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* pk, const dfgpu_array* rows, ArrayHolder& ob, ArrayHolder& op) {
+  const int64_t m = rows->length; const uint32_t* rp = (const uint32_t*)rows->values->ptr;
+  BufferPtr run_of = alloc_buffer(ctx, (size_t)(m + 1) * 4);
+  expand_matches(ctx, m, ob, op, [&](uint32_t* cnt) {
+    KernelTimer kt_(ctx, "k_probe_lookup_rank");
+    DFGPU_INT_KEY_DISPATCH(pk->type, hipLaunchKernelGGL((k_probe_lookup_runs<T>), dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const T*)pk->values->ptr, rp, m, t->key_min,
+                                                        (const uint64_t*)t->bitmap->ptr, (const uint32_t*)t->rank_prefix->ptr, (const uint32_t*)t->sel_rows->values->ptr, t->sel_rows->length, t->n_build,
+                                                        (uint32_t*)run_of->ptr, cnt));
+  }, [&](const uint32_t* cnt, const uint64_t* offs, uint64_t* obp, uint32_t* opp) {
+    KernelTimer kt_(ctx, "k_probe_expand");
+    hipLaunchKernelGGL(k_probe_expand, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, rp, (const uint32_t*)run_of->ptr, cnt, offs, m, (const uint32_t*)t->sel_rows->values->ptr, (const uint32_t*)nullptr, obp, opp);
+  });
+}
+// pass 2 of the hash table: unique keys give the build row of every match, repeated keys emit their key group (CSR).  found_slot: from match_bits_by_hash.
+static void hash_pairs(dfgpu_ctx* ctx, const dfgpu_join_table* t, const KeySet& pks, ArrayHolder& rows, const BufferPtr& found_slot, ArrayHolder& ob, ArrayHolder& op) {
+  const int64_t m = rows.get()->length; const uint32_t* rp = (const uint32_t*)rows.get()->values->ptr;
+  // unique: out_build[i] = build row; repeated: slot_of[i] / cnt[i] = the slot of the key group and its size
+  auto lookup = [&](uint64_t* out_build, uint32_t* slot_of, uint32_t* cnt) {
+    KernelTimer kt_(ctx, "k_probe_lookup");
+    const uint32_t* sc = t->unique ? nullptr : (const uint32_t*)t->slot_count->ptr;
+    if (found_slot) hipLaunchKernelGGL(k_probe_found, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, rp, m, (const uint32_t*)found_slot->ptr, (const uint64_t*)t->slots->ptr, sc, t->unique ? 1 : 0,
+                                       out_build, slot_of, cnt);
+    else
+    hipLaunchKernelGGL(k_probe_lookup, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, t->ks, pks, rp, m, t->null_equals_null ? 1 : 0, ctx->force_hash_collisions ? 1 : 0, (const uint64_t*)t->slots->ptr, sc,
+                       t->capacity - 1, t->unique ? 1 : 0, out_build, slot_of, cnt, ctx->d_flags);
+  };
+  if (t->unique) {
+    ob.a = new_fixed(ctx, DFGPU_UINT64, m);
+    if (m) lookup((uint64_t*)ob.get()->values->ptr, nullptr, nullptr);
+    KERNEL_CHECK();
+    op.a = rows.release();
+    return;
+  }
+  BufferPtr slot_of = alloc_buffer(ctx, (size_t)(m + 1) * 4);
+  expand_matches(ctx, m, ob, op, [&](uint32_t* cnt) { lookup(nullptr, (uint32_t*)slot_of->ptr, cnt); }, [&](const uint32_t* cnt, const uint64_t* offs, uint64_t* obp, uint32_t* opp) {
+    KernelTimer kt_(ctx, "k_probe_expand");
+    hipLaunchKernelGGL(k_probe_expand, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, rp, (const uint32_t*)slot_of->ptr, cnt, offs, m, (const uint32_t*)t->slot_start->ptr, (const uint32_t*)t->csr_rows->ptr, obp, opp);
+  });
 }
 
 }  // namespace dfgpu
@@ -760,43 +887,14 @@ dfgpu_status dfgpu_join_build(dfgpu_ctx* ctx, const dfgpu_array* const* keys, in
     std::unique_ptr<dfgpu_join_table> t(new dfgpu_join_table());
     t->ctx = ctx; t->nkeys = nkeys; t->null_equals_null = null_equals_null != 0;
     int64_t n = keys[0]->length; t->n_build = n;
-    ArrayHolder packed;
-    bool packable = ctx->join_key_packing && nkeys >= 2 && nkeys <= 4 && !null_equals_null && !ctx->force_hash_collisions && n > 0;
-    for (int c = 0; c < nkeys && packable; c++) packable = keys[c]->type != DFGPU_DICTIONARY && int_key_type(keys[c]->type) && keys[c]->length == n;
-    if (packable) {
-      t->pack_n = nkeys; for (int c = 0; c < nkeys; c++) t->pack_types[c] = logical_type(keys[c]);
-      std::vector<long long> init((size_t)2 * nkeys); for (int c = 0; c < nkeys; c++) { init[(size_t)2 * c] = INT64_MAX; init[(size_t)2 * c + 1] = INT64_MIN; }
-      HIP_CHECK(hipMemcpyAsync(ctx->d_scratch64 + 16, init.data(), init.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-      PackCols pc = pack_cols(t.get(), keys);
-      hipLaunchKernelGGL(k_cols_minmax, dim3(grid_for(n, BLOCK * 8, ctx->num_cus * 4)), dim3(BLOCK), 0, ctx->stream, pc, n, (long long*)(ctx->d_scratch64 + 16));
-      KERNEL_CHECK();
-      ctx->count_sync("sync:key_packing_ranges"); fetch_to_pinned(ctx, 16, ctx->d_scratch64 + 16, init.size() * 8);
-      unsigned __int128 prod = 1; bool any_valid = true, nullable = false;
-      for (int c = nkeys - 1; c >= 0; c--) {
-        long long lo = (long long)ctx->h_pinned[16 + 2 * c], hi = (long long)ctx->h_pinned[16 + 2 * c + 1];
-        if (lo > hi) { any_valid = false; lo = hi = 0; }                       // a column of NULLs only: nothing can match
-        t->pack_min[c] = lo; t->pack_range[c] = (uint64_t)hi - (uint64_t)lo + 1; t->pack_stride[c] = (uint64_t)prod;
-        if (t->pack_range[c] == 0) { prod = (unsigned __int128)1 << 100; break; }
-        prod *= t->pack_range[c]; nullable = nullable || keys[c]->validity != nullptr;
-        if (prod > ((unsigned __int128)1 << 40)) break;
-      }
-      if (prod <= ((unsigned __int128)1 << 40)) {
-        (void)any_valid;
-        packed.a = pack_key_array(ctx, t.get(), keys, nullable);
-        const dfgpu_array* pk1 = packed.get(); keys = &pk1; nkeys = 1; t->nkeys = 1;
-        t->ks = make_keyset(keys, 1);
-        t->keys.push_back(packed.release());                                   // the table owns the packed column
-      } else t->pack_n = 0;
-    }
-    if (!t->pack_n) {
-      t->ks = make_keyset(keys, nkeys);
-      for (int c = 0; c < nkeys; c++) { t->keys.push_back(const_cast<dfgpu_array*>(keys[c])); dfgpu_array_retain(t->keys.back()); }
-    }
+    if (dfgpu_array* packed = pack_build_keys(ctx, t.get(), keys, nkeys)) { t->nkeys = 1; t->keys.push_back(packed); }      // the table owns the packed column
+    else for (int c = 0; c < nkeys; c++) { t->keys.push_back(const_cast<dfgpu_array*>(keys[c])); dfgpu_array_retain(t->keys.back()); }
+    t->ks = make_keyset(t->keys.data(), t->nkeys);
     t->build_mask = effective_mask(ctx, opt_mask, n);
     t->mem = (int64_t)bitmap_bytes(n);               // the visited bitmap: accounted here, allocated and cleared when a join type that marks rows first does (an Inner join never)
-    // order of preference: rank index (clustered keys: no table at all), radix-partitioned LDS tables (large builds on unsorted keys
-    // whose domain is too sparse for the membership bitmap in front of the general table), general open-addressing table
-    if (!build_rank_index(ctx, t.get()) && !build_rank_index_unsorted(ctx, t.get()) && !((pj_domain_is_sparse(ctx, t.get()) || pj_hashed_candidate(ctx, t.get())) && pj_build(ctx, t.get()))) build_hash_table(ctx, t.get(), true);
+    // order of preference: rank index (clustered keys: no table at all), rank index over unsorted unique keys, radix-partitioned LDS tables (large builds
+    // whose keys the membership bitmap cannot prefilter, pj_build), general open-addressing table
+    if (!build_rank_index(ctx, t.get()) && !build_rank_index_unsorted(ctx, t.get()) && !pj_build(ctx, t.get())) build_hash_table(ctx, t.get(), true);
     *out = t.release();
   });
 }
@@ -822,7 +920,7 @@ dfgpu_status dfgpu_join_probe_selection(dfgpu_ctx* ctx, const dfgpu_join_table* 
 dfgpu_status dfgpu_join_lookup(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* const* probe_keys, int32_t nkeys, const dfgpu_array* rows, dfgpu_array** out_build_idx) {
   return guard(ctx, [&] {
     if (!t || !probe_keys || !out_build_idx) fail(DFGPU_INVALID_ARGUMENT, "join_lookup: null argument");
-    if (!(t->rank_mode && t->unique && !t->rank_runs && t->bitmap) || nkeys != 1 || probe_keys[0]->type != t->keys[0]->type || probe_keys[0]->validity)
+    if (!rank_lookup_ok(t, probe_keys, nkeys))
       fail(DFGPU_INVALID_ARGUMENT, "join_lookup: only after dfgpu_join_probe_deferred left the build indices out (a unique rank-indexed build, one integer key column without NULLs)");
     if (rows && rows->type != DFGPU_UINT32) fail(DFGPU_INVALID_ARGUMENT, "join_lookup: rows must be UInt32");
     const dfgpu_array* pk = probe_keys[0];
@@ -830,27 +928,21 @@ dfgpu_status dfgpu_join_lookup(dfgpu_ctx* ctx, const dfgpu_join_table* t, const 
     ArrayHolder ob(new_fixed(ctx, DFGPU_UINT64, m));
     // NULL entries of `rows` (the NULL side of an outer join's indices above a deferred join) stay NULL in the answer: take() through it then yields NULL rows
     const uint64_t* rv = rows && rows->validity ? (const uint64_t*)rows->validity->ptr : nullptr;
-    if (m) { KernelTimer kt_(ctx, "k_probe_lookup_rank");
-      const bool all = !rv && (rows == nullptr || (rows->identity && rows->length == pk->length)), sel = t->sel_rows != nullptr;
-      const uint32_t* rp = rows ? (const uint32_t*)rows->values->ptr : nullptr;
-#define LR(ALL, SEL) DFGPU_INT_KEY_DISPATCH(pk->type, hipLaunchKernelGGL((k_probe_lookup_rank<T, ALL, SEL>), dim3(grid_for(m, BLOCK * LR_ROWS)), dim3(BLOCK), 0, ctx->stream, (const T*)pk->values->ptr, rp, m, t->key_min, \
-                                                            (const uint64_t*)t->bitmap->ptr, t->rank_prefix ? (const uint32_t*)t->rank_prefix->ptr : nullptr, \
-                                                            t->sel_rows ? (const uint32_t*)t->sel_rows->values->ptr : nullptr, t->rank_identity ? 1 : 0, (uint64_t*)ob.get()->values->ptr, rv, pk->length))
-      if (all && sel) { LR(true, true); } else if (all) { LR(true, false); } else if (sel) { LR(false, true); } else { LR(false, false); }
-#undef LR
-      KERNEL_CHECK(); }
+    lookup_rank(ctx, t, pk, rows ? (const uint32_t*)rows->values->ptr : nullptr, rv, m, !rv && (rows == nullptr || (rows->identity && rows->length == pk->length)), (uint64_t*)ob.get()->values->ptr);
     if (rv) { ob.get()->validity = rows->validity; ob.get()->null_count = rows->null_count; }
     *out_build_idx = ob.release();
   });
 }
+// Check the arguments and pack the keys, go partition by partition if the table and batch are for it, else pass 1 (match bits, by bitmap or by hash), then the
+// selection form if it was asked for, or pass 2 (the pairs) by representation
 static dfgpu_status join_probe_impl(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* const* probe_keys, int32_t nkeys,
                                     const dfgpu_array* opt_mask, dfgpu_array** out_build_idx, dfgpu_array** out_probe_idx, bool may_defer, dfgpu_array** out_selection) {
   return guard(ctx, [&] {
     if (!t || !probe_keys || (!out_selection && (!out_build_idx || !out_probe_idx))) fail(DFGPU_INVALID_ARGUMENT, "join_probe: null argument");
     check_key_types(t, probe_keys, nkeys);
-    // the selection form (dfgpu_join_probe_selection): only for the tables whose probe would be deferred -- decided before any pass runs
-    if (out_selection && !(t->rank_mode && t->unique && !t->rank_runs && t->bitmap && !t->pack_n && nkeys == 1 && probe_keys[0]->type == t->keys[0]->type && !probe_keys[0]->validity))
-      fail(DFGPU_NOT_IMPLEMENTED, "join_probe_selection: only a unique rank-indexed build probed by one integer key column of the build's type without NULLs");
+    // the selection form (dfgpu_join_probe_selection) and the deferred probe: only for the tables dfgpu_join_lookup can look up in -- decided before any pass runs
+    const bool lookup_ok = rank_lookup_ok(t, probe_keys, nkeys);
+    if (out_selection && !lookup_ok) fail(DFGPU_NOT_IMPLEMENTED, "join_probe_selection: only a unique rank-indexed build probed by one integer key column of the build's type without NULLs");
     ArrayHolder packed_probe; const dfgpu_array* pk1 = nullptr;
     if (t->pack_n) {
       for (int c = 0; c < nkeys; c++) if (probe_keys[c]->type == DFGPU_DICTIONARY || probe_keys[c]->length != probe_keys[0]->length) fail(DFGPU_NOT_IMPLEMENTED, "probe of a packed multi-key table with dictionary-encoded keys");
@@ -860,138 +952,26 @@ static dfgpu_status join_probe_impl(dfgpu_ctx* ctx, const dfgpu_join_table* t, c
     KeySet pks = make_keyset(probe_keys, nkeys);
     int64_t n = probe_keys[0]->length;
     BufferPtr mask = effective_mask(ctx, opt_mask, n);
-    int64_t nw = (n + 63) / 64;
     const uint64_t* mk = mask ? (const uint64_t*)mask->ptr : nullptr;
-    int nen = t->null_equals_null ? 1 : 0, fz = ctx->force_hash_collisions ? 1 : 0;
     if (!out_selection && pj_probe_eligible(ctx, t, probe_keys, nkeys, n)) {        // large batch against a partitioned build: partition by partition out of LDS
       pj_probe(ctx, t, probe_keys, nkeys, mk, out_build_idx, out_probe_idx);
       check_flags(ctx, "join_probe");
       return;
     }
-    // pass 1: match bit per probe row
     BufferPtr match_bits = alloc_buffer(ctx, bitmap_bytes(n), n == 0);
-    bool use_bitmap = false, fast_hash = false; BufferPtr found_slot;
-    if (n) {
-      const dfgpu_array* pk = probe_keys[0];
-      if (!t->bitmap && t->lazy_bitmap && pk->type == t->keys[0]->type && t->range <= (uint64_t)n * 16) {
-        auto* mt = const_cast<dfgpu_join_table*>(t); const dfgpu_array* key0 = t->keys[0];
-        KernelTimer kt_(ctx, "join_build_bitmap");
-        mt->bitmap = alloc_buffer(ctx, bitmap_bytes((int64_t)t->range), true); mt->mem += (int64_t)bitmap_bytes((int64_t)t->range);
-        DFGPU_INT_KEY_DISPATCH(key0->type, hipLaunchKernelGGL((k_key_setbits<T>), dim3(grid_for(t->n_build, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const T*)key0->values->ptr,
-                                                              (const uint32_t*)t->lazy_row_slot->ptr, t->n_build, t->key_min, (uint64_t*)mt->bitmap->ptr));
-        KERNEL_CHECK();
-        mt->lazy_bitmap = false; mt->lazy_row_slot.reset();
-      }
-      use_bitmap = t->bitmap && pk->type == t->keys[0]->type;      // same physical integer type, no dictionary
-      if (!use_bitmap && !t->slots) build_hash_table(ctx, const_cast<dfgpu_join_table*>(t), false);   // rank index cannot serve this probe column
-      if (use_bitmap) {
-        KernelTimer kt_(ctx, "k_probe_match_bitmap");
-        int64_t rows_per_block = (int64_t)BLOCK * PM_ROWS;
-        const uint64_t* kvp = pk->validity ? (const uint64_t*)pk->validity->ptr : nullptr;
-        // the kernel reads two keys per load (2 x sizeof(T) aligned): a zero-copy slice at an odd row offset (dfgpu_array_slice) is copied once
-        const void* kptr = pk->values->ptr; BufferPtr aligned_keys; const size_t kw = (size_t)type_width(pk->type);
-        if ((uintptr_t)kptr % (2 * kw)) { aligned_keys = alloc_buffer(ctx, (size_t)n * kw); HIP_CHECK(hipMemcpyAsync(aligned_keys->ptr, kptr, (size_t)n * kw, hipMemcpyDeviceToDevice, ctx->stream)); kptr = aligned_keys->ptr; }
-#define PM_LAUNCH(HM, HV) DFGPU_INT_KEY_DISPATCH(pk->type, hipLaunchKernelGGL((k_probe_match_bitmap<T, HM, HV>), dim3(grid_for(n, (int)rows_per_block)), dim3(BLOCK), 0, ctx->stream, (const T*)kptr, \
-                                                            kvp, mk, n, t->key_min, t->range, (const uint64_t*)t->bitmap->ptr, (uint64_t*)match_bits->ptr))
-        if (mk && kvp) { PM_LAUNCH(true, true); } else if (mk) { PM_LAUNCH(true, false); } else if (kvp) { PM_LAUNCH(false, true); } else { PM_LAUNCH(false, false); }
-#undef PM_LAUNCH
-      } else {
-        KernelTimer kt_(ctx, "k_probe_match_hash");
-        auto plain8 = [](const dfgpu_array* a) { return (a->type == DFGPU_INT64 || a->type == DFGPU_UINT64) && !a->validity; };
-        fast_hash = (nkeys == 1 || nkeys == 2) && !nen && !fz && t->n_build > 0;
-        for (int c = 0; c < nkeys && fast_hash; c++) fast_hash = plain8(probe_keys[c]) && plain8(t->keys[(size_t)c]);
-        if (fast_hash) {
-          found_slot = alloc_buffer(ctx, (size_t)n * 4);
-          const uint64_t *b0 = (const uint64_t*)t->keys[0]->values->ptr, *b1 = nkeys == 2 ? (const uint64_t*)t->keys[1]->values->ptr : nullptr;
-          const uint64_t *p0 = (const uint64_t*)probe_keys[0]->values->ptr, *p1 = nkeys == 2 ? (const uint64_t*)probe_keys[1]->values->ptr : nullptr;
-          dim3 hgrid(grid_for(n, BLOCK * HP_ROWS));
-#define HP(NK, HM) hipLaunchKernelGGL((k_probe_hash_i64<NK, HM>), hgrid, dim3(BLOCK), 0, ctx->stream, b0, b1, p0, p1, n, mk, (const uint64_t*)t->slots->ptr, t->capacity - 1, (uint64_t*)match_bits->ptr, (uint32_t*)found_slot->ptr)
-          if (nkeys == 1) { if (mk) HP(1, true); else HP(1, false); } else { if (mk) HP(2, true); else HP(2, false); }
-#undef HP
-        } else
-        hipLaunchKernelGGL(k_probe_match_hash, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, t->ks, pks, n, mk, nen, fz, (const uint64_t*)t->slots->ptr, t->capacity - 1, (uint64_t*)match_bits->ptr);
-      }
-      KERNEL_CHECK();
-    }
-    (void)nw;
+    const bool use_bitmap = n && match_bits_by_bitmap(ctx, t, probe_keys[0], n, mk, (uint64_t*)match_bits->ptr);
+    const BufferPtr found_slot = n && !use_bitmap ? match_bits_by_hash(ctx, t, probe_keys, nkeys, pks, n, mk, (uint64_t*)match_bits->ptr) : nullptr;
+    KERNEL_CHECK();
     if (out_selection) {            // the match bits ARE the answer: a Boolean column over the probe rows (bits of a partial last word beyond n are zero)
       ArrayHolder sel(new_array(ctx, DFGPU_BOOL, n)); sel.get()->values = match_bits; sel.get()->null_count = 0;
       check_flags(ctx, "join_probe");
       *out_selection = sel.release();
       return;
     }
-    ArrayHolder rows(mask_to_indices_impl(ctx, (const uint64_t*)match_bits->ptr, n));      // matched probe rows, ascending
-    int64_t m = rows.get()->length;
-    const uint32_t* rp = (const uint32_t*)rows.get()->values->ptr;
-    ArrayHolder ob, op;
-    if (t->rank_mode && use_bitmap && t->rank_runs) {          // sorted build key with repeats: every match emits its contiguous run
-      const dfgpu_array* pk = probe_keys[0];
-      BufferPtr run_of = alloc_buffer(ctx, (size_t)(m + 1) * 4), cnt = alloc_buffer(ctx, (size_t)(m + 1) * 4), offs = alloc_buffer(ctx, (size_t)(m + 1) * 8);
-      int64_t total = 0;
-      if (m) {
-        { KernelTimer kt_(ctx, "k_probe_lookup_rank");
-          DFGPU_INT_KEY_DISPATCH(pk->type, hipLaunchKernelGGL((k_probe_lookup_runs<T>), dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const T*)pk->values->ptr, rp, m, t->key_min,
-                                                              (const uint64_t*)t->bitmap->ptr, (const uint32_t*)t->rank_prefix->ptr, (const uint32_t*)t->sel_rows->values->ptr, t->sel_rows->length, t->n_build,
-                                                              (uint32_t*)run_of->ptr, (uint32_t*)cnt->ptr)); }
-        KERNEL_CHECK();
-        exclusive_scan_u32(ctx, (const uint32_t*)cnt->ptr, (uint64_t*)offs->ptr, m, ctx->d_scratch64 + 8);
-        total = (int64_t)read_scratch(ctx, 8);
-      }
-      if (total > 0xFFFFFFF0ll) fail(DFGPU_RESOURCES_EXHAUSTED, "join output of %lld rows for one probe batch; split the probe batch", (long long)total);
-      ob.a = new_fixed(ctx, DFGPU_UINT64, total); op.a = new_fixed(ctx, DFGPU_UINT32, total);
-      if (total) { KernelTimer kt_(ctx, "k_probe_expand");
-        hipLaunchKernelGGL(k_probe_expand, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, rp, (const uint32_t*)run_of->ptr, (const uint32_t*)cnt->ptr, (const uint64_t*)offs->ptr, m,
-                           (const uint32_t*)t->sel_rows->values->ptr, (const uint32_t*)nullptr, (uint64_t*)ob.get()->values->ptr, (uint32_t*)op.get()->values->ptr); }
-      KERNEL_CHECK();
-    } else if (t->rank_mode && use_bitmap && may_defer && t->unique && !probe_keys[0]->validity) {
-      // the caller resolves build rows later, for the rows it still holds by then (dfgpu_join_lookup): only the matched probe rows leave
-      *out_build_idx = nullptr; *out_probe_idx = rows.release();
-      check_flags(ctx, "join_probe");
-      return;
-    } else if (t->rank_mode && use_bitmap) {
-      ob.a = new_fixed(ctx, DFGPU_UINT64, m);
-      const dfgpu_array* pk = probe_keys[0];
-      if (m) { KernelTimer kt_(ctx, "k_probe_lookup_rank");
-        const bool all = rows.get()->identity && m == n, sel = t->sel_rows != nullptr;
-#define LR(ALL, SEL) DFGPU_INT_KEY_DISPATCH(pk->type, hipLaunchKernelGGL((k_probe_lookup_rank<T, ALL, SEL>), dim3(grid_for(m, BLOCK * LR_ROWS)), dim3(BLOCK), 0, ctx->stream, (const T*)pk->values->ptr, rp, m, t->key_min, \
-                                                            (const uint64_t*)t->bitmap->ptr, t->rank_prefix ? (const uint32_t*)t->rank_prefix->ptr : nullptr, \
-                                                            t->sel_rows ? (const uint32_t*)t->sel_rows->values->ptr : nullptr, t->rank_identity ? 1 : 0, (uint64_t*)ob.get()->values->ptr))
-        if (all && sel) { LR(true, true); } else if (all) { LR(true, false); } else if (sel) { LR(false, true); } else { LR(false, false); }
-#undef LR
-      }
-      KERNEL_CHECK();
-      op.a = rows.release();
-    } else if (t->unique) {
-      ob.a = new_fixed(ctx, DFGPU_UINT64, m);
-      if (m) { KernelTimer kt_(ctx, "k_probe_lookup");
-        if (fast_hash) hipLaunchKernelGGL(k_probe_found, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, rp, m, (const uint32_t*)found_slot->ptr, (const uint64_t*)t->slots->ptr, (const uint32_t*)nullptr, 1,
-                                          (uint64_t*)ob.get()->values->ptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
-        else
-        hipLaunchKernelGGL(k_probe_lookup, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, t->ks, pks, rp, m, nen, fz, (const uint64_t*)t->slots->ptr, (const uint32_t*)nullptr,
-                           t->capacity - 1, 1, (uint64_t*)ob.get()->values->ptr, (uint32_t*)nullptr, (uint32_t*)nullptr, ctx->d_flags); }
-      KERNEL_CHECK();
-      op.a = rows.release();
-    } else {
-      BufferPtr slot_of = alloc_buffer(ctx, (size_t)(m + 1) * 4), cnt = alloc_buffer(ctx, (size_t)(m + 1) * 4), offs = alloc_buffer(ctx, (size_t)(m + 1) * 8);
-      int64_t total = 0;
-      if (m) {
-        { KernelTimer kt_(ctx, "k_probe_lookup");
-        if (fast_hash) hipLaunchKernelGGL(k_probe_found, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, rp, m, (const uint32_t*)found_slot->ptr, (const uint64_t*)t->slots->ptr, (const uint32_t*)t->slot_count->ptr, 0,
-                                          (uint64_t*)nullptr, (uint32_t*)slot_of->ptr, (uint32_t*)cnt->ptr);
-        else
-        hipLaunchKernelGGL(k_probe_lookup, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, t->ks, pks, rp, m, nen, fz, (const uint64_t*)t->slots->ptr, (const uint32_t*)t->slot_count->ptr,
-                           t->capacity - 1, 0, (uint64_t*)nullptr, (uint32_t*)slot_of->ptr, (uint32_t*)cnt->ptr, ctx->d_flags); }
-        KERNEL_CHECK();
-        exclusive_scan_u32(ctx, (const uint32_t*)cnt->ptr, (uint64_t*)offs->ptr, m, ctx->d_scratch64 + 8);
-        total = (int64_t)read_scratch(ctx, 8);
-      }
-      if (total > 0xFFFFFFF0ll) fail(DFGPU_RESOURCES_EXHAUSTED, "join output of %lld rows for one probe batch; split the probe batch", (long long)total);
-      ob.a = new_fixed(ctx, DFGPU_UINT64, total); op.a = new_fixed(ctx, DFGPU_UINT32, total);
-      if (total) { KernelTimer kt_(ctx, "k_probe_expand");
-        hipLaunchKernelGGL(k_probe_expand, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, rp, (const uint32_t*)slot_of->ptr, (const uint32_t*)cnt->ptr, (const uint64_t*)offs->ptr, m,
-                           (const uint32_t*)t->slot_start->ptr, (const uint32_t*)t->csr_rows->ptr, (uint64_t*)ob.get()->values->ptr, (uint32_t*)op.get()->values->ptr); }
-      KERNEL_CHECK();
-    }
+    ArrayHolder rows(mask_to_indices_impl(ctx, (const uint64_t*)match_bits->ptr, n)), ob, op;      // matched probe rows, ascending
+    if (use_bitmap && t->rep == JoinRep::RANK_RUNS) rank_runs_pairs(ctx, t, probe_keys[0], rows.get(), ob, op);
+    else if (use_bitmap && t->rep == JoinRep::RANK) rank_pairs(ctx, t, probe_keys[0], rows, n, may_defer && lookup_ok, ob, op);
+    else hash_pairs(ctx, t, pks, rows, found_slot, ob, op);
     check_flags(ctx, "join_probe");
     *out_build_idx = ob.release(); *out_probe_idx = op.release();
   });

@@ -543,18 +543,27 @@ __global__ void __launch_bounds__(BLOCK) k_pj_verify(KeySet bks, KeySet pks, con
 static PjOffsets pj_partition_keys(dfgpu_ctx* ctx, const KeySet& ks, int64_t n, const uint64_t* mask, bool null_eq, uint32_t P, RpRec12* recs, uint64_t* d_total, const char* th, const char* ts, const char* tw) {
   return pj_partition_t(ctx, PjHashKeys{ ks, mask, null_eq ? 1 : 0, ctx->join_partitioned_hash_mask }, n, P, recs, d_total, th, ts, tw);
 }
-bool pj_hashed_candidate(dfgpu_ctx* ctx, const dfgpu_join_table* t) {
-  if (!ctx->join_partitioned || !ctx->join_partitioned_hashed || ctx->force_hash_collisions || t->n_build < ctx->join_partitioned_min_build) return false;
-  return !(t->nkeys == 1 && !t->null_equals_null && pj_key_type_ok(t->keys[0]));      // those are the integer mode's (which asks pj_domain_is_sparse first)
+// The integer mode is for key domains the membership bitmap cannot prefilter: true = range of the selected build keys beyond 256 x rows (or beyond 2^32),
+// a bitmap over it would be mostly empty lines.  build_rank_index_unsorted draws the same line from the other side.
+static bool pj_domain_is_sparse(dfgpu_ctx* ctx, const dfgpu_join_table* t) {
+  const dfgpu_array* key0 = t->keys[0];
+  if (key0->type == DFGPU_UINT64) return true;
+  long long lo, hi;
+  if (t->have_minmax && !key0->validity) { lo = t->sel_min; hi = t->sel_max; }       // build_rank_index_unsorted has been here (it takes columns without NULLs only)
+  else selected_key_range(ctx, t, "sync:pj_key_range", &lo, &hi);
+  if (lo > hi) return false;
+  const uint64_t range = (uint64_t)hi - (uint64_t)lo + 1;
+  return range == 0 || range > (1ull << 32) || range > (uint64_t)t->n_build * 256;
 }
 
+// Takes large builds in one of two modes: integer (one integer key column, NULLs never match) over a sparse domain, or hashed (any other keys).
 bool pj_build(dfgpu_ctx* ctx, dfgpu_join_table* t) {
   const int64_t n = t->n_build;
-  if (!ctx->join_partitioned || ctx->force_hash_collisions) return false;
-  if (n < ctx->join_partitioned_min_build || n > 0xFFFFFFF0ll) return false;
+  if (!ctx->join_partitioned || ctx->force_hash_collisions || n < ctx->join_partitioned_min_build) return false;
   const dfgpu_array* key0 = t->keys[0];
   const bool hashed = !(t->nkeys == 1 && !t->null_equals_null && pj_key_type_ok(key0));
-  if (hashed && !ctx->join_partitioned_hashed) return false;
+  if (hashed ? !ctx->join_partitioned_hashed : !pj_domain_is_sparse(ctx, t)) return false;
+  if (n > 0xFFFFFFF0ll) return false;
   int64_t cap = ctx->join_partition_rows; if (cap < 16) cap = 16; if (cap > 14000) cap = 14000;
   const int64_t per = std::min<int64_t>(cap, 7300);      // <= 8192 keys: a 64 KB table at load <= 1/2, two workgroups per CU
   int64_t P64 = (n + per - 1) / per; if (P64 < 1) P64 = 1;
@@ -610,14 +619,14 @@ bool pj_build(dfgpu_ctx* ctx, dfgpu_join_table* t) {
   }
   int sbits = 6; while ((1ull << sbits) < 2 * max_keys && sbits < PJ_MAX_SBITS) sbits++;
   part->sbits = sbits;
-  t->part = std::move(part);
+  t->part = std::move(part); t->rep = JoinRep::PARTITIONED;
   t->unique = !dup;
   t->mem += (int64_t)n * 12 + (int64_t)(P64 + 1) * 4;
   return true;
 }
 
 bool pj_probe_eligible(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* const* probe_keys, int32_t nkeys, int64_t n) {
-  if (!t->part || !ctx->join_partitioned || n < ctx->join_partitioned_min_probe || n > 0xFFFF0000ll) return false;
+  if (t->rep != JoinRep::PARTITIONED || !ctx->join_partitioned || n < ctx->join_partitioned_min_probe || n > 0xFFFF0000ll) return false;
   if (t->part->hashed) return nkeys == t->nkeys;       // the caller has checked the column types against the build's; dictionaries hash by value
   return nkeys == 1 && probe_keys[0]->type == t->keys[0]->type;          // same physical integer type, no dictionary
 }
@@ -677,23 +686,18 @@ void pj_probe(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* cons
     return;
   }
   // repeated build keys: restore the order of the (probe row, group) matches, then every match emits its group
-  BufferPtr rows = alloc_buffer(ctx, (size_t)(m + 1) * 4), ref = alloc_buffer(ctx, (size_t)(m + 1) * 4), cnt = alloc_buffer(ctx, (size_t)(m + 1) * 4), offs = alloc_buffer(ctx, (size_t)(m + 1) * 8);
-  int64_t total = 0;
-  if (m) {
+  BufferPtr rows = alloc_buffer(ctx, (size_t)(m + 1) * 4), ref = alloc_buffer(ctx, (size_t)(m + 1) * 4);
+  ArrayHolder ob, op;
+  expand_matches(ctx, m, ob, op, [&](uint32_t* cnt) {
     if (P > PJ_MAX_P) hipLaunchKernelGGL((k_pj_restore<true, (int)PJ_MAX_P_BIG>), dim3(rgrid), dim3(PJ_NT), 0, ctx->stream, (const uint64_t*)hits->ptr, (const uint32_t*)off.pstart->ptr, (const uint32_t*)hT->ptr, (const uint16_t*)lT->ptr, (int)P, NC,
                        (const uint32_t*)coff->ptr, (uint32_t*)rows->ptr, (uint64_t*)nullptr, (uint32_t*)ref->ptr);
     else hipLaunchKernelGGL((k_pj_restore<true>), dim3(rgrid), dim3(PJ_NT), 0, ctx->stream, (const uint64_t*)hits->ptr, (const uint32_t*)off.pstart->ptr, (const uint32_t*)hT->ptr, (const uint16_t*)lT->ptr, (int)P, NC,
                        (const uint32_t*)coff->ptr, (uint32_t*)rows->ptr, (uint64_t*)nullptr, (uint32_t*)ref->ptr);
-    hipLaunchKernelGGL(k_pj_group_counts, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)ref->ptr, m, (const uint32_t*)part.grp_cnt->ptr, (uint32_t*)cnt->ptr);
-    KERNEL_CHECK();
-    exclusive_scan_u32(ctx, (const uint32_t*)cnt->ptr, (uint64_t*)offs->ptr, m, ctx->d_scratch64 + 8);
-    total = (int64_t)read_scratch(ctx, 8);
-  }
-  if (total > 0xFFFFFFF0ll) fail(DFGPU_RESOURCES_EXHAUSTED, "join output of %lld rows for one probe batch; split the probe batch", (long long)total);
-  ArrayHolder ob(new_fixed(ctx, DFGPU_UINT64, total)), op(new_fixed(ctx, DFGPU_UINT32, total));
-  if (total) hipLaunchKernelGGL(k_pj_expand, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)rows->ptr, (const uint32_t*)ref->ptr, (const uint64_t*)offs->ptr, m, (const uint32_t*)part.grp_start->ptr,
-                                (const uint32_t*)part.grp_cnt->ptr, (const uint32_t*)part.csr_rows->ptr, (uint64_t*)ob.get()->values->ptr, (uint32_t*)op.get()->values->ptr);
-  KERNEL_CHECK();
+    hipLaunchKernelGGL(k_pj_group_counts, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)ref->ptr, m, (const uint32_t*)part.grp_cnt->ptr, cnt);
+  }, [&](const uint32_t* cnt, const uint64_t* offs, uint64_t* obp, uint32_t* opp) {
+    hipLaunchKernelGGL(k_pj_expand, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint32_t*)rows->ptr, (const uint32_t*)ref->ptr, offs, m, (const uint32_t*)part.grp_start->ptr,
+                       (const uint32_t*)part.grp_cnt->ptr, (const uint32_t*)part.csr_rows->ptr, obp, opp);
+  });
   kt_.reset();
   if (part.hashed) pj_verify(ctx, t, pks, ob, op);
   *out_build = ob.release(); *out_probe = op.release();

@@ -317,6 +317,75 @@ def test_sparse_small_build_gets_its_bitmap_from_the_first_large_probe(ctx, dups
     probe(1000)
 
 
+@pytest.mark.parametrize("case", ["partitioned", "rank_index", "sparse_hash"])
+def test_one_table_probed_along_every_path(ctx, case):
+    """One table probed in sequence by batches that move it between paths; every probe's pairs equal the oracle's and the profile shows the path it took.
+    partitioned: a probe below join_partitioned_min_probe builds the fallback hash table, a large one goes partition by partition, a small one reuses the fallback.
+    rank_index: a dictionary probe builds the fallback hash table, plain probes stay on the rank index, deferred (then dfgpu_join_lookup) and as a selection.
+    sparse_hash: the first large probe builds the lazy bitmap, the small probes before and after take the hash table and the bitmap."""
+    import dfgpu
+    rng = np.random.default_rng(len(case) + 7)
+    opts = {"join_partitioned_min_build": 1, "join_partitioned_min_probe": 50_000} if case == "partitioned" else {}
+    saved = {k: ctx.get_option(k) for k in opts}
+    for k, v in opts.items():
+        ctx.set_option(k, v)
+    try:
+        if case == "partitioned":
+            bk = np.unique(rng.integers(-(1 << 62), 1 << 62, 20_000, dtype=np.int64)); rng.shuffle(bk)          # unsorted keys over a sparse domain
+            draw = lambda n: np.where(rng.random(n) < 0.3, rng.choice(bk, n), rng.integers(-(1 << 62), 1 << 62, n, dtype=np.int64))
+        else:
+            bk = np.arange(0, 30_000, 3, dtype=np.int64) if case == "rank_index" else np.sort(rng.choice(3_000_000, 60, replace=False)).astype(np.int64)[::-1].copy()
+            draw = lambda n: np.where(rng.random(n) < 0.3, rng.choice(bk, n), rng.integers(-10, int(bk.max()) + 100, n))
+        bkeys = pa.array(bk)
+        table = dfgpu.JoinTable(ctx, [ctx.from_arrow(bkeys)])
+        ctx.profile_select(None); ctx.profile_enable(True); ctx.profile_read()
+
+        def probe(n, dictionary=False, nulls=True):
+            parr = pa.array(draw(n).astype(np.int64), mask=(rng.random(n) < 0.05) if nulls else None)
+            bi, pi = table.probe([ctx.from_arrow(parr.dictionary_encode() if dictionary else parr)])
+            want = po.hash_join([[bkeys]], [[parr]], "Inner", batch_size=1 << 40)
+            assert len(want.build_idx) > 0
+            assert np.array_equal(bi.to_numpy().astype(np.int64), want.build_idx) and np.array_equal(pi.to_numpy().astype(np.int64), want.probe_idx)
+            return parr, bi, pi, set(ctx.profile_read())
+
+        if case == "partitioned":
+            ks = probe(5_000)[3]
+            assert {"k_join_build", "k_probe_match_hash"} <= ks and "pj_join" not in ks, ks
+            ks = probe(120_000)[3]
+            assert "pj_join" in ks and not {"k_join_build", "k_probe_match_hash"} & ks, ks
+            ks = probe(5_000)[3]
+            assert "k_probe_match_hash" in ks and not {"k_join_build", "pj_join"} & ks, ks
+        elif case == "rank_index":
+            ks = probe(20_000)[3]
+            assert {"k_probe_match_bitmap", "k_probe_lookup_rank"} <= ks and "k_join_build" not in ks, ks
+            ks = probe(20_000, dictionary=True)[3]
+            assert {"k_join_build", "k_probe_match_hash", "k_probe_lookup"} <= ks and "k_probe_match_bitmap" not in ks, ks
+            ks = probe(20_000)[3]
+            assert {"k_probe_match_bitmap", "k_probe_lookup_rank"} <= ks and "k_join_build" not in ks, ks
+            parr, bi, pi, _ = probe(20_000, nulls=False)
+            keys = [ctx.from_arrow(parr)]
+            dbi, dpi = table.probe_deferred(keys)
+            ks = set(ctx.profile_read())
+            assert dbi is None and np.array_equal(dpi.to_numpy(), pi.to_numpy())
+            assert "k_probe_match_bitmap" in ks and not {"k_probe_lookup_rank", "k_join_build"} & ks, ks
+            assert np.array_equal(table.lookup(keys, dpi).to_numpy(), bi.to_numpy()) and "k_probe_lookup_rank" in set(ctx.profile_read())
+            sel = table.probe_selection(keys)
+            ks = set(ctx.profile_read())
+            assert sel is not None and np.array_equal(np.nonzero(np.asarray(sel.to_arrow()))[0], pi.to_numpy().astype(np.int64))
+            assert "k_probe_match_bitmap" in ks and not {"k_probe_lookup_rank", "k_probe_match_hash"} & ks, ks
+        else:
+            ks = probe(1_000)[3]
+            assert "k_probe_match_hash" in ks and not {"join_build_bitmap", "k_probe_match_bitmap"} & ks, ks
+            ks = probe(400_000)[3]
+            assert {"join_build_bitmap", "k_probe_match_bitmap"} <= ks and "k_probe_match_hash" not in ks, ks
+            ks = probe(1_000)[3]
+            assert "k_probe_match_bitmap" in ks and not {"join_build_bitmap", "k_probe_match_hash"} & ks, ks
+    finally:
+        ctx.profile_enable(False)
+        for k, v in saved.items():
+            ctx.set_option(k, v)
+
+
 def test_identity_index_arrays_are_recognised_and_skipped(ctx, task_ctx):
     """A compaction that keeps every row and the probe indices of a join whose probe rows all match once are 0 .. n-1: the producer marks
     them (dfgpu_array_is_identity), dfgpu_take through them hands back the values array, and the plan layer passes probe-side columns
@@ -394,10 +463,11 @@ def test_probe_key_column_sliced_at_an_odd_row_offset(ctx):
         assert np.array_equal(bi.to_numpy().astype(np.int64), want.build_idx) and np.array_equal(pi.to_numpy().astype(np.int64), want.probe_idx)
 
 
-@pytest.mark.parametrize("shape", ["sorted_keys", "unsorted_unique_keys", "masked_build", "repeated_keys", "nullable_probe"])
+@pytest.mark.parametrize("shape", ["sorted_keys", "unsorted_unique_keys", "masked_build", "repeated_keys", "nullable_probe", "packed_keys"])
 def test_deferred_probe_and_lookup_at_the_abi(ctx, shape):
     """dfgpu_join_probe_deferred / dfgpu_join_lookup: a unique rank-indexed build leaves the build indices out and gives them later for any subset of the matched probe
-    rows; every other table (repeated keys -> CSR, a nullable probe column) answers at once, exactly as dfgpu_join_probe.  Both ways equal the plain probe."""
+    rows; every other table (repeated keys -> CSR, a nullable probe column, two key columns packed into one rank-indexed key) answers at once, exactly as
+    dfgpu_join_probe.  Both ways equal the plain probe.  A lookup into the packed table by one Int64 column is an argument error (its keys are packed tuples)."""
     import dfgpu
     rng = np.random.default_rng(len(shape))
     nb, npr = 30_000, 100_000
@@ -409,13 +479,24 @@ def test_deferred_probe_and_lookup_at_the_abi(ctx, shape):
     bmask = ctx.from_arrow(pa.array(rng.random(nb) < 0.8)) if shape == "masked_build" else None
     p = rng.integers(0, 2 * nb + 40, npr).astype(np.int64)
     pa_p = pa.array(p, mask=(rng.random(npr) < 0.05) if shape == "nullable_probe" else None)
-    table = dfgpu.JoinTable(ctx, [ctx.from_arrow(pa.array(b))], mask=bmask)
-    probe = [ctx.from_arrow(pa_p)]
-    bi, pi = table.probe(probe)
+    split = lambda k: [ctx.from_arrow(pa.array(k // 64)), ctx.from_arrow(pa.array(k % 64))]        # sorted unique tuples: packed, they are a sorted unique key
+    ctx.profile_select(None); ctx.profile_enable(True); ctx.profile_read()
+    try:
+        table = dfgpu.JoinTable(ctx, split(b) if shape == "packed_keys" else [ctx.from_arrow(pa.array(b))], mask=bmask)
+        probe = split(p) if shape == "packed_keys" else [ctx.from_arrow(pa_p)]
+        bi, pi = table.probe(probe)
+        ranked = "k_probe_lookup_rank" in set(ctx.profile_read())
+    finally:
+        ctx.profile_enable(False)
     dbi, dpi = table.probe_deferred(probe)
     assert np.array_equal(dpi.to_numpy(), pi.to_numpy()) if dbi is None or shape != "repeated_keys" else True
-    if shape in ("repeated_keys", "nullable_probe"):
+    if shape in ("repeated_keys", "nullable_probe", "packed_keys"):
         assert dbi is not None and np.array_equal(dbi.to_numpy(), bi.to_numpy()) and np.array_equal(dpi.to_numpy(), pi.to_numpy())
+        if shape == "packed_keys":
+            assert ranked
+            with pytest.raises(dfgpu.DfgpuError) as e:
+                table.lookup([ctx.from_arrow(pa.array(p))])
+            assert e.value.kind == "InvalidArgument"
         return
     assert dbi is None
     assert np.array_equal(table.lookup(probe, dpi).to_numpy(), bi.to_numpy())                       # every matched row
