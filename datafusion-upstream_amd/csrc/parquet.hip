@@ -5,6 +5,7 @@
 // /root/reference; the format itself is the published parquet-format specification, restated here).  The host side parses the Thrift
 // compact footer and the page headers (bytes, no data); everything that touches values runs on the device:
 //
+//   k_pq_gzip     two waves per page: GZIP members (inflate_device.h), a symbol decoder and a byte mover joined by an LDS queue
 //   k_pq_snappy   one wave per page: Snappy raw-format decompression; the last 64 KB of output live in an LDS ring (every back reference of
 //                 the standard 64 KB-block compressor resolves there), tags are parsed out of an LDS window of the input
 //   k_pq_decode   one workgroup per page: definition levels and dictionary indices (RLE / bit-packed hybrid, a batch of runs parsed by one
@@ -22,6 +23,7 @@
 #include <unistd.h>
 #include "device_utils.h"
 #include "zstd_device.h"
+#include "inflate_device.h"
 
 namespace dfgpu {
 namespace pq {
@@ -54,7 +56,7 @@ struct TR {
 
 enum { PT_BOOLEAN = 0, PT_INT32 = 1, PT_INT64 = 2, PT_INT96 = 3, PT_FLOAT = 4, PT_DOUBLE = 5, PT_BYTE_ARRAY = 6, PT_FLBA = 7 };
 enum { ENC_PLAIN = 0, ENC_PLAIN_DICT = 2, ENC_RLE = 3, ENC_BIT_PACKED = 4, ENC_DELTA_BP = 5, ENC_DELTA_LBA = 6, ENC_DELTA_BA = 7, ENC_RLE_DICT = 8, ENC_BSS = 9 };
-enum { CODEC_NONE = 0, CODEC_SNAPPY = 1, CODEC_ZSTD = 6, CODEC_LZ4_RAW = 7 };
+enum { CODEC_NONE = 0, CODEC_SNAPPY = 1, CODEC_GZIP = 2, CODEC_ZSTD = 6, CODEC_LZ4_RAW = 7 };
 enum { PG_DATA = 0, PG_INDEX = 1, PG_DICT = 2, PG_DATA_V2 = 3 };
 
 struct Leaf {
@@ -1286,6 +1288,14 @@ __global__ void __launch_bounds__(64) k_pq_lz4(const SnJob* __restrict__ jobs, u
   if (!zs::lz4_decode(ring, win, jb.src, jb.csize, jb.dst, jb.usize, lane) && lane == 0) atomicOr(flags, DFGPU_FLAG_OOB);
 }
 
+// GZIP pages: a kernel of their own, two waves per page (inflate_device.h: wave 0 decodes symbols, wave 1 moves bytes and checks the CRC-32)
+__global__ void __launch_bounds__(128) k_pq_gzip(const SnJob* __restrict__ jobs, uint32_t* flags) {
+  __shared__ __attribute__((aligned(16))) gz::Lds L;
+  const SnJob jb = jobs[blockIdx.x];
+  if (jb.raw) { for (uint32_t i = threadIdx.x; i < jb.usize; i += 128) jb.dst[i] = jb.src[i]; return; }
+  if (!gz::inflate_page(&L, jb.src, jb.csize, jb.dst, jb.usize) && (threadIdx.x & 63) == 0) atomicOr(flags, DFGPU_FLAG_OOB);
+}
+
 static void plan_column(dfgpu_ctx* ctx, dfgpu_parquet* f, int leaf_idx, int rg0, int nrg, ColumnRead& cr, std::vector<SnJob>& jobs) {
   const Leaf& leaf = f->leaves[(size_t)leaf_idx];
   if (!leaf.arrow) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: Parquet column '%s': %s", leaf.name.c_str(), leaf.why.c_str());
@@ -1300,7 +1310,7 @@ static void plan_column(dfgpu_ctx* ctx, dfgpu_parquet* f, int leaf_idx, int rg0,
   bool staged = false;
   for (int g = rg0; g < rg0 + nrg; g++) {
     const RowGroup& rg = f->rgs[(size_t)g]; const Chunk& ch = rg.cols[(size_t)leaf_idx];
-    if (ch.codec != CODEC_NONE && ch.codec != CODEC_SNAPPY && ch.codec != CODEC_ZSTD && ch.codec != CODEC_LZ4_RAW) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: Parquet compression codec %d of column '%s' (UNCOMPRESSED, SNAPPY, ZSTD and LZ4_RAW are decoded on the device)", ch.codec, leaf.name.c_str());
+    if (ch.codec != CODEC_NONE && ch.codec != CODEC_SNAPPY && ch.codec != CODEC_GZIP && ch.codec != CODEC_ZSTD && ch.codec != CODEC_LZ4_RAW) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: Parquet compression codec %d of column '%s' (UNCOMPRESSED, SNAPPY, GZIP, ZSTD and LZ4_RAW are decoded on the device)", ch.codec, leaf.name.c_str());
     if (ch.num_values != rg.rows) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: Parquet column '%s' holds %lld values for %lld rows (repeated values)", leaf.name.c_str(), (long long)ch.num_values, (long long)rg.rows);
     if (ch.num_values == 0) continue;                       // a row group without rows: nothing to walk
     int64_t start = ch.dict_off > 0 && ch.dict_off < ch.data_off ? ch.dict_off : ch.data_off;
@@ -1522,7 +1532,14 @@ dfgpu_status dfgpu_parquet_read(dfgpu_ctx* ctx, dfgpu_parquet* f, int32_t first_
     for (int32_t i : order) plan_column(ctx, f, columns[i], first_row_group, num_row_groups, reads[(size_t)i], jobs);
     const bool compressed = !jobs.empty();
     if (compressed) for (int32_t i = 0; i < ncols; i++) if (reads[(size_t)i].copied) HIP_CHECK(hipStreamWaitEvent(ctx->stream, reads[(size_t)i].copied, 0));      // the decompressors take every page of the read in one launch
-    std::vector<SnJob> zjobs, ljobs; { std::vector<SnJob> sj; for (auto& j : jobs) (j.codec == CODEC_ZSTD ? zjobs : j.codec == CODEC_LZ4_RAW ? ljobs : sj).push_back(j); jobs.swap(sj); }
+    std::vector<SnJob> zjobs, ljobs, gjobs; { std::vector<SnJob> sj; for (auto& j : jobs) (j.codec == CODEC_ZSTD ? zjobs : j.codec == CODEC_LZ4_RAW ? ljobs : j.codec == CODEC_GZIP ? gjobs : sj).push_back(j); jobs.swap(sj); }
+    if (!gjobs.empty()) {                         // GZIP: a DEFLATE stream is sequential, the pages of the read are the parallelism -- one workgroup each, the longest first
+      std::stable_sort(gjobs.begin(), gjobs.end(), [](const SnJob& x, const SnJob& y) { return x.usize > y.usize; });
+      BufferPtr dg = upload(ctx, gjobs);
+      KernelTimer kt(ctx, "pq_gzip");
+      hipLaunchKernelGGL(k_pq_gzip, dim3((unsigned)gjobs.size()), dim3(128), 0, ctx->stream, (const SnJob*)dg->ptr, ctx->d_flags);
+      KERNEL_CHECK();
+    }
     if (!ljobs.empty()) {
       std::stable_sort(ljobs.begin(), ljobs.end(), [](const SnJob& x, const SnJob& y) { return x.usize > y.usize; });
       BufferPtr dl = upload(ctx, ljobs);
