@@ -393,6 +393,7 @@ static const CtxOption kCtxOptions[] = {
   { "join_rank_index_unsorted", OPT_BOOL(join_rank_index_unsorted) },
   { "join_lazy_build_rows", OPT_BOOL(join_lazy_build_rows) },
   { "join_selection_output", OPT_BOOL(join_selection_output) },
+  { "join_probe_fused_filter", OPT_BOOL(join_probe_fused_filter) },
   { "join_key_packing", OPT_BOOL(join_key_packing) },
   { "join_swap_small_semi", OPT_BOOL(join_swap_small_semi) },
   { "join_partitioned", OPT_BOOL(join_partitioned) },

@@ -45,6 +45,7 @@ struct dfgpu_ctx {
   bool join_rank_index = true;
   bool join_lazy_build_rows = true;         // plan layer: an Inner HashJoinExec over a unique rank-indexed build looks the build rows up when a build-side column is read (dfgpu_join_probe_deferred)
   bool join_selection_output = true;        // plan layer: such a join whose build side contributes key columns only answers with the probe batch under a selection (dfgpu_join_probe_selection)
+  bool join_probe_fused_filter = true;      // plan layer: a FilterExec `column <op> literal` under a HashJoinExec's probe side is evaluated inside the bitmap probe (dfgpu_join_probe_fused)
   bool join_rank_index_unsorted = true;     // unique integer keys over a dense domain in ANY order (a repartitioned or filtered primary-key column): bitmap + rank -> build row
   bool join_key_packing = true;
   bool group_run_detection = true;

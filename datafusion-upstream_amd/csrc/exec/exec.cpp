@@ -131,8 +131,32 @@ static Col col_take(const Col& c, const ArrayRef& idx, const MemoPtr& memo = nul
 }
 static Col col_of(ArrayRef a) { Col c; c.arr = std::move(a); return c; }
 
+// A FilterExec predicate `column <op> scalar` that has not been evaluated yet: the HashJoinExec the filter feeds the probe side of evaluates it inside its probe
+// (dfgpu_join_probe_fused).  It holds the column itself, not a schema index, so a projection that drops or reorders columns on the way does not disturb it.
+struct PendingPredicate { ArrayRef column, scalar; int op = 0; explicit operator bool() const { return op != 0; } };
 struct Batch {
-  SchemaPtr schema; std::vector<Col> cols; ArrayRef selection; int64_t base_rows = 0;
+  SchemaPtr schema; std::vector<Col> cols; int64_t base_rows = 0;
+ private:
+  // the rows of the batch that count are those of `sel_` (all when empty) for which `pend_` (if any) holds.  Private: whoever reads the selection reads it through
+  // selection(), which evaluates a pending predicate first -- only the fused probe takes the two apart (take_filter)
+  mutable ArrayRef sel_; mutable PendingPredicate pend_;
+ public:
+  bool filtered() const { return sel_ || pend_; }
+  bool has_pending() const { return (bool)pend_; }
+  // the selection bitmap (empty = every row).  A pending predicate is evaluated into it here, by the call FilterExec itself would have made, and AND-ed with the selection
+  // the batch already carried: after this the batch is what it would be had the filter evaluated at once.
+  const ArrayRef& selection(const TaskContext& tc) const {
+    if (pend_) {
+      dfgpu_array* o = nullptr; tc.check(dfgpu_binary(tc.ctx, pend_.op, pend_.column.a, 0, pend_.scalar.a, 1, &o)); ArrayRef mask = ArrayRef::adopt(o);
+      if (sel_) { dfgpu_array* a = nullptr; tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_AND, mask.a, 0, sel_.a, 0, &a)); mask = ArrayRef::adopt(a); }
+      sel_ = mask; pend_ = PendingPredicate();
+    }
+    return sel_;
+  }
+  void set_selection(ArrayRef s) { sel_ = std::move(s); pend_ = PendingPredicate(); }
+  void set_pending(ArrayRef column, int op, ArrayRef scalar) { pend_.column = std::move(column); pend_.op = op; pend_.scalar = std::move(scalar); }      // on top of the selection the batch carries
+  void filter_like(const Batch& o) { sel_ = o.sel_; pend_ = o.pend_; }        // an operator that passes the rows on untouched
+  ArrayRef take_filter(PendingPredicate* pending) { *pending = pend_; pend_ = PendingPredicate(); ArrayRef m = std::move(sel_); sel_ = ArrayRef(); return m; }      // the fused probe
   // A pending gather of a result-sized batch (<= 2^20 rows) takes its siblings along: every other column of the batch that waits behind the SAME index arrays is gathered in the
   // same launch (dfgpu_take_multi) -- at that size a launch costs more than the bytes it moves, and a query's last operators read 3-5 columns through each row list.
   const ArrayRef& column(const TaskContext& tc, int i) {
@@ -157,13 +181,13 @@ struct Batch {
 static ArrayRef mask_indices(const TaskContext& tc, const ArrayRef& mask) { dfgpu_array* o = nullptr; tc.check(dfgpu_mask_to_indices(tc.ctx, mask.a, &o)); return ArrayRef::adopt(o); }
 // ≙ filter_record_batch (filter.rs:325), lazily per column
 static Batch materialize(const TaskContext& tc, const Batch& b) {
-  if (!b.selection) return b;
-  ArrayRef sel = mask_indices(tc, b.selection);
+  if (!b.filtered()) return b;
+  ArrayRef sel = mask_indices(tc, b.selection(tc));
   Batch o; o.schema = b.schema; o.base_rows = sel.len();
   MemoPtr memo = std::make_shared<TakeMemo>(); for (auto& c : b.cols) o.cols.push_back(col_take(c, sel, memo));
   return o;
 }
-static int64_t num_rows(const TaskContext& tc, const Batch& b) { return b.selection ? mask_indices(tc, b.selection).len() : b.base_rows; }
+static int64_t num_rows(const TaskContext& tc, const Batch& b) { return b.filtered() ? mask_indices(tc, b.selection(tc)).len() : b.base_rows; }
 static ArrayRef concat_arrays(const TaskContext& tc, std::vector<ArrayRef>& parts) {
   std::vector<const dfgpu_array*> p; for (auto& x : parts) p.push_back(x.a);
   dfgpu_array* o = nullptr; tc.check(dfgpu_concat(tc.ctx, p.data(), (int32_t)p.size(), &o)); return ArrayRef::adopt(o);
@@ -310,7 +334,7 @@ struct Plan : std::enable_shared_from_this<Plan> {
   // description built once can be executed again from scratch.
   virtual PlanPtr fresh() const = 0;
 };
-static int64_t metric_rows(const TaskContext& tc, const Batch& b) { if (!b.selection) return b.base_rows; int64_t k = 0; tc.check(dfgpu_mask_count(tc.ctx, b.selection.a, &k)); return k; }
+static int64_t metric_rows(const TaskContext& tc, const Batch& b) { if (!b.filtered()) return b.base_rows; int64_t k = 0; tc.check(dfgpu_mask_count(tc.ctx, b.selection(tc).a, &k)); return k; }
 struct MeteredStream : Stream {
   const Plan* op; PlanPtr keep; std::unique_ptr<Stream> in; TaskContext tc;
   MeteredStream(PlanPtr k, std::unique_ptr<Stream> i, TaskContext t) : op(k.get()), keep(std::move(k)), in(std::move(i)), tc(t) {}
@@ -433,7 +457,25 @@ static ArrayRef known_mask(const TaskContext& tc, const ArrayRef& m) {     // NU
 
 struct FilterExec : Plan {        // filter.rs:56-66, batch_filter :315-327
   ExprPtr pred; PlanPtr input;
-  PlanPtr fresh() const override { auto f = std::make_shared<FilterExec>(); f->pred = pred; f->input = input->fresh(); return f; }
+  // set by the HashJoinExec this filter feeds the probe (right) side of, through operators that pass a batch's filter on untouched (mark_probe_filter): only then may the
+  // predicate travel with the batch unevaluated -- any other consumer would evaluate it at once anyway
+  mutable bool feeds_probe = false;
+  PlanPtr fresh() const override { auto f = std::make_shared<FilterExec>(); f->pred = pred; f->input = input->fresh(); f->feeds_probe = feeds_probe; return f; }
+  // `column <op> literal` (either order) as the compare fast path takes it (csrc/expr.hip): Int32 / Date32 / Int64 column without validity, non-NULL literal of its type,
+  // op EQ..GTEQ -- nothing that could raise or yield NULL -- over a materialised column of a device-sized batch
+  bool deferrable(const TaskContext& tc, const Batch& b, ArrayRef* column, int* op, ArrayRef* scalar) const {
+    if (!feeds_probe || b.has_pending() || b.base_rows <= (tc.batch_size > 8192 ? tc.batch_size : 8192)) return false;
+    auto* be = dynamic_cast<const BinaryExpr*>(pred.get()); if (!be || be->op < DFGPU_OP_EQ || be->op > DFGPU_OP_GTEQ) return false;
+    const bool col_left = be->l->column_index() >= 0;
+    auto* lit = dynamic_cast<const LiteralExpr*>((col_left ? be->r : be->l).get()); const int ci = (col_left ? be->l : be->r)->column_index();
+    if (!lit || ci < 0 || ci >= (int)b.cols.size() || !b.cols[(size_t)ci].arr) return false;
+    int64_t v = 1; if (dfgpu_ctx_get_option(tc.ctx, "join_probe_fused_filter", &v) == DFGPU_OK && v == 0) return false;
+    dfgpu_array_desc cd, sd; dfgpu_array_describe(b.cols[(size_t)ci].arr.a, &cd); dfgpu_array_describe(lit->scalar.a, &sd);
+    if ((cd.type != DFGPU_INT32 && cd.type != DFGPU_DATE32 && cd.type != DFGPU_INT64) || cd.validity || cd.length != b.base_rows || sd.type != cd.type || sd.length != 1 || sd.validity || sd.null_count != 0) return false;
+    static const int swapped[6] = { DFGPU_OP_EQ, DFGPU_OP_NEQ, DFGPU_OP_GT, DFGPU_OP_GTEQ, DFGPU_OP_LT, DFGPU_OP_LTEQ };      // literal <op> column == column <swapped op> literal
+    *column = b.cols[(size_t)ci].arr; *scalar = lit->scalar; *op = col_left ? be->op : swapped[be->op - DFGPU_OP_EQ];
+    return true;
+  }
   std::vector<std::shared_ptr<const Plan>> children() const override { return {input}; }
   const char* name() const override { return "FilterExec"; }
   SchemaPtr schema() const override { return input->schema(); }
@@ -443,20 +485,21 @@ struct FilterExec : Plan {        // filter.rs:56-66, batch_filter :315-327
     S(const FilterExec* o, std::unique_ptr<Stream> i, TaskContext t) : op(o), in(std::move(i)), tc(t) {}
     bool next(Batch& out) override {
       Batch b; if (!in->next(b)) return false;
-      if (b.selection && !op->pred->safe()) b = materialize(tc, b);
+      { ArrayRef column, scalar; int cmp = 0; if (op->deferrable(tc, b, &column, &cmp, &scalar)) { b.set_pending(column, cmp, scalar); out = std::move(b); return true; } }
+      if (b.filtered() && !op->pred->safe()) b = materialize(tc, b);
       Value v = op->pred->eval(tc, b);
       ArrayRef mask = into_array(tc, v, b.base_rows);
       dfgpu_array_desc d; dfgpu_array_describe(mask.a, &d);
       if (d.type != DFGPU_BOOL) fail(DFGPU_INTERNAL, "Cannot create filter_array from non-boolean predicates");
-      if (b.selection) { ArrayRef km = known_mask(tc, mask); dfgpu_array* o = nullptr; tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_AND, km.a, 0, b.selection.a, 0, &o)); mask = ArrayRef::adopt(o); }
-      b.selection = mask; out = std::move(b); return true;
+      if (b.filtered()) { ArrayRef km = known_mask(tc, mask); dfgpu_array* o = nullptr; tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_AND, km.a, 0, b.selection(tc).a, 0, &o)); mask = ArrayRef::adopt(o); }
+      b.set_selection(mask); out = std::move(b); return true;
     }
   };
   std::unique_ptr<Stream> execute(int p, const TaskContext& tc) const override { return std::unique_ptr<Stream>(new S(this, input->run(p, tc), tc)); }
 };
 
 static Batch materialize_subset(const TaskContext& tc, Batch& b, const std::set<int>& needed) {   // compact only referenced columns
-  ArrayRef sel = mask_indices(tc, b.selection);
+  ArrayRef sel = mask_indices(tc, b.selection(tc));
   Batch o; o.schema = b.schema; o.base_rows = sel.len();
   ArrayRef filler; MemoPtr memo = std::make_shared<TakeMemo>();
   for (size_t i = 0; i < b.cols.size(); i++) {
@@ -490,12 +533,12 @@ struct ProjectionExec : Plan {    // projection.rs:52-62, batch_project :295-317
     // (evaluate_deferred) and reads keys and arguments through the selection as a mask: nothing is evaluated here, so the selection is carried whatever its density and
     // the count -- a pass over the bitmap and a host round trip per batch -- is not taken.)
     RowSel rowsel;
-    if (b.selection && !only_columns() && !defer) {
-      int64_t kept = 0; tc.check(dfgpu_mask_count(tc.ctx, b.selection.a, &kept));
-      if (kept * 4 >= b.base_rows) { tc.check(dfgpu_ctx_set_row_selection(tc.ctx, b.selection.a)); rowsel.c = tc.ctx; }
+    if (b.filtered() && !only_columns() && !defer) {
+      int64_t kept = 0; tc.check(dfgpu_mask_count(tc.ctx, b.selection(tc).a, &kept));
+      if (kept * 4 >= b.base_rows) { tc.check(dfgpu_ctx_set_row_selection(tc.ctx, b.selection(tc).a)); rowsel.c = tc.ctx; }
       else { std::set<int> need; for (auto& e : exprs) e->columns(need); b = materialize_subset(tc, b, need); if (defer) defer->assign(exprs.size(), false); defer = nullptr; }
     }
-    Batch o; o.base_rows = b.base_rows; o.selection = b.selection; auto s = std::make_shared<Schema>();
+    Batch o; o.base_rows = b.base_rows; o.filter_like(b); auto s = std::make_shared<Schema>();         // plain columns: a pending predicate goes along unevaluated
     if (defer) defer->assign(exprs.size(), false);
     for (size_t i = 0; i < exprs.size(); i++) {
       int ci = exprs[i]->column_index();
@@ -511,7 +554,7 @@ struct ProjectionExec : Plan {    // projection.rs:52-62, batch_project :295-317
   // evaluate one deferred expression of project() over the batch it was deferred on
   void evaluate_deferred(const TaskContext& tc, Batch& raw, Batch& projected, size_t i) const {
     RowSel rowsel;
-    if (raw.selection) { tc.check(dfgpu_ctx_set_row_selection(tc.ctx, raw.selection.a)); rowsel.c = tc.ctx; }
+    if (raw.filtered()) { tc.check(dfgpu_ctx_set_row_selection(tc.ctx, raw.selection(tc).a)); rowsel.c = tc.ctx; }
     ArrayRef a = into_array(tc, exprs[i]->eval(tc, raw), raw.base_rows);
     projected.schema->f[i] = field_of(names[i], a.a); projected.cols[i] = col_of(a);
   }
@@ -540,7 +583,7 @@ struct CoalesceBatchesExec : Plan {    // coalesce_batches.rs:198-260
     bool next(Batch& out) override {
       while (!done) {
         Batch b; if (!in->next(b)) { done = true; break; }
-        if (b.selection) { if (b.base_rows >= op->target) { out = std::move(b); return true; } b = materialize(tc, b); }   // device mega-batch: keep the fused mask
+        if (b.filtered()) { if (b.base_rows >= op->target) { out = std::move(b); return true; } b = materialize(tc, b); }   // device mega-batch: keep the fused mask
         if (b.base_rows == 0) continue;
         if (b.base_rows >= op->target && buf.empty()) { out = std::move(b); return true; }
         rows += b.base_rows; buf.push_back(std::move(b));
@@ -570,16 +613,17 @@ struct CoalescePartitionsExec : Plan {   // coalesce_partitions.rs
 static void partition_batch(const TaskContext& tc, Batch& b, const std::vector<ExprPtr>& exprs, int n, std::vector<std::vector<Batch>>& outs) {
   if (b.base_rows == 0) return;
   bool safe_keys = true; for (auto& e : exprs) safe_keys &= e->safe();
-  if (n <= 256 && (!b.selection || safe_keys)) {
+  if (n <= 256 && (!b.filtered() || safe_keys)) {
     // one pass (dfgpu_partition_columns): the key expressions run over the full-length batch (a fused selection goes along as the mask),
     // every materialised fixed-width column is written grouped by destination in the same read; lazy / variable-width columns follow
     // through the grouped row numbers
-    Batch kb = b; kb.selection = ArrayRef();
+    const ArrayRef bsel = b.selection(tc);
+    Batch kb = b; kb.set_selection(ArrayRef());
     std::vector<ArrayRef> keys; std::vector<const dfgpu_array*> kp;
     for (auto& e : exprs) { keys.push_back(into_array(tc, e->eval(tc, kb), kb.base_rows)); kp.push_back(keys.back().a); }
     std::vector<const dfgpu_array*> cp; for (auto& c : b.cols) cp.push_back(c.arr ? c.arr.a : nullptr);
     std::vector<dfgpu_array*> oc(b.cols.size(), nullptr); std::vector<int64_t> counts((size_t)n); dfgpu_array* idx = nullptr;
-    tc.check(dfgpu_partition_columns(tc.ctx, kp.data(), (int32_t)kp.size(), n, cp.data(), (int32_t)cp.size(), b.selection.a, oc.data(), &idx, counts.data()));
+    tc.check(dfgpu_partition_columns(tc.ctx, kp.data(), (int32_t)kp.size(), n, cp.data(), (int32_t)cp.size(), bsel.a, oc.data(), &idx, counts.data()));
     ArrayRef indices = ArrayRef::adopt(idx); std::vector<ArrayRef> moved; for (auto* x : oc) moved.push_back(ArrayRef::adopt(x));
     int64_t off = 0;
     for (int d = 0; d < n; d++) {
@@ -599,7 +643,7 @@ static void partition_batch(const TaskContext& tc, Batch& b, const std::vector<E
     return;
   }
   ArrayRef sel; Batch kb = b;
-  if (b.selection) { std::set<int> need; for (auto& e : exprs) e->columns(need); sel = mask_indices(tc, b.selection); kb = materialize_subset(tc, b, need); }
+  if (b.filtered()) { std::set<int> need; for (auto& e : exprs) e->columns(need); sel = mask_indices(tc, b.selection(tc)); kb = materialize_subset(tc, b, need); }
   if (kb.base_rows == 0) return;
   std::vector<ArrayRef> keys; std::vector<const dfgpu_array*> kp;
   for (auto& e : exprs) { keys.push_back(into_array(tc, e->eval(tc, kb), kb.base_rows)); kp.push_back(keys.back().a); }
@@ -677,7 +721,7 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
     auto bs = std::make_shared<BuildSide>();
     std::vector<Batch> in;
     if (partition < 0) { for (int p = 0; p < left->partitions(); p++) drain(left, p, tc, in); } else drain(left, partition, tc, in);
-    if (in.size() == 1 && in[0].selection) { bs->batch = in[0]; *fused = in[0].selection; bs->batch.selection = ArrayRef(); bs->segments = { bs->batch.base_rows }; bs->empty = false; }
+    if (in.size() == 1 && in[0].filtered()) { *fused = in[0].selection(tc); bs->batch = in[0]; bs->batch.set_selection(ArrayRef()); bs->segments = { bs->batch.base_rows }; bs->empty = false; }
     else {
       std::vector<Batch> m; for (auto& b : in) { Batch x = materialize(tc, b); if (x.base_rows) { bs->segments.push_back(x.base_rows); m.push_back(std::move(x)); } }
       if (m.empty()) return bs;
@@ -815,17 +859,31 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
         // a probe batch of the reference's size (<= max(batch_size, 8192) rows) comes out in the reference's chunks; the device's own
         // whole-partition batches are answered in one piece (their consumers re-slice to batch_size)
         const bool chunked = pb.base_rows <= (tc.batch_size > 8192 ? tc.batch_size : 8192);
-        if (chunked && pb.selection) { pb = materialize(tc, pb); if (pb.base_rows == 0) continue; }
+        if (chunked && pb.filtered()) { pb = materialize(tc, pb); if (pb.base_rows == 0) continue; }
         // Right / Full / RightSemi / RightAnti emit the probe rows WITHOUT a match (adjust_indices_by_join_type over the batch's row range,
         // joins/utils.rs:1234-1279): rows a fused FilterExec dropped must not come back as unmatched rows, so the selection is applied first
-        if (pb.selection && (op->join_type == DFGPU_JOIN_RIGHT || op->join_type == DFGPU_JOIN_FULL || op->right_only())) { pb = materialize(tc, pb); if (pb.base_rows == 0) continue; }
-        ArrayRef mask = pb.selection; pb.selection = ArrayRef();
+        if (pb.filtered() && (op->join_type == DFGPU_JOIN_RIGHT || op->join_type == DFGPU_JOIN_FULL || op->right_only())) { pb = materialize(tc, pb); if (pb.base_rows == 0) continue; }
+        // a predicate the FilterExec below left pending goes into the probe itself; without a table to probe it is evaluated like anywhere else
+        PendingPredicate pend; ArrayRef mask;
+        if (pb.has_pending() && !bs->empty) mask = pb.take_filter(&pend); else { mask = pb.selection(tc); pb.set_selection(ArrayRef()); }
         ArrayRef bidx, pidx;
         if (bs->empty) { dfgpu_array *a = nullptr, *b = nullptr; dfgpu_array_desc d{}; d.type = DFGPU_UINT64; d.values = &d; tc.check(dfgpu_array_import_host(tc.ctx, &d, &a)); d.type = DFGPU_UINT32; tc.check(dfgpu_array_import_host(tc.ctx, &d, &b)); bidx = ArrayRef::adopt(a); pidx = ArrayRef::adopt(b); }
         else {
           std::vector<ArrayRef> keys; std::vector<const dfgpu_array*> kp;
           for (auto& e : op->on_r) { keys.push_back(into_array(tc, e->eval(tc, pb), pb.base_rows)); kp.push_back(keys.back().a); }
           dfgpu_array *b = nullptr, *p = nullptr;
+          // One probe in the form asked for, with the pending predicate folded in (dfgpu_join_probe_fused).  A table or form that does not take the predicate
+          // (DFGPU_NOT_IMPLEMENTED, nothing launched) gets it evaluated into the mask -- Batch::selection, the one resolver -- and is probed as before, this route and the next.
+          auto probe_as = [&](int form, dfgpu_array** ob, dfgpu_array** opi, dfgpu_array** os) -> dfgpu_status {
+            if (pend) {
+              dfgpu_status st = dfgpu_join_probe_fused(tc.ctx, bs->table->t, kp.data(), (int32_t)kp.size(), mask.a, pend.column.a, pend.op, pend.scalar.a, form, ob, opi, os);
+              if (st != DFGPU_NOT_IMPLEMENTED) return st;
+              Batch r; r.base_rows = pb.base_rows; r.set_selection(mask); r.set_pending(pend.column, pend.op, pend.scalar); mask = r.selection(tc); pend = PendingPredicate();
+            }
+            if (form == DFGPU_PROBE_SELECTION) return dfgpu_join_probe_selection(tc.ctx, bs->table->t, kp.data(), (int32_t)kp.size(), mask.a, os);
+            if (form == DFGPU_PROBE_DEFERRED) return dfgpu_join_probe_deferred(tc.ctx, bs->table->t, kp.data(), (int32_t)kp.size(), mask.a, ob, opi);
+            return dfgpu_join_probe(tc.ctx, bs->table->t, kp.data(), (int32_t)kp.size(), mask.a, ob, opi);
+          };
           // an Inner join whose build rows nothing here needs (no filter, no final pass, one piece): the table may leave them for later (LazyLookup)
           bool defer = !chunked && op->join_type == DFGPU_JOIN_INNER && !op->filter && !need_final && kp.size() == 1 && lazy_build_rows;
           // An Inner join over a unique build of which nothing but (aliased) key columns leaves the build side: its output is the probe batch under the selection
@@ -835,9 +893,9 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
           if (defer && selection_output && op->selection_consumer) {
             std::vector<int> al = key_aliases(&bs->batch, pb); bool all = !al.empty(); for (int a : al) all = all && a >= 0;
             if (all) {
-              dfgpu_array* s = nullptr; dfgpu_status st = dfgpu_join_probe_selection(tc.ctx, bs->table->t, kp.data(), 1, mask.a, &s);
+              dfgpu_array* s = nullptr; dfgpu_status st = probe_as(DFGPU_PROBE_SELECTION, nullptr, nullptr, &s);
               if (st == DFGPU_OK) {
-                Batch o; o.schema = out_schema; o.base_rows = pb.base_rows; o.selection = ArrayRef::adopt(s);
+                Batch o; o.schema = out_schema; o.base_rows = pb.base_rows; o.set_selection(ArrayRef::adopt(s));
                 for (int a : al) o.cols.push_back(pb.cols[(size_t)a]);
                 for (auto& c : pb.cols) o.cols.push_back(c);
                 out = std::move(o); return true;
@@ -847,7 +905,7 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
           }
           for (auto& c : bs->batch.cols) defer = defer && (bool)c.arr;
           if (defer) {
-            tc.check(dfgpu_join_probe_deferred(tc.ctx, bs->table->t, kp.data(), 1, mask.a, &b, &p)); pidx = ArrayRef::adopt(p);
+            tc.check(probe_as(DFGPU_PROBE_DEFERRED, &b, &p, nullptr)); pidx = ArrayRef::adopt(p);
             if (!b) {
               auto lz = std::make_shared<LazyLookup>(); lz->keep = bs; lz->table = bs->table->t; lz->probe_key = keys[0]; lz->rows = pidx; lz->m = pidx.len();
               // Left for later when that can only win: every probe row matched (the lookup is the big one, and a later operator may thin the rows first -- Q18), or no
@@ -857,7 +915,7 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
               if (!wanted || (dfgpu_array_is_identity(pidx.a) && pidx.len() == pb.base_rows)) { out = build_batch(&bs->batch, pb, ArrayRef(), pidx, lz); return true; }
               bidx = lz->resolve(tc, ArrayRef());
             } else bidx = ArrayRef::adopt(b);
-          } else { tc.check(dfgpu_join_probe(tc.ctx, bs->table->t, kp.data(), (int32_t)kp.size(), mask.a, &b, &p)); bidx = ArrayRef::adopt(b); pidx = ArrayRef::adopt(p); }
+          } else { tc.check(probe_as(DFGPU_PROBE_PAIRS, &b, &p, nullptr)); bidx = ArrayRef::adopt(b); pidx = ArrayRef::adopt(p); }
           if (!chunked) { apply_filter(pb, bidx, pidx); if (need_final) tc.check(dfgpu_join_mark_visited(tc.ctx, bs->table->t, bidx.a)); }
         }
         if (chunked) {
@@ -895,7 +953,7 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
       Batch& lb = bs->batch;
       const bool anti = op->join_type == DFGPU_JOIN_LEFT_ANTI;
       if (anti && fused) {          // the complement below runs over every row of the left batch: apply a fused selection first
-        Batch sel = lb; sel.selection = fused; lb = materialize(tc, sel); fused = ArrayRef(); bs->segments = { lb.base_rows };
+        Batch sel = lb; sel.set_selection(fused); lb = materialize(tc, sel); fused = ArrayRef(); bs->segments = { lb.base_rows };
       }
       ArrayRef lidx;
       if (!have_right) {
@@ -1523,7 +1581,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
         for (int ci : need) ensure(ci);
       }
       if (b.base_rows == 0) return;
-      ArrayRef mask = b.selection; b.selection = ArrayRef();
+      ArrayRef mask = b.selection(tc); b.set_selection(ArrayRef());
       if (!sets.empty()) { if (specials) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: COUNT(DISTINCT) / string MIN-MAX under grouping sets on the device"); for (size_t ci = 0; ci < deferred.size(); ci++) ensure((int)ci); group_aggregate_sets(tc, b, mask, groups, accs); return; }
       ArrayRef gids; int64_t total = 1;
       if (grouped) {
@@ -2073,7 +2131,7 @@ const char* dfgpu_batch_column_name(const dfgpu_batch* b, int32_t i) { return (b
 dfgpu_status dfgpu_batch_num_rows(dfgpu_ctx* ctx, dfgpu_batch* b, int64_t* out) { return guard([&] { if (!ctx || !b || !out) fail(DFGPU_INVALID_ARGUMENT, "batch_num_rows: null argument"); TaskContext tc{ctx, 8192}; *out = num_rows(tc, b->b); }); }
 // every pending gather of the batch: columns that go through the same index array are gathered together (dfgpu_take_multi)
 static void materialize_all(const TaskContext& tc, Batch& b) {
-  if (b.selection) b = materialize(tc, b);
+  if (b.filtered()) b = materialize(tc, b);
   std::map<const dfgpu_array*, std::vector<size_t>> groups;
   for (size_t i = 0; i < b.cols.size(); i++) { Col& c = b.cols[i]; if (!c.arr && c.source && !c.chain.empty()) groups[col_indices(tc, c).a].push_back(i); }
   for (auto& g : groups) {
@@ -2093,7 +2151,7 @@ dfgpu_status dfgpu_batch_column(dfgpu_ctx* ctx, dfgpu_batch* b, int32_t i, dfgpu
   return guard([&] {
     if (!ctx || !b || !out) fail(DFGPU_INVALID_ARGUMENT, "batch_column: null argument");
     TaskContext tc{ctx, 8192};
-    if (b->b.selection) b->b = materialize(tc, b->b);
+    if (b->b.filtered()) b->b = materialize(tc, b->b);
     const ArrayRef& a = b->b.column(tc, i); dfgpu_array_retain(a.a); *out = a.a;
   });
 }
@@ -2176,10 +2234,12 @@ dfgpu_status dfgpu_plan_coalesce_batches(const dfgpu_plan* input, int64_t target
 dfgpu_status dfgpu_plan_coalesce_partitions(const dfgpu_plan* input, dfgpu_plan** out) { return guard([&] { auto c = std::make_shared<CoalescePartitionsExec>(); c->input = pl(input); *out = new dfgpu_plan{c}; }); }
 // the nearest HashJoinExec below `p` through operators that pass a selection on untouched (CoalesceBatchesExec, a ProjectionExec of plain columns) learns that its
 // consumer fuses selections
-static void mark_selection_consumer(const PlanPtr& p) {
+// probe_side: `p` is the right input of a HashJoinExec -- the nearest FilterExec on the same walk learns that its predicate may travel to that join's probe unevaluated
+static void mark_selection_consumer(const PlanPtr& p, bool probe_side = false) {
   const Plan* q = p.get();
   while (q) {
     if (auto* hj = dynamic_cast<const HashJoinExec*>(q)) { hj->selection_consumer = true; return; }
+    if (auto* fe = dynamic_cast<const FilterExec*>(q)) { if (probe_side) fe->feeds_probe = true; return; }
     if (auto* cb = dynamic_cast<const CoalesceBatchesExec*>(q)) q = cb->input.get();
     else if (auto* pr = dynamic_cast<const ProjectionExec*>(q)) { if (!pr->only_columns()) return; q = pr->input.get(); }
     else return;
@@ -2198,7 +2258,7 @@ dfgpu_status dfgpu_plan_hash_join(const dfgpu_plan* left, const dfgpu_plan* righ
     for (int i = 0; i < non; i++) { j->on_l.push_back(ex(on_left[i])); j->on_r.push_back(ex(on_right[i])); }
     if (filter) { j->filter = ex(filter); for (int i = 0; i < nf; i++) { j->f_side.push_back(fs[i]); j->f_index.push_back(fi[i]); } }
     j->join_type = join_type; j->mode = mode; j->null_equals_null = nen != 0;
-    mark_selection_consumer(j->left); mark_selection_consumer(j->right);
+    mark_selection_consumer(j->left); mark_selection_consumer(j->right, true);
     *out = new dfgpu_plan{j};
   });
 }

@@ -145,59 +145,102 @@ __device__ inline uint64_t spread32(uint64_t x) {      // bit i -> bit 2i
   x = (x | (x << 2)) & 0x3333333333333333ull; x = (x | (x << 1)) & 0x5555555555555555ull; return x;
 }
 // One 512-row chunk per wave, launched 1:1 (measured faster than a persistent grid: consecutive workgroups keep the key
-// stream and the bitmap window local).  Mask / validity presence and "the whole chunk is in range" are compile-time so
-// that the loads of one chunk are not split across branches (measured 1.34 -> 1.18 ms per 600M keys).
-// Bitmap window: clustered probe keys (a fact table stored in key order) put the wave's 512 keys inside one run of 64
-// bitmap words, so the wave loads that run once, coalesced, from the first key of its chunk and looks bits up with
-// ds_bpermute; keys outside the window take the per-lane gather (profiles/experiments/probe_stream_microbench.hip:
-// 1.29 -> 1.05 ms per 600M sorted keys, unchanged for random keys).
-template <typename T, bool HAS_MASK, bool HAS_VALID, bool FULL>
-__device__ inline void probe_match_chunk(const T* keys, const uint64_t* key_valid, const uint64_t* mask, int64_t n, int64_t kmin, uint64_t range,
+// stream and the bitmap window local).  Mask / validity / predicate presence, the predicate's operator and "the whole
+// chunk is in range" are compile-time so that the loads of one chunk are not split across branches.
+// A wave makes at most two dependent memory round trips:
+//  1. everything that depends on nothing -- the four key loads, the selection words, the key validity words and the
+//     fused predicate's column values (OP != 0: `pred[j] OP scalar` is AND-ed into the row's selection bit, so the
+//     FilterExec below the join writes no bitmap and the probe reads none back) -- is issued before the first wait;
+//  2. the bitmap words.  With all eight keys of every lane known, one ballot decides how: clustered probe keys (a fact
+//     table stored in key order) put the wave's 512 keys inside one run of 64 bitmap words, which the wave loads once,
+//     coalesced, from the first key of its chunk and reads with ds_bpermute; any other wave (random keys) issues no
+//     window load and every lane gathers its eight words back to back behind one wait -- rows that are not selected
+//     or out of range read word 0.  The branch is wave-uniform, so neither side's loads are split across exec masks.
+// The structure before this one loaded the window unconditionally after the first key and gathered per pair of rows
+// behind a full wait: a random-key wave paid six round trips in a row.  Measured on TPC-H SF100 Q3:
+// 600 M clustered Int64 keys with `l_shipdate > date` fused 1.18 ms (compare 0.41 + probe 1.02 ms before); 150 M random
+// keys over a 1.9 MB bitmap with `o_orderdate < date` fused 0.52 ms (0.13 + 0.51 before): that launch is bound by the
+// L1's line fills, one per gathered key, which the load order does not change.  The step: 3.36 -> 2.95 ms, 3.27 ms
+// with the filters left to FilterExec (option join_probe_fused_filter = 0), i.e. the load order alone.
+// Two chunks per wave (the second chunk's loads in flight while the first resolves: 86 VGPRs, occupancy 5) lost 4 %
+// of the step on both probes and is not kept.
+template <int OP, typename P> __device__ inline bool probe_pred(P x, P s) {
+  switch (OP) { case 0: return true; case DFGPU_OP_EQ: return x == s; case DFGPU_OP_NEQ: return x != s; case DFGPU_OP_LT: return x < s;
+    case DFGPU_OP_LTEQ: return x <= s; case DFGPU_OP_GT: return x > s; default: return x >= s; }
+}
+template <typename T, typename P, int OP, bool HAS_MASK, bool HAS_VALID, bool FULL>
+__device__ inline void probe_match_chunk(const T* keys, const uint64_t* key_valid, const uint64_t* mask, const P* pred, P ps, int64_t n, int64_t kmin, uint64_t range,
                                          const uint64_t* bitmap, uint64_t* match_bits, int64_t base, int lane) {
-  // Every load of the chunk that does not depend on another is issued before the first wait: the four 16-byte key loads and the four selection words (round 4: the kernel
-  // used to load keys[base] on its own, wait, and only then issue the rest -- two memory round trips per wave in a row -- and fetched every selection word inside the loop
-  // behind the previous iteration's store).  The window's first key is lane 0's first key.
-  T k[PM_ROWS / 2][2];
+  constexpr int PAIRS = PM_ROWS / 2;
+  T k[PAIRS][2]; P pv[PAIRS][2]; uint64_t sw[PAIRS];
 #pragma unroll
-  for (int r = 0; r < PM_ROWS / 2; r++) {                      // lane l owns rows base + 128 r + 2l, +1
+  for (int r = 0; r < PAIRS; r++) {                            // lane l owns rows base + 128 r + 2l, +1
     int64_t j = base + r * 2 * WAVE + 2 * lane;
-    if (FULL || j + 1 < n) { struct alignas(2 * sizeof(T)) P { T a, b; }; P p = *(const P*)(keys + j); k[r][0] = p.a; k[r][1] = p.b; }
+    if (FULL || j + 1 < n) { struct alignas(2 * sizeof(T)) K2 { T a, b; }; K2 p = *(const K2*)(keys + j); k[r][0] = p.a; k[r][1] = p.b; }
     else { k[r][0] = j < n ? keys[j] : (T)0; k[r][1] = 0; }
   }
-  uint64_t mws[PM_ROWS / 2];
+  if (OP != 0) {
 #pragma unroll
-  for (int r = 0; r < PM_ROWS / 2; r++) { int64_t j = base + r * 2 * WAVE + 2 * lane; mws[r] = (HAS_MASK && (FULL || j < n)) ? mask[j >> 6] >> (j & 63) : 3ull; }
-  uint64_t d0 = (uint64_t)((int64_t)k[0][0] - kmin);           // lane 0: row `base` (the caller guarantees base < n)
-  d0 = (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)d0) | ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(d0 >> 32)) << 32);
-  int64_t w0i = d0 < range ? (int64_t)(d0 >> 6) : 0;
-  uint64_t win = (uint64_t)(w0i + lane) * 64 < range ? bitmap[w0i + lane] : 0ull;
+    for (int r = 0; r < PAIRS; r++) {
+      int64_t j = base + r * 2 * WAVE + 2 * lane;
+      if (FULL || j + 1 < n) { struct alignas(2 * sizeof(P)) P2 { P a, b; }; P2 p = *(const P2*)(pred + j); pv[r][0] = p.a; pv[r][1] = p.b; }
+      else { pv[r][0] = j < n ? pred[j] : ps; pv[r][1] = ps; }
+    }
+  }
+  // j is even and base a multiple of 512: rows j and j + 1 are bits (j & 63), +1 of one word
 #pragma unroll
-  for (int r = 0; r < PM_ROWS / 2; r++) {
+  for (int r = 0; r < PAIRS; r++) {
     int64_t j = base + r * 2 * WAVE + 2 * lane;
-    const uint64_t mw = mws[r];
-    bool h[2];
+    uint64_t w = 3ull;
+    if (HAS_MASK && (FULL || j < n)) w &= mask[j >> 6] >> (j & 63);
+    if (HAS_VALID && (FULL || j < n)) w &= key_valid[j >> 6] >> (j & 63);
+    sw[r] = w;
+  }
+  uint64_t d0 = (uint64_t)((int64_t)k[0][0] - kmin);           // lane 0: row `base` (the caller guarantees base < n); the window starts at its word
+  d0 = (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)d0) | ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(d0 >> 32)) << 32);
+  const int64_t w0i = d0 < range ? (int64_t)(d0 >> 6) : 0;
+  uint64_t d[PAIRS][2]; bool go[PAIRS][2]; bool inwin = true;
+#pragma unroll
+  for (int r = 0; r < PAIRS; r++) {
+    int64_t j = base + r * 2 * WAVE + 2 * lane;
 #pragma unroll
     for (int e = 0; e < 2; e++) {
-      uint64_t d = (uint64_t)((int64_t)k[r][e] - kmin);
-      bool go = (FULL || j + e < n) && ((mw >> e) & 1) && (!HAS_VALID || valid_at(key_valid, j + e)) && d < range;
-      int64_t rel = (int64_t)(d >> 6) - w0i;
-      uint64_t word = __shfl(win, (int)(rel & 63), 64);
-      if (go && (rel < 0 || rel >= WAVE)) word = bitmap[d >> 6];
-      h[e] = go && ((word >> (d & 63)) & 1ull);
+      d[r][e] = (uint64_t)((int64_t)k[r][e] - kmin);
+      go[r][e] = (bool)((int)(FULL || j + e < n) & (int)((sw[r] >> e) & 1) & (int)probe_pred<OP, P>(pv[r][e], ps) & (int)(d[r][e] < range));      // `&`: a short circuit would sink the predicate load behind the selection bit
+      int64_t rel = (int64_t)(d[r][e] >> 6) - w0i;
+      inwin = inwin && (!go[r][e] || (rel >= 0 && rel < WAVE));
     }
-    uint64_t be = ballot64(h[0]), bo = ballot64(h[1]);           // wave-uniform: the interleave below runs on the scalar unit
+  }
+  uint64_t word[PAIRS][2];
+  if (ballot64(!inwin) == 0) {            // every live key of the wave inside the 64-word window (also: no live key at all -- range 0 loads nothing)
+    uint64_t win = (uint64_t)(w0i + lane) * 64 < range ? bitmap[w0i + lane] : 0ull;
+#pragma unroll
+    for (int r = 0; r < PAIRS; r++)
+#pragma unroll
+      for (int e = 0; e < 2; e++) word[r][e] = __shfl(win, (int)(((int64_t)(d[r][e] >> 6) - w0i) & 63), 64);
+  } else {                                // some lane has a live key: range > 0, word 0 exists
+#pragma unroll
+    for (int r = 0; r < PAIRS; r++)
+#pragma unroll
+      for (int e = 0; e < 2; e++) word[r][e] = bitmap[go[r][e] ? d[r][e] >> 6 : 0];
+  }
+#pragma unroll
+  for (int r = 0; r < PAIRS; r++) {
+    bool h0 = go[r][0] && ((word[r][0] >> (d[r][0] & 63)) & 1ull), h1 = go[r][1] && ((word[r][1] >> (d[r][1] & 63)) & 1ull);
+    uint64_t be = ballot64(h0), bo = ballot64(h1);               // wave-uniform: the interleave below runs on the scalar unit
     uint64_t w0 = spread32(be) | (spread32(bo) << 1), w1 = spread32(be >> 32) | (spread32(bo >> 32) << 1);
     int64_t wbase = (base >> 6) + 2 * r;
     if (lane == 0) { if (FULL || base + r * 2 * WAVE < n) match_bits[wbase] = w0; if (FULL || base + r * 2 * WAVE + WAVE < n) match_bits[wbase + 1] = w1; }
   }
 }
-template <typename T, bool HAS_MASK, bool HAS_VALID>
-__global__ void __launch_bounds__(BLOCK) k_probe_match_bitmap(const T* keys, const uint64_t* key_valid, const uint64_t* mask, int64_t n, int64_t kmin, uint64_t range,
+// OP: 0 = no predicate (pred unused, P = T), else the DFGPU_OP_* comparison of the fused predicate `pred[j] OP ps`
+template <typename T, typename P, int OP, bool HAS_MASK, bool HAS_VALID>
+__global__ void __launch_bounds__(BLOCK) k_probe_match_bitmap(const T* keys, const uint64_t* key_valid, const uint64_t* mask, const P* pred, P ps, int64_t n, int64_t kmin, uint64_t range,
                                                               const uint64_t* bitmap, uint64_t* match_bits) {
   int lane = lane_id();
   int64_t base = ((int64_t)blockIdx.x * (BLOCK / WAVE) + (threadIdx.x >> 6)) * (WAVE * PM_ROWS);
-  if (base + WAVE * PM_ROWS <= n) probe_match_chunk<T, HAS_MASK, HAS_VALID, true>(keys, key_valid, mask, n, kmin, range, bitmap, match_bits, base, lane);
-  else if (base < n) probe_match_chunk<T, HAS_MASK, HAS_VALID, false>(keys, key_valid, mask, n, kmin, range, bitmap, match_bits, base, lane);
+  if (base + WAVE * PM_ROWS <= n) probe_match_chunk<T, P, OP, HAS_MASK, HAS_VALID, true>(keys, key_valid, mask, pred, ps, n, kmin, range, bitmap, match_bits, base, lane);
+  else if (base < n) probe_match_chunk<T, P, OP, HAS_MASK, HAS_VALID, false>(keys, key_valid, mask, pred, ps, n, kmin, range, bitmap, match_bits, base, lane);
 }
 // ---- probe pass 2: the matched probe rows (ascending) look their key group up; unique builds emit the build row directly
 __global__ void __launch_bounds__(BLOCK) k_probe_lookup(KeySet bks, KeySet pks, const uint32_t* rows, int64_t m, int null_eq, int force_zero,
@@ -770,9 +813,33 @@ static void lookup_rank(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_a
 #undef LR
   KERNEL_CHECK();
 }
+// a `column <op> scalar` predicate handed down by the FilterExec below the join, evaluated inside the bitmap probe (k_probe_match_bitmap): op 0 = none
+struct ProbePred { const dfgpu_array* col = nullptr; int op = 0; int64_t scalar = 0; };
+// what the fused probe kernel is instantiated for: Int32 / Date32 / Int64 keys without validity, an Int32 / Date32 / Int64 predicate column without validity, the six comparisons
+static bool probe_pred_ok(const dfgpu_join_table* t, const dfgpu_array* pk, const ProbePred& pp) {
+  auto w48 = [](int32_t ty) { return ty == DFGPU_INT32 || ty == DFGPU_DATE32 || ty == DFGPU_INT64; };
+  return pp.col && pp.op >= DFGPU_OP_EQ && pp.op <= DFGPU_OP_GTEQ && w48(pp.col->type) && !pp.col->validity && pp.col->length == pk->length && w48(pk->type) && !pk->validity &&
+         pk->type == t->keys[0]->type && (t->bitmap || (t->lazy_row_slot && t->range <= (uint64_t)pk->length * 16));
+}
+// the kernel reads two values per load (2 x width aligned): a zero-copy slice at an odd row offset (dfgpu_array_slice) is copied once
+static const void* pair_aligned(dfgpu_ctx* ctx, const dfgpu_array* a, int64_t n, BufferPtr& keep) {
+  const void* p = a->values->ptr; const size_t w = (size_t)type_width(a->type);
+  if ((uintptr_t)p % (2 * w)) { keep = alloc_buffer(ctx, (size_t)n * w); HIP_CHECK(hipMemcpyAsync(keep->ptr, p, (size_t)n * w, hipMemcpyDeviceToDevice, ctx->stream)); p = keep->ptr; }
+  return p;
+}
+template <typename T, typename P>
+static void launch_probe_fused(dfgpu_ctx* ctx, int op, dim3 grid, const T* keys, const uint64_t* mk, const P* pred, P ps, int64_t n, int64_t kmin, uint64_t range, const uint64_t* bitmap, uint64_t* match_bits) {
+  switch (op) {
+#define PF_CASE(OP) case OP: if (mk) hipLaunchKernelGGL((k_probe_match_bitmap<T, P, OP, true, false>), grid, dim3(BLOCK), 0, ctx->stream, keys, (const uint64_t*)nullptr, mk, pred, ps, n, kmin, range, bitmap, match_bits); \
+                             else hipLaunchKernelGGL((k_probe_match_bitmap<T, P, OP, false, false>), grid, dim3(BLOCK), 0, ctx->stream, keys, (const uint64_t*)nullptr, mk, pred, ps, n, kmin, range, bitmap, match_bits); break;
+    PF_CASE(DFGPU_OP_EQ) PF_CASE(DFGPU_OP_NEQ) PF_CASE(DFGPU_OP_LT) PF_CASE(DFGPU_OP_LTEQ) PF_CASE(DFGPU_OP_GT) PF_CASE(DFGPU_OP_GTEQ)
+#undef PF_CASE
+    default: fail(DFGPU_INTERNAL, "fused probe: operator %d", op);
+  }
+}
 // pass 1 (one match bit per probe row) by the membership bitmap; a lazy one is built here by the first probe batch large enough to pay for it.
-// false = no bitmap this probe column can use: nothing launched.
-static bool match_bits_by_bitmap(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* pk, int64_t n, const uint64_t* mk, uint64_t* match_bits) {
+// false = no bitmap this probe column can use: nothing launched.  A predicate (pp.op != 0) must have passed probe_pred_ok, which implies a usable bitmap.
+static bool match_bits_by_bitmap(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* pk, int64_t n, const uint64_t* mk, uint64_t* match_bits, const ProbePred& pp = ProbePred()) {
   const dfgpu_array* key0 = t->keys[0];
   if (pk->type != key0->type) return false;      // same physical integer type, no dictionary
   if (t->lazy_row_slot && t->range <= (uint64_t)n * 16) {
@@ -785,13 +852,21 @@ static bool match_bits_by_bitmap(dfgpu_ctx* ctx, const dfgpu_join_table* t, cons
   }
   if (!t->bitmap) return false;
   KernelTimer kt_(ctx, "k_probe_match_bitmap");
-  int64_t rows_per_block = (int64_t)BLOCK * PM_ROWS;
+  const dim3 grid(grid_for(n, BLOCK * PM_ROWS));
   const uint64_t* kvp = pk->validity ? (const uint64_t*)pk->validity->ptr : nullptr;
-  // the kernel reads two keys per load (2 x sizeof(T) aligned): a zero-copy slice at an odd row offset (dfgpu_array_slice) is copied once
-  const void* kptr = pk->values->ptr; BufferPtr aligned_keys; const size_t kw = (size_t)type_width(pk->type);
-  if ((uintptr_t)kptr % (2 * kw)) { aligned_keys = alloc_buffer(ctx, (size_t)n * kw); HIP_CHECK(hipMemcpyAsync(aligned_keys->ptr, kptr, (size_t)n * kw, hipMemcpyDeviceToDevice, ctx->stream)); kptr = aligned_keys->ptr; }
-#define PM_LAUNCH(HM, HV) DFGPU_INT_KEY_DISPATCH(pk->type, hipLaunchKernelGGL((k_probe_match_bitmap<T, HM, HV>), dim3(grid_for(n, (int)rows_per_block)), dim3(BLOCK), 0, ctx->stream, (const T*)kptr, \
-                                                          kvp, mk, n, t->key_min, t->range, (const uint64_t*)t->bitmap->ptr, match_bits))
+  BufferPtr aligned_keys, aligned_pred; const void* kptr = pair_aligned(ctx, pk, n, aligned_keys);
+  const uint64_t* bm = (const uint64_t*)t->bitmap->ptr;
+  if (pp.op) {
+    const void* pptr = pair_aligned(ctx, pp.col, n, aligned_pred);
+    const bool k8 = pk->type == DFGPU_INT64, p8 = pp.col->type == DFGPU_INT64;
+    if (k8 && p8) launch_probe_fused<int64_t, int64_t>(ctx, pp.op, grid, (const int64_t*)kptr, mk, (const int64_t*)pptr, pp.scalar, n, t->key_min, t->range, bm, match_bits);
+    else if (k8) launch_probe_fused<int64_t, int32_t>(ctx, pp.op, grid, (const int64_t*)kptr, mk, (const int32_t*)pptr, (int32_t)pp.scalar, n, t->key_min, t->range, bm, match_bits);
+    else if (p8) launch_probe_fused<int32_t, int64_t>(ctx, pp.op, grid, (const int32_t*)kptr, mk, (const int64_t*)pptr, pp.scalar, n, t->key_min, t->range, bm, match_bits);
+    else launch_probe_fused<int32_t, int32_t>(ctx, pp.op, grid, (const int32_t*)kptr, mk, (const int32_t*)pptr, (int32_t)pp.scalar, n, t->key_min, t->range, bm, match_bits);
+    return true;
+  }
+#define PM_LAUNCH(HM, HV) DFGPU_INT_KEY_DISPATCH(pk->type, hipLaunchKernelGGL((k_probe_match_bitmap<T, T, 0, HM, HV>), grid, dim3(BLOCK), 0, ctx->stream, (const T*)kptr, \
+                                                          kvp, mk, (const T*)nullptr, (T)0, n, t->key_min, t->range, bm, match_bits))
   if (mk && kvp) { PM_LAUNCH(true, true); } else if (mk) { PM_LAUNCH(true, false); } else if (kvp) { PM_LAUNCH(false, true); } else { PM_LAUNCH(false, false); }
 #undef PM_LAUNCH
   return true;
@@ -903,7 +978,8 @@ int64_t dfgpu_join_table_num_rows(const dfgpu_join_table* t) { return t ? t->n_b
 int64_t dfgpu_join_table_memory(const dfgpu_join_table* t) { return t ? t->mem : 0; }
 
 static dfgpu_status join_probe_impl(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* const* probe_keys, int32_t nkeys,
-                                    const dfgpu_array* opt_mask, dfgpu_array** out_build_idx, dfgpu_array** out_probe_idx, bool may_defer, dfgpu_array** out_selection);
+                                    const dfgpu_array* opt_mask, dfgpu_array** out_build_idx, dfgpu_array** out_probe_idx, bool may_defer, dfgpu_array** out_selection,
+                                    const dfgpu::ProbePred* pred = nullptr);
 dfgpu_status dfgpu_join_probe(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* const* probe_keys, int32_t nkeys,
                               const dfgpu_array* opt_mask, dfgpu_array** out_build_idx, dfgpu_array** out_probe_idx) {
   return join_probe_impl(ctx, t, probe_keys, nkeys, opt_mask, out_build_idx, out_probe_idx, false, nullptr);
@@ -916,6 +992,21 @@ dfgpu_status dfgpu_join_probe_deferred(dfgpu_ctx* ctx, const dfgpu_join_table* t
 dfgpu_status dfgpu_join_probe_selection(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* const* probe_keys, int32_t nkeys, const dfgpu_array* opt_mask, dfgpu_array** out_selection) {
   if (!out_selection) return DFGPU_INVALID_ARGUMENT;
   return join_probe_impl(ctx, t, probe_keys, nkeys, opt_mask, nullptr, nullptr, false, out_selection);
+}
+/* see include/dfgpu.h */
+dfgpu_status dfgpu_join_probe_fused(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* const* probe_keys, int32_t nkeys, const dfgpu_array* opt_mask,
+                                    const dfgpu_array* pred_column, int32_t pred_op, const dfgpu_array* pred_scalar, int32_t out_form,
+                                    dfgpu_array** out_build_idx, dfgpu_array** out_probe_idx, dfgpu_array** out_selection) {
+  if (!pred_column || !pred_scalar || out_form < DFGPU_PROBE_PAIRS || out_form > DFGPU_PROBE_SELECTION) return DFGPU_INVALID_ARGUMENT;
+  const bool sel = out_form == DFGPU_PROBE_SELECTION;
+  if (sel && !out_selection) return DFGPU_INVALID_ARGUMENT;
+  dfgpu::ProbePred pp; pp.col = pred_column; pp.op = pred_op;
+  // the scalar as the compare fast path reads it (expr.hip): a host-resident non-NULL value of the column's type; anything else is not a predicate the kernel takes
+  const int32_t pt = pred_column->type;
+  const bool scalar_ok = pred_scalar->type == pt && pred_scalar->length == 1 && pred_scalar->has_host_scalar && pred_scalar->host_scalar_valid && (pt == DFGPU_INT32 || pt == DFGPU_DATE32 || pt == DFGPU_INT64);
+  if (scalar_ok) { if (pt == DFGPU_INT64) memcpy(&pp.scalar, pred_scalar->host_scalar, 8); else { int32_t v; memcpy(&v, pred_scalar->host_scalar, 4); pp.scalar = v; } }
+  else pp.op = 0;                                   // declined below, after the ordinary argument checks
+  return join_probe_impl(ctx, t, probe_keys, nkeys, opt_mask, sel ? nullptr : out_build_idx, sel ? nullptr : out_probe_idx, out_form == DFGPU_PROBE_DEFERRED, sel ? out_selection : nullptr, &pp);
 }
 dfgpu_status dfgpu_join_lookup(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* const* probe_keys, int32_t nkeys, const dfgpu_array* rows, dfgpu_array** out_build_idx) {
   return guard(ctx, [&] {
@@ -936,13 +1027,18 @@ dfgpu_status dfgpu_join_lookup(dfgpu_ctx* ctx, const dfgpu_join_table* t, const 
 // Check the arguments and pack the keys, go partition by partition if the table and batch are for it, else pass 1 (match bits, by bitmap or by hash), then the
 // selection form if it was asked for, or pass 2 (the pairs) by representation
 static dfgpu_status join_probe_impl(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* const* probe_keys, int32_t nkeys,
-                                    const dfgpu_array* opt_mask, dfgpu_array** out_build_idx, dfgpu_array** out_probe_idx, bool may_defer, dfgpu_array** out_selection) {
+                                    const dfgpu_array* opt_mask, dfgpu_array** out_build_idx, dfgpu_array** out_probe_idx, bool may_defer, dfgpu_array** out_selection,
+                                    const dfgpu::ProbePred* pred) {
   return guard(ctx, [&] {
     if (!t || !probe_keys || (!out_selection && (!out_build_idx || !out_probe_idx))) fail(DFGPU_INVALID_ARGUMENT, "join_probe: null argument");
     check_key_types(t, probe_keys, nkeys);
     // the selection form (dfgpu_join_probe_selection) and the deferred probe: only for the tables dfgpu_join_lookup can look up in -- decided before any pass runs
     const bool lookup_ok = rank_lookup_ok(t, probe_keys, nkeys);
     if (out_selection && !lookup_ok) fail(DFGPU_NOT_IMPLEMENTED, "join_probe_selection: only a unique rank-indexed build probed by one integer key column of the build's type without NULLs");
+    // a fused predicate (dfgpu_join_probe_fused): only the bitmap probe evaluates one -- decided before any pass runs, like the selection form
+    if (pred && (nkeys != 1 || t->pack_n || !probe_pred_ok(t, probe_keys[0], *pred) || pj_probe_eligible(ctx, t, probe_keys, nkeys, probe_keys[0]->length)))
+      fail(DFGPU_NOT_IMPLEMENTED, "join_probe_fused: only a table with a membership bitmap probed by one Int32 / Date32 / Int64 key column without NULLs, and a predicate `column <op> scalar` "
+                                  "(op EQ..GTEQ) over an Int32 / Date32 / Int64 column without NULLs");
     ArrayHolder packed_probe; const dfgpu_array* pk1 = nullptr;
     if (t->pack_n) {
       for (int c = 0; c < nkeys; c++) if (probe_keys[c]->type == DFGPU_DICTIONARY || probe_keys[c]->length != probe_keys[0]->length) fail(DFGPU_NOT_IMPLEMENTED, "probe of a packed multi-key table with dictionary-encoded keys");
@@ -959,7 +1055,7 @@ static dfgpu_status join_probe_impl(dfgpu_ctx* ctx, const dfgpu_join_table* t, c
       return;
     }
     BufferPtr match_bits = alloc_buffer(ctx, bitmap_bytes(n), n == 0);
-    const bool use_bitmap = n && match_bits_by_bitmap(ctx, t, probe_keys[0], n, mk, (uint64_t*)match_bits->ptr);
+    const bool use_bitmap = n && match_bits_by_bitmap(ctx, t, probe_keys[0], n, mk, (uint64_t*)match_bits->ptr, pred ? *pred : ProbePred());
     const BufferPtr found_slot = n && !use_bitmap ? match_bits_by_hash(ctx, t, probe_keys, nkeys, pks, n, mk, (uint64_t*)match_bits->ptr) : nullptr;
     KERNEL_CHECK();
     if (out_selection) {            // the match bits ARE the answer: a Boolean column over the probe rows (bits of a partial last word beyond n are zero)

@@ -356,6 +356,20 @@ class JoinTable:
         self.ctx.check(st)
         return Array(self.ctx, out)
 
+    def probe_fused(self, keys: Sequence[Array], pred_column: Array, pred_op: int, pred_scalar: Array, mask: Optional[Array] = None, form: int = 0):
+        """dfgpu_join_probe_fused: the probe with `pred_column <pred_op> pred_scalar` folded in.  form 0 -> (build indices, probe indices), 1 -> the same with build
+        indices None when the table defers them, 2 -> the Boolean selection; None when the table or the predicate does not take the fused form"""
+        hs, n = capi.handle_array([a.h.value for a in keys])
+        ob, op, sel = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        st = self.ctx.lib.dfgpu_join_probe_fused(self.ctx.h, self.h, hs, n, mask.h if mask is not None else None, pred_column.h, pred_op, pred_scalar.h, form,
+                                                 C.byref(ob), C.byref(op), C.byref(sel))
+        if st == 4:
+            return None
+        self.ctx.check(st)
+        if form == 2:
+            return Array(self.ctx, sel)
+        return (Array(self.ctx, ob) if ob.value else None), Array(self.ctx, op)
+
     def lookup(self, keys: Sequence[Array], rows: Optional[Array] = None) -> Array:
         """dfgpu_join_lookup: build rows of the probe rows `rows` (UInt32, known to match; None = every row of `keys`)"""
         hs, n = capi.handle_array([a.h.value for a in keys])

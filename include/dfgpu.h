@@ -116,6 +116,8 @@ DFGPU_API dfgpu_status dfgpu_ctx_synchronize(dfgpu_ctx *ctx);
  * polls -- instead of a device-to-host copy followed by a stream synchronisation (same values; the switch exists for A/B runs);
  * "join_selection_output" (1/0) == let the plan layer's HashJoinExec answer an Inner join whose build side contributes key columns only with the probe batch under a selection
  * (dfgpu_join_probe_selection) when the operator above fuses selections (rows and row order identical); "join_lazy_build_rows" (1/0) == build rows of a deferred probe looked up on demand;
+ * "join_probe_fused_filter" (1/0) == let the plan layer's FilterExec hand a `column <op> literal` predicate over a device-sized batch to the HashJoinExec it feeds the probe
+ * side of, which evaluates it inside the probe (dfgpu_join_probe_fused) instead of through a bitmap; 0 = the filter evaluates at once (rows and row order identical);
  * "group_lazy_keys" (1/0) == a run-numbered first batch keeps its group keys as (key columns, first rows) until somebody needs them stored (dfgpu_groups_emit_deferred);
  * "agg_order_inverse_map" (1/0) == first-seen order of millions of pre-aggregated partial rows through an inverse map over the input rows instead of sort passes (same order);
  * "sort_fused_small_passes" (1/0) == sorts below 2^20 rows fold every pass's offset scan into its scatter (identical indices);
@@ -295,6 +297,18 @@ DFGPU_API dfgpu_status dfgpu_join_probe_deferred(dfgpu_ctx *ctx, const dfgpu_joi
  * selection -- no index vector is built and nothing is read back (≙ build_batch_from_indices with probe indices = the set bits, joins/utils.rs:1180-1230). */
 DFGPU_API dfgpu_status dfgpu_join_probe_selection(dfgpu_ctx *ctx, const dfgpu_join_table *table, const dfgpu_array *const *probe_keys, int32_t nkeys,
                                                   const dfgpu_array *opt_mask, dfgpu_array **out_selection);
+/* A probe with the scan filter `pred_column <pred_op> pred_scalar` folded in: probe row i takes part when opt_mask selects it AND the predicate holds for it; the predicate is
+ * evaluated inside the probe's own pass over the keys, so no predicate bitmap is written or read.  out_form picks the answer: DFGPU_PROBE_PAIRS == dfgpu_join_probe
+ * (out_build_idx, out_probe_idx), DFGPU_PROBE_DEFERRED == dfgpu_join_probe_deferred (same two), DFGPU_PROBE_SELECTION == dfgpu_join_probe_selection (out_selection); the outputs
+ * of the other forms are not touched.  The answer is exactly that of the unfused call with opt_mask AND-ed with dfgpu_binary(pred_op, pred_column, pred_scalar).
+ * Taken only when the table has (or builds on this call) a membership bitmap the probe column can use -- one Int32 / Date32 / Int64 key column of the build key's type without
+ * validity -- and the predicate is one the kernel is instantiated for: pred_op DFGPU_OP_EQ .. DFGPU_OP_GTEQ, pred_column Int32 / Date32 / Int64 without validity and as long as
+ * the keys, pred_scalar a non-NULL scalar (length 1) of pred_column's type.  Anything else -- hash and partitioned tables, narrow or nullable keys, a selection form the table
+ * cannot give -- answers DFGPU_NOT_IMPLEMENTED before launching anything, and the caller evaluates the predicate into opt_mask and probes the ordinary way. */
+enum { DFGPU_PROBE_PAIRS = 0, DFGPU_PROBE_DEFERRED = 1, DFGPU_PROBE_SELECTION = 2 };
+DFGPU_API dfgpu_status dfgpu_join_probe_fused(dfgpu_ctx *ctx, const dfgpu_join_table *table, const dfgpu_array *const *probe_keys, int32_t nkeys, const dfgpu_array *opt_mask,
+                                              const dfgpu_array *pred_column, int32_t pred_op, const dfgpu_array *pred_scalar, int32_t out_form,
+                                              dfgpu_array **out_build_idx, dfgpu_array **out_probe_idx, dfgpu_array **out_selection);
 DFGPU_API dfgpu_status dfgpu_join_lookup(dfgpu_ctx *ctx, const dfgpu_join_table *table, const dfgpu_array *const *probe_keys, int32_t nkeys, const dfgpu_array *rows,
                                          dfgpu_array **out_build_idx);
 /* ≙ visited_left_side.set_bit for every joined build index (hash_join.rs:1274-1278). */
