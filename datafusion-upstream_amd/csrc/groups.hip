@@ -717,6 +717,7 @@ static bool groups_intern_dense(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_arr
   const int fgrid = grid_for(n, BLOCK * DENSE_ROWS, ctx->num_cus * 8); const int64_t len1 = nkeys == 2 ? dc.c[1].dict_len : 1;
   bool tab = fast && dc.c[0].dict_len * len1 <= DENSE_MAX && dsize <= 65535;
   for (int c = 0; c < nkeys && tab; c++) tab = (((uintptr_t)dc.c[c].keys) & 15) == 0;
+  KernelTimer kt_first_(ctx, !fast ? "k_dense_first" : tab ? "k_dense_first_tab" : "k_dense_first_fast");
   if (fast) dense_fast_dispatch(kt0, nkeys, mk != nullptr, [&](auto s) { using S = decltype(s);
     if (tab) hipLaunchKernelGGL((k_dense_first_tab<typename S::Key, S::nc, S::mask>), dim3(grid_for(n, BLOCK * 4, ctx->num_cus * 8)), block, 0, ctx->stream, dc, n, mk, dmp, (uint32_t*)first->ptr, (int)dsize, (int)len1);
     else hipLaunchKernelGGL((k_dense_first_fast<typename S::Key, S::nc, S::mask>), dim3(fgrid), block, 0, ctx->stream, dc, n, mk, dmp, (uint32_t*)first->ptr, (int)dsize); });

@@ -22,7 +22,10 @@ void hash_keys_device(dfgpu_ctx* ctx, const dfgpu_array* const* cols, int32_t k,
   int64_t n = cols[0]->length;
   if (n == 0) return;
   const ColView& c = ks.c[0];
-  if (k == 1 && !ctx->force_hash_collisions && !c.keys && !c.validity && (c.type == DFGPU_INT64 || c.type == DFGPU_UINT64 || c.type == DFGPU_FLOAT64) && ((uintptr_t)c.values & 15) == 0)
+  // two keys per load: a zero-copy slice that starts at an odd row (dfgpu_array_slice) is 8 but not 16 bytes aligned and takes the row kernel
+  const bool pairs = k == 1 && !ctx->force_hash_collisions && !c.keys && !c.validity && (c.type == DFGPU_INT64 || c.type == DFGPU_UINT64 || c.type == DFGPU_FLOAT64) && ((uintptr_t)c.values & 15) == 0;
+  KernelTimer kt_(ctx, pairs ? "k_hash_i64" : "k_hash_rows");
+  if (pairs)
     hipLaunchKernelGGL(k_hash_i64, dim3(grid_for((n + 1) / 2, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)c.values, n, seed, out);
   else
     hipLaunchKernelGGL(k_hash_rows, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, ks, n, seed, ctx->force_hash_collisions ? 1 : 0, out);

@@ -193,6 +193,12 @@ class Context:
         self.check(self.lib.dfgpu_mask_to_indices(self.h, mask.h, C.byref(out)))
         return self._wrap(out)
 
+    def mask_count(self, mask: "Array") -> int:
+        """dfgpu_mask_count: number of rows of a Boolean column that are true and not NULL"""
+        out = C.c_int64(0)
+        self.check(self.lib.dfgpu_mask_count(self.h, mask.h, C.byref(out)))
+        return int(out.value)
+
     # ---- a12
     def binary(self, op: int, lhs: "Array", rhs: "Array", lhs_scalar: bool = False, rhs_scalar: bool = False) -> "Array":
         out = C.c_void_p()

@@ -199,7 +199,23 @@ DFGPU_API int32_t dfgpu_array_is_identity(const dfgpu_array *a);
 /* UInt32 0, 1, .., length - 1 (flagged as the identity): group ids of rows that are one group each, in order */
 DFGPU_API dfgpu_status dfgpu_array_iota(dfgpu_ctx *ctx, int64_t length, dfgpu_array **out);
 DFGPU_API int64_t dfgpu_array_null_count(dfgpu_ctx *ctx, const dfgpu_array *a);   /* computes if unknown */
-/* RecordBatch::slice: zero copy when offset % 64 == 0 (batch_size 8192 chunks), otherwise a copy. */
+/* RecordBatch::slice.  A column without a bitmap (no validity buffer, not Boolean) is sliced without a copy at every row; one with a bitmap when offset % 64 == 0
+ * (batch_size 8192 chunks), otherwise it is copied, because a bitmap cannot be re-based at bit granularity.  The zero-copy result is a VIEW: its buffers point into
+ * the buffers of `a`, which it keeps alive.
+ *
+ * What a consumer of a dfgpu_array may assume -- every entry point of this header takes views wherever it takes arrays:
+ *   - the values buffer is aligned to the element width only (an Int64 column that starts at an odd row: 8 bytes, not 16; Int8 / Int16: 1 / 2 bytes).  A kernel
+ *     that loads several elements at once checks the pointer and keeps a branch for the other case (hash_keys_device), or declines the shape before it launches
+ *     (dfgpu_acc_update_batch_fused answers DFGPU_NOT_IMPLEMENTED and the caller evaluates node by node);
+ *   - validity and Boolean buffers start on an 8-byte word, and every word that holds one of the `length` bits can be read whole; the bits past `length` in the
+ *     last word are UNDEFINED (the parent's live bits), never to be counted, selected or copied out;
+ *   - Utf8: offsets[0] is arbitrary (the first row's bytes start at values + offsets[0]), `values` is the parent's base pointer, and values_bytes is an upper bound
+ *     of offsets[length] - offsets[0], not the size of the window;
+ *   - null_count may be -1 (unknown until dfgpu_array_null_count measures it), also when the window holds no NULL or only NULLs; a validity buffer does not imply a NULL;
+ *   - a dictionary is shared with the parent: entries no code of the window refers to are normal.
+ * dfgpu_array_wrap_device is deliberately stricter than that: memory handed in from outside must be 8-byte aligned in every buffer, whatever the element width,
+ * because validity and Boolean words are read as 64-bit words and the rule is cheap to state to a caller.  Views made here from such an array may then be aligned to
+ * the element width only; a view is not something to hand back to dfgpu_array_wrap_device. */
 DFGPU_API dfgpu_status dfgpu_array_slice(dfgpu_ctx *ctx, const dfgpu_array *a, int64_t offset, int64_t length, dfgpu_array **out);
 /* concat_batches per column (hash_join.rs:764, coalesce_batches.rs:198-260, sorts/sort.rs:505). */
 DFGPU_API dfgpu_status dfgpu_concat(dfgpu_ctx *ctx, const dfgpu_array *const *arrays, int32_t n, dfgpu_array **out);

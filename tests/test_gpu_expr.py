@@ -15,8 +15,30 @@ CMP = ["=", "!=", "<", "<=", ">", ">=", "IS DISTINCT FROM", "IS NOT DISTINCT FRO
 OPCODE = {"+": 0, "-": 1, "*": 2, "/": 3, "%": 4, "=": 10, "!=": 11, "<": 12, "<=": 13, ">": 14, ">=": 15, "IS DISTINCT FROM": 16, "IS NOT DISTINCT FROM": 17, "AND": 20, "OR": 21}
 
 
+RAGGED = [0, 1, 63, 64, 65, 127, 4097]          # bitmap results: no word, one bit, a word less one bit, a full word, a word and a bit, two words less one, a ragged 65th word
+
+
+def exported(ctx, out):
+    """device result -> pyarrow.  A Boolean result is first checked against its own export, which the caller compares with the oracle: null_count, dfgpu_mask_count, and the
+    result as the mask of mask_to_indices and filter -- whatever its last word holds past `length` must not show."""
+    a = out.to_arrow()
+    if pa.types.is_boolean(a.type):
+        truth = np.asarray(a.fill_null(False), dtype=bool)
+        assert out.null_count == a.null_count
+        assert ctx.mask_count(out) == int(truth.sum())
+        assert np.array_equal(ctx.mask_to_indices(out).to_numpy(), np.flatnonzero(truth).astype(np.uint32))
+        rows = ctx.from_arrow(pa.array(np.arange(len(a), dtype=np.int64)))
+        assert np.array_equal(ctx.filter(rows, out).to_numpy(), np.flatnonzero(truth))
+    return a
+
+
 def dev_binary(ctx, op, l, r, ls=False, rs=False):
-    return ctx.binary(OPCODE[op], ctx.from_arrow(l), ctx.from_arrow(r), ls, rs).to_arrow()
+    return exported(ctx, ctx.binary(OPCODE[op], ctx.from_arrow(l), ctx.from_arrow(r), ls, rs))
+
+
+def scalar_from(r, kind):
+    """one non-NULL row of `r` to serve as a literal; for a column without one (no row, or NULLs only) a value of its kind"""
+    return r.drop_null().slice(0, 1) if r.null_count < len(r) else rand_array(kind, 1, 0.0, np.random.default_rng(1))
 
 
 def same(a, b):
@@ -30,14 +52,24 @@ def same(a, b):
 @pytest.mark.parametrize("kind", ["int8", "int32", "int64", "uint16", "uint64", "float32", "float64", "date32", "decimal", "utf8", "bool", "dict"])
 @pytest.mark.parametrize("op", CMP)
 def test_comparisons(ctx, kind, op):
-    n = 3000
+    comparisons(ctx, kind, op, 3000)
+
+
+@pytest.mark.parametrize("kind", ["int8", "int32", "int64", "uint16", "uint64", "float32", "float64", "date32", "decimal", "utf8", "bool", "dict"])
+@pytest.mark.parametrize("op", CMP)
+@pytest.mark.parametrize("n", RAGGED)
+def test_comparisons_ragged_lengths(ctx, kind, op, n):
+    comparisons(ctx, kind, op, n)
+
+
+def comparisons(ctx, kind, op, n):
     l, r = rand_array(kind, n), rand_array(kind, n)
     if kind in ("utf8", "dict", "bool", "int8"):      # make equal pairs likely
         pass
     else:
         r = pa.array([lv if i % 3 == 0 else rv for i, (lv, rv) in enumerate(zip(l.to_pylist(), r.to_pylist()))], type=r.type)
     assert same(dev_binary(ctx, op, l, r), po.binary(op, l, r))
-    s = r.slice(5, 1) if r.slice(5, 1).null_count == 0 else r.drop_null().slice(0, 1)
+    s = r.slice(5, 1) if n > 5 and r.slice(5, 1).null_count == 0 else scalar_from(r, kind)
     assert same(dev_binary(ctx, op, l, s, rs=True), po.binary(op, l, s, r_scalar=True))
     assert same(dev_binary(ctx, op, s, l, ls=True), po.binary(op, s, l, l_scalar=True))
 
@@ -52,22 +84,44 @@ def test_float_total_order_nan_and_zero(ctx):
 @pytest.mark.parametrize("kind", ["int8", "int16", "int32", "int64", "uint8", "uint32", "uint64", "float32", "float64"])
 @pytest.mark.parametrize("op", ["+", "-", "*"])
 def test_wrapping_arithmetic(ctx, kind, op):
-    l, r = rand_array(kind, 4000), rand_array(kind, 4000)
+    wrapping_arithmetic(ctx, kind, op, 4000)
+
+
+@pytest.mark.parametrize("kind", ["int8", "int16", "int32", "int64", "uint8", "uint32", "uint64", "float32", "float64"])
+@pytest.mark.parametrize("op", ["+", "-", "*"])
+@pytest.mark.parametrize("n", RAGGED)
+def test_wrapping_arithmetic_ragged_lengths(ctx, kind, op, n):
+    wrapping_arithmetic(ctx, kind, op, n)
+
+
+def wrapping_arithmetic(ctx, kind, op, n):
+    l, r = rand_array(kind, n), rand_array(kind, n)
     assert same(dev_binary(ctx, op, l, r), po.binary(op, l, r))
-    s = r.drop_null().slice(0, 1)
+    s = scalar_from(r, kind)
     assert same(dev_binary(ctx, op, l, s, rs=True), po.binary(op, l, s, r_scalar=True))
 
 
 @pytest.mark.parametrize("kind", ["int32", "int64", "uint32", "float64"])
 @pytest.mark.parametrize("op", ["/", "%"])
 def test_division(ctx, kind, op):
+    division(ctx, kind, op, 3000)
+
+
+@pytest.mark.parametrize("kind", ["int32", "int64", "uint32", "float64"])
+@pytest.mark.parametrize("op", ["/", "%"])
+@pytest.mark.parametrize("n", RAGGED)
+def test_division_ragged_lengths(ctx, kind, op, n):
+    division(ctx, kind, op, n)
+
+
+def division(ctx, kind, op, n):
     import dfgpu
-    l = rand_array(kind, 3000)
-    r = rand_array(kind, 3000)
+    l = rand_array(kind, n)
+    r = rand_array(kind, n)
     if kind != "float64":
         r = pa.array([None if v is None else (v if v != 0 else 1) for v in r.to_pylist()], type=r.type)
     assert same(dev_binary(ctx, op, l, r), po.binary(op, l, r))
-    if kind != "float64":
+    if kind != "float64" and l.null_count < n:          # a zero divisor is an error where a non-NULL dividend meets it
         z = pa.array([0], type=r.type)
         with pytest.raises(dfgpu.DfgpuError) as e:
             dev_binary(ctx, op, l.drop_null(), z, rs=True)
@@ -162,29 +216,48 @@ def test_dictionary_column_vs_plain_scalar_uses_dictionary_predicate(ctx, op):
 
 @pytest.mark.parametrize("op", ["AND", "OR"])
 def test_kleene_logic(ctx, op):
-    l, r = rand_array("bool", 5000, 0.3), rand_array("bool", 5000, 0.3)
+    kleene_logic(ctx, op, 5000)
+
+
+@pytest.mark.parametrize("op", ["AND", "OR"])
+@pytest.mark.parametrize("n", RAGGED)
+def test_kleene_logic_ragged_lengths(ctx, op, n):
+    kleene_logic(ctx, op, n)
+
+
+def kleene_logic(ctx, op, n):
+    l, r = rand_array("bool", n, 0.3), rand_array("bool", n, 0.3)
     assert same(dev_binary(ctx, op, l, r), po.binary(op, l, r))
     for s in [pa.array([True]), pa.array([False]), pa.array([None], type=pa.bool_())]:
         assert same(dev_binary(ctx, op, l, s, rs=True), po.binary(op, l, s, r_scalar=True))
 
 
 def test_not_isnull_negative_inlist(ctx):
-    b = rand_array("bool", 3000, 0.2)
-    assert same(ctx.not_(ctx.from_arrow(b)).to_arrow(), po.not_(b))
+    not_isnull_negative_inlist(ctx, 3000, n_utf8=2000)
+
+
+@pytest.mark.parametrize("n", RAGGED)
+def test_not_isnull_negative_inlist_ragged_lengths(ctx, n):
+    not_isnull_negative_inlist(ctx, n, n_utf8=n)
+
+
+def not_isnull_negative_inlist(ctx, n, n_utf8):
+    b = rand_array("bool", n, 0.2)
+    assert same(exported(ctx, ctx.not_(ctx.from_arrow(b))), po.not_(b))
     for kind in ["int64", "utf8", "dict", "decimal"]:
-        a = rand_array(kind, 3000, 0.3)
-        assert same(ctx.is_null(ctx.from_arrow(a)).to_arrow(), po.is_null(a))
-        assert same(ctx.is_null(ctx.from_arrow(a), True).to_arrow(), po.is_null(a, True))
+        a = rand_array(kind, n, 0.3)
+        assert same(exported(ctx, ctx.is_null(ctx.from_arrow(a))), po.is_null(a))
+        assert same(exported(ctx, ctx.is_null(ctx.from_arrow(a), True)), po.is_null(a, True))
     for kind in ["int32", "int64", "float64", "decimal"]:
-        a = rand_array(kind, 3000, 0.2)
+        a = rand_array(kind, n, 0.2)
         assert same(ctx.negative(ctx.from_arrow(a)).to_arrow(), po.negative(a))
-    a = pa.array(RNG.integers(0, 20, 3000), mask=RNG.random(3000) < 0.1)
+    a = pa.array(RNG.integers(0, 20, n), mask=RNG.random(n) < 0.1)
     for lst in [pa.array([1, 5, 7]), pa.array([1, None, 7]), pa.array([], type=pa.int64())]:
         for neg in (False, True):
-            assert same(ctx.in_list(ctx.from_arrow(a), ctx.from_arrow(lst), neg).to_arrow(), po.in_list(a, lst, neg))
-    u = rand_array("utf8", 2000, 0.2)
+            assert same(exported(ctx, ctx.in_list(ctx.from_arrow(a), ctx.from_arrow(lst), neg)), po.in_list(a, lst, neg))
+    u = rand_array("utf8", n_utf8, 0.2)
     lst = pa.array(["BUILDING0", "ASIA3", "a1"])
-    assert same(ctx.in_list(ctx.from_arrow(u), ctx.from_arrow(lst)).to_arrow(), po.in_list(u, lst))
+    assert same(exported(ctx, ctx.in_list(ctx.from_arrow(u), ctx.from_arrow(lst))), po.in_list(u, lst))
 
 
 CASTS = [("int32", pa.int64()), ("int64", pa.float64()), ("int8", pa.decimal128(10, 2)), ("int64", pa.decimal128(38, 4)), ("decimal", pa.decimal128(20, 4)),
@@ -194,8 +267,18 @@ CASTS = [("int32", pa.int64()), ("int64", pa.float64()), ("int8", pa.decimal128(
 
 @pytest.mark.parametrize("kind,to", [c for c in CASTS if c[1] is not None])
 def test_cast(ctx, kind, to):
+    cast(ctx, kind, to, 3000)
+
+
+@pytest.mark.parametrize("kind,to", [c for c in CASTS if c[1] is not None])
+@pytest.mark.parametrize("n", RAGGED)
+def test_cast_ragged_lengths(ctx, kind, to, n):
+    cast(ctx, kind, to, n)
+
+
+def cast(ctx, kind, to, n):
     import dfgpu
-    a = rand_array(kind, 3000, 0.15)
+    a = rand_array(kind, n, 0.15)
     code = {pa.int32(): 4, pa.int64(): 5, pa.float32(): 10, pa.float64(): 11, pa.date32(): 12}.get(to)
     if pa.types.is_decimal(to):
         got = ctx.cast(ctx.from_arrow(a), dfgpu.capi.DECIMAL128, to.precision, to.scale).to_arrow()
