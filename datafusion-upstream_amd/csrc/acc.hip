@@ -4,14 +4,14 @@
 // groups_accumulator/{prim_op,accumulate}.rs; aggregate/utils.rs:55-125 (DecimalAverager).
 //
 // State lives in HBM, one slot per group: value/sum (8 B, or 16 B lo|hi for Decimal128), count (AVG, COUNT),
-// seen byte (NullState).  Two update paths:
-//   * few groups (<= 8, e.g. TPC-H Q1's 4): every lane keeps all group partials in registers over a
-//     grid-stride loop (compare-select, no divergence, no atomics in the loop), then wave shuffle
-//     reduce -> LDS -> one global atomic per workgroup and group.
-//   * many groups (Q3: 1e6, Q18: 1.5e8): one device-scope atomic per row; Decimal128 wrapping add is two
-//     64-bit atomics with the carry taken from the value the low add returned (exact mod 2^128).
-// Float64 SUM is order dependent in the reference too (sequential add in row order, prim_op.rs:101-109):
-// the contract is <= 1e-9 relative.
+// seen byte (NullState).  A batch of n rows over `total` known groups takes ONE path (choose_path, first match wins; sum-like = SUM / AVG / COUNT):
+//   REGISTERS          sum-like, total <= 8 (TPC-H Q1's 4): k_acc_small, partials in registers; update_batch_multi shares a pass (k_acc_small_multi)
+//   LDS_CACHE          n >= 8 * total, not Decimal128 MIN / MAX: k_acc_cached, a per-workgroup LDS cache in front of the global atomics
+//   RUN_COMBINE_PLAIN  sum-like, plain_batch: k_acc_add_plain combines runs of equal ids; the only path that derives unwritten run-number ids itself
+//   RUN_COMBINE        sum-like otherwise: k_acc_update_add, the same combine row by row
+//   ROW_ATOMIC         MIN / MAX otherwise: k_acc_update, one atomic per row; Decimal128 adds two passes around it (row_atomic_minmax128)
+// Decimal128 wrapping add: two 64-bit atomics, carry from the value the low add returned (exact mod 2^128).  Float64 SUM is order dependent in the reference too
+// (prim_op.rs:101-109): <= 1e-9 relative.  Profile label of every path: k_acc_update.  count_only_valid is always 1; removing it would change tuned device code.
 #include "int128.h"
 #include <algorithm>
 #include <tuple>
@@ -352,7 +352,7 @@ __global__ void __launch_bounds__(BLOCK) k_acc_add_plain(int kind, const T* valu
 // groups 4 ms.  Each workgroup therefore keeps a 4096-entry, 4-probe cache (group id tag, partial value, row count) in LDS:
 // the first groups a workgroup meets claim entries and accumulate with LDS atomics; a group that finds both probes taken
 // falls through to the global atomic.  Hot groups are met first with overwhelming probability, so their traffic stays in
-// LDS and reaches HBM as one atomic per (workgroup, group) at the end.  Chosen by launch_update when the batch has >= 8 rows
+// LDS and reaches HBM as one atomic per (workgroup, group) at the end.  Chosen by choose_path when the batch has >= 8 rows
 // per known group on average (uniform high-cardinality batches keep the direct path).
 constexpr int ACC_CACHE = 4096;        // entries per workgroup: 64 KB of LDS for 8-byte states, 96 KB for i128
 constexpr int ACC_PROBES = 4;
@@ -520,84 +520,165 @@ static void acc_resize(dfgpu_acc* a, int64_t total) {
     hipLaunchKernelGGL(k_acc_clear, dim3(grid_for(vw + cw + sb, BLOCK, ctx->num_cus * 8)), dim3(BLOCK), 0, ctx->stream, (uint64_t*)((char*)a->vals->ptr + a->n * a->width), vw,
                        (uint64_t*)((char*)a->counts->ptr + a->n * 8), cw, (uint8_t*)a->seen->ptr + a->n, sb);
     KERNEL_CHECK();
-    a->n = total;
-    return;
+  } else {
+    HIP_CHECK(hipMemsetAsync((char*)a->counts->ptr + a->n * 8, 0, (size_t)add * 8, ctx->stream));
+    HIP_CHECK(hipMemsetAsync((char*)a->seen->ptr + a->n, 0, (size_t)add, ctx->stream));
+    if (minmax) {
+      bool mn = a->kind == DFGPU_AGG_MIN; uint64_t init;
+      // starting values: NATIVE::MAX for MIN, NATIVE::MIN for MAX (min_max.rs:102-139); integer state is widened to 64 bit
+      if (a->cls == CLS_F64) { double d = a->state_type == DFGPU_FLOAT32 ? 3.40282346638528859812e+38 : 1.7976931348623157e308; if (!mn) d = -d; memcpy(&init, &d, 8); }
+      else if (a->cls == CLS_U64) { uint64_t mx = a->state_type == DFGPU_UINT8 ? 0xFFull : a->state_type == DFGPU_UINT16 ? 0xFFFFull : a->state_type == DFGPU_UINT32 ? 0xFFFFFFFFull : ~0ull; init = mn ? mx : 0; }
+      else { int bits = a->cls == CLS_I128 ? 64 : type_width(a->state_type) * 8; int64_t mx = bits == 64 ? INT64_MAX : ((1ll << (bits - 1)) - 1); int64_t mnv = bits == 64 ? INT64_MIN : -(1ll << (bits - 1)); init = (uint64_t)(mn ? mx : mnv); }
+      dim3 grid(grid_for(add, BLOCK)), block(BLOCK);
+      if (a->cls == CLS_I128) { hipLaunchKernelGGL(k_fill64, grid, block, 0, ctx->stream, (uint64_t*)a->vals->ptr, a->n, total, init, 2, 1);
+                                hipLaunchKernelGGL(k_fill64, grid, block, 0, ctx->stream, (uint64_t*)a->vals->ptr, a->n, total, mn ? ~0ull : 0ull, 2, 0); }
+      else hipLaunchKernelGGL(k_fill64, grid, block, 0, ctx->stream, (uint64_t*)a->vals->ptr, a->n, total, init, 1, 0);
+      KERNEL_CHECK();
+    } else HIP_CHECK(hipMemsetAsync((char*)a->vals->ptr + a->n * a->width, 0, (size_t)add * a->width, ctx->stream));
   }
-  HIP_CHECK(hipMemsetAsync((char*)a->counts->ptr + a->n * 8, 0, (size_t)add * 8, ctx->stream));
-  HIP_CHECK(hipMemsetAsync((char*)a->seen->ptr + a->n, 0, (size_t)add, ctx->stream));
-  if (a->kind == DFGPU_AGG_MIN || a->kind == DFGPU_AGG_MAX) {
-    bool mn = a->kind == DFGPU_AGG_MIN; uint64_t init;
-    // starting values: NATIVE::MAX for MIN, NATIVE::MIN for MAX (min_max.rs:102-139); integer state is widened to 64 bit
-    if (a->cls == CLS_F64) { double d = a->state_type == DFGPU_FLOAT32 ? 3.40282346638528859812e+38 : 1.7976931348623157e308; if (!mn) d = -d; memcpy(&init, &d, 8); }
-    else if (a->cls == CLS_U64) { uint64_t mx = a->state_type == DFGPU_UINT8 ? 0xFFull : a->state_type == DFGPU_UINT16 ? 0xFFFFull : a->state_type == DFGPU_UINT32 ? 0xFFFFFFFFull : ~0ull; init = mn ? mx : 0; }
-    else { int bits = a->cls == CLS_I128 ? 64 : type_width(a->state_type) * 8; int64_t mx = bits == 64 ? INT64_MAX : ((1ll << (bits - 1)) - 1); int64_t mnv = bits == 64 ? INT64_MIN : -(1ll << (bits - 1)); init = (uint64_t)(mn ? mx : mnv); }
-    dim3 grid(grid_for(add, BLOCK)), block(BLOCK);
-    if (a->cls == CLS_I128) { hipLaunchKernelGGL(k_fill64, grid, block, 0, ctx->stream, (uint64_t*)a->vals->ptr, a->n, total, init, 2, 1);
-                              hipLaunchKernelGGL(k_fill64, grid, block, 0, ctx->stream, (uint64_t*)a->vals->ptr, a->n, total, mn ? ~0ull : 0ull, 2, 0); }
-    else hipLaunchKernelGGL(k_fill64, grid, block, 0, ctx->stream, (uint64_t*)a->vals->ptr, a->n, total, init, 1, 0);
-    KERNEL_CHECK();
-  } else HIP_CHECK(hipMemsetAsync((char*)a->vals->ptr + a->n * a->width, 0, (size_t)add * a->width, ctx->stream));
   a->n = total;
 }
 
-static void launch_update(dfgpu_acc* a, int kind, int cls, const dfgpu_array* values, const dfgpu_array* gids, const dfgpu_array* filt, int64_t total, void* vals) {
-  dfgpu_ctx* ctx = a->ctx; int64_t n = gids->length;
+// ------------------------------------------------------------ host: one batch into one set of state arrays
+static void must(dfgpu_ctx* ctx, dfgpu_status rc) { if (rc != DFGPU_OK) fail(rc, "%s", ctx->err.c_str()); }      // a nested entry point's error, passed on
+static bool sum_like(int kind) { return kind == DFGPU_AGG_SUM || kind == DFGPU_AGG_AVG || kind == DFGPU_AGG_COUNT; }
+// The arrays an update writes: an accumulator's own (none yet before its first group), or what the merge of COUNT and AVG states makes of them
+struct AccState { void* vals; uint64_t* counts; uint8_t* seen; };
+static AccState own_state(const dfgpu_acc* a) { return {a->vals ? a->vals->ptr : nullptr, a->counts ? (uint64_t*)a->counts->ptr : nullptr, a->seen ? (uint8_t*)a->seen->ptr : nullptr}; }
+static void check_batch_args(const dfgpu_array* gids, const dfgpu_array* values, const dfgpu_array* filt) {
   if (gids->type != DFGPU_UINT32) fail(DFGPU_INVALID_ARGUMENT, "group ids must be a UINT32 array");
-  // run numbers that were never written out are derived inside the plain accumulate kernel; every other kernel reads stored ids
-  std::shared_ptr<DeferredIds> runs = gids->deferred_ids && gids->deferred_ids->kind == 1 ? gids->deferred_ids : nullptr;
-  {
-    bool sl = kind == DFGPU_AGG_SUM || kind == DFGPU_AGG_AVG || kind == DFGPU_AGG_COUNT;
-    bool plain = sl && !filt && total > SMALL_G && n < 8 * total &&
-                 (kind == DFGPU_AGG_COUNT ? (!values || !values->validity)
-                                          : (values && !values->validity && values->type == (cls == CLS_I128 ? DFGPU_DECIMAL128 : cls == CLS_F64 ? DFGPU_FLOAT64 : values->type) &&
-                                             (cls == CLS_I128 || cls == CLS_F64 || values->type == DFGPU_INT64 || values->type == DFGPU_UINT64)));
-    if (!plain) runs.reset();
-    if (!runs) materialize_ids(ctx, gids);
-  }
-  if (values && values->length != n) fail(DFGPU_INVALID_ARGUMENT, "values (%lld rows) and group ids (%lld rows) differ in length", (long long)values->length, (long long)n);
-  if (filt && (filt->type != DFGPU_BOOL || filt->length != n)) fail(DFGPU_INVALID_ARGUMENT, "opt_filter must be a Boolean array of the batch length");
-  if (!n) return;
-  ColView v{}; if (values) v = make_view(values);
-  const uint64_t* fb = filt ? (const uint64_t*)filt->values->ptr : nullptr; const uint64_t* fv = filt && filt->validity ? (const uint64_t*)filt->validity->ptr : nullptr;
-  const uint32_t* g = (const uint32_t*)gids->values->ptr;
-  int blocks = grid_for(n, BLOCK * 8, ctx->num_cus * 8);
+  if (values && values->length != gids->length) fail(DFGPU_INVALID_ARGUMENT, "values (%lld rows) and group ids (%lld rows) differ in length", (long long)values->length, (long long)gids->length);
+  if (filt && (filt->type != DFGPU_BOOL || filt->length != gids->length)) fail(DFGPU_INVALID_ARGUMENT, "opt_filter must be a Boolean array of the batch length");
+}
+// stored exactly as the element type the kernels instantiate for the class, no validity, no dictionary (SUM / AVG of a narrower integer widens per row)
+static bool stored_as_state(const dfgpu_array* values, int cls) {
+  return values && !values->validity && values->type == (cls == CLS_F64 ? DFGPU_FLOAT64 : cls == CLS_I128 ? DFGPU_DECIMAL128 : cls == CLS_U64 ? DFGPU_UINT64 : DFGPU_INT64);
+}
+// "plain": every row goes from memory into the state unconditionally.  COUNT reads no values: COUNT(*), or a column that cannot be NULL
+static bool plain_batch(int kind, int cls, const dfgpu_array* values, const dfgpu_array* filt) {
+  if (kind != DFGPU_AGG_COUNT) return !filt && stored_as_state(values, cls);
+  return !filt && (!values || (!values->validity && !(values->type == DFGPU_DICTIONARY && values->dictionary->validity)));
+}
+enum class AccPath { REGISTERS, LDS_CACHE, RUN_COMBINE_PLAIN, RUN_COMBINE, ROW_ATOMIC };
+static AccPath choose_path(int kind, int cls, bool plain, int64_t n, int64_t total) {
+  if (sum_like(kind) && total <= SMALL_G) return AccPath::REGISTERS;
+  if (n >= 8 * total && (sum_like(kind) || cls != CLS_I128)) return AccPath::LDS_CACHE;          // the cache holds no Decimal128 extremes
+  if (!sum_like(kind)) return AccPath::ROW_ATOMIC;
+  return plain ? AccPath::RUN_COMBINE_PLAIN : AccPath::RUN_COMBINE;
+}
+struct AccBatch { int kind, cls; ColView v; int has_values; bool plain; const uint32_t* gids; const uint64_t* fbits; const uint64_t* fvalid; int64_t n, total; AccState st; };
+template <int V> using Int = std::integral_constant<int, V>;
+// f(T{}, Int<CLS>{}) for a sum-like kernel: signed and unsigned 64-bit sums wrap alike and share the unsigned instantiation
+template <typename U64, typename F> static void sum_class_dispatch(int cls, F&& f) {
+  if (cls == CLS_F64) f(double{}, Int<CLS_F64>{}); else if (cls == CLS_I128) f(i128{}, Int<CLS_I128>{}); else f(U64{}, Int<CLS_U64>{});
+}
+static dim3 row_grid(dfgpu_ctx* ctx, int64_t n) { return dim3(grid_for(n, BLOCK * 8, ctx->num_cus * 8)); }
+// REGISTERS, RUN_COMBINE and ROW_ATOMIC walk the rows alike: one grid, one argument list (k_acc_small takes the group count as an int and raises no flag)
+static void launch_per_row(dfgpu_ctx* ctx, AccPath path, const AccBatch& b) {
   KernelTimer kt_(ctx, "k_acc_update");
-  bool sumlike = kind == DFGPU_AGG_SUM || kind == DFGPU_AGG_AVG || kind == DFGPU_AGG_COUNT;
-  if (sumlike && total <= SMALL_G) {
-#define SMALL(T, C) hipLaunchKernelGGL((k_acc_small<T, C>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, kind, v, values ? 1 : 0, g, fb, fv, n, (int)total, vals, (uint64_t*)a->counts->ptr, (uint8_t*)a->seen->ptr, 1)
-    if (cls == CLS_F64) SMALL(double, CLS_F64); else if (cls == CLS_I128) SMALL(i128, CLS_I128); else SMALL(uint64_t, CLS_U64);
-#undef SMALL
-  } else if (n >= 8 * total && !(cls == CLS_I128 && !sumlike)) {
-    int cblocks = grid_for(n, BLOCK * 32, ctx->num_cus * 4);         // >= 8192 rows per workgroup amortise the cache flush
-    // plain: the values are stored exactly as the kernel's T (MIN / MAX state keeps the input type; SUM / AVG of a narrower integer widens per row)
-    bool cplain = !filt && (!values ? kind == DFGPU_AGG_COUNT
-                                    : (kind == DFGPU_AGG_COUNT ? !values->validity
-                                       : (!values->validity && values->type != DFGPU_DICTIONARY &&
-                                          (cls == CLS_F64 ? values->type == DFGPU_FLOAT64 : cls == CLS_I128 ? values->type == DFGPU_DECIMAL128 : cls == CLS_U64 ? values->type == DFGPU_UINT64 : values->type == DFGPU_INT64))));
-    const bool cvals = values && kind != DFGPU_AGG_COUNT;
-#define CACHED(T, C, O) do { if (cplain) hipLaunchKernelGGL((k_acc_cached<T, C, O, true>), dim3(cblocks), dim3(BLOCK), 0, ctx->stream, kind, v, cvals ? 1 : 0, g, fb, fv, n, total, vals, (uint64_t*)a->counts->ptr, (uint8_t*)a->seen->ptr, 1, ctx->d_flags); \
-                             else hipLaunchKernelGGL((k_acc_cached<T, C, O, false>), dim3(cblocks), dim3(BLOCK), 0, ctx->stream, kind, v, values ? 1 : 0, g, fb, fv, n, total, vals, (uint64_t*)a->counts->ptr, (uint8_t*)a->seen->ptr, 1, ctx->d_flags); } while (0)
-    if (sumlike) { if (cls == CLS_F64) CACHED(double, CLS_F64, OP_ADD); else if (cls == CLS_I128) CACHED(i128, CLS_I128, OP_ADD); else CACHED(unsigned long long, CLS_U64, OP_ADD); }
-    else if (kind == DFGPU_AGG_MIN) { if (cls == CLS_F64) CACHED(double, CLS_F64, OP_MIN); else if (cls == CLS_U64) CACHED(unsigned long long, CLS_U64, OP_MIN); else CACHED(long long, CLS_I64, OP_MIN); }
-    else { if (cls == CLS_F64) CACHED(double, CLS_F64, OP_MAX); else if (cls == CLS_U64) CACHED(unsigned long long, CLS_U64, OP_MAX); else CACHED(long long, CLS_I64, OP_MAX); }
-#undef CACHED
-  } else if (sumlike && !filt && (kind == DFGPU_AGG_COUNT ? (!values || !values->validity)
-                                  : (!values->validity && values->type == (cls == CLS_I128 ? DFGPU_DECIMAL128 : cls == CLS_F64 ? DFGPU_FLOAT64 : values->type) &&
-                                     (cls == CLS_I128 || cls == CLS_F64 || values->type == DFGPU_INT64 || values->type == DFGPU_UINT64)))) {
-    int pblocks = grid_for(n, BLOCK * ADD_ROWS);
-    const void* vp = kind == DFGPU_AGG_COUNT ? nullptr : values->values->ptr;
-    RunIds ri{}; if (runs) { ri.heads = (const uint64_t*)runs->heads->ptr; ri.prefix = (const uint32_t*)runs->prefix->ptr; ri.base = runs->base; }
-#define PLAIN(T, C, HV) do { if (runs) hipLaunchKernelGGL((k_acc_add_plain<T, C, HV, true>), dim3(pblocks), dim3(BLOCK), 0, ctx->stream, kind, (const T*)vp, g, ri, n, total, vals, (uint64_t*)a->counts->ptr, (uint8_t*)a->seen->ptr, ctx->d_flags); \
-                             else hipLaunchKernelGGL((k_acc_add_plain<T, C, HV, false>), dim3(pblocks), dim3(BLOCK), 0, ctx->stream, kind, (const T*)vp, g, ri, n, total, vals, (uint64_t*)a->counts->ptr, (uint8_t*)a->seen->ptr, ctx->d_flags); } while (0)
-    if (kind == DFGPU_AGG_COUNT) { PLAIN(unsigned long long, CLS_U64, false); } else if (cls == CLS_F64) { PLAIN(double, CLS_F64, true); } else if (cls == CLS_I128) { PLAIN(i128, CLS_I128, true); } else { PLAIN(unsigned long long, CLS_U64, true); }
-#undef PLAIN
-  } else if (sumlike) {
-#define ADD(T, C) hipLaunchKernelGGL((k_acc_update_add<T, C>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, kind, v, values ? 1 : 0, g, fb, fv, n, total, vals, (uint64_t*)a->counts->ptr, (uint8_t*)a->seen->ptr, 1, ctx->d_flags)
-    if (cls == CLS_F64) ADD(double, CLS_F64); else if (cls == CLS_I128) ADD(i128, CLS_I128); else ADD(unsigned long long, CLS_U64);
-#undef ADD
-  } else {
-    hipLaunchKernelGGL(k_acc_update, dim3(blocks), dim3(BLOCK), 0, ctx->stream, kind, cls, v, values ? 1 : 0, g, fb, fv, n, total, vals, (uint64_t*)a->counts->ptr, (uint8_t*)a->seen->ptr, 1, ctx->d_flags);
+  auto go = [&](auto kernel, auto total, auto... flags) {
+    hipLaunchKernelGGL(kernel, row_grid(ctx, b.n), dim3(BLOCK), 0, ctx->stream, b.kind, b.v, b.has_values, b.gids, b.fbits, b.fvalid, b.n, total, b.st.vals, b.st.counts, b.st.seen, 1, flags...); };
+  if (path == AccPath::REGISTERS) sum_class_dispatch<uint64_t>(b.cls, [&](auto t, auto c) { go(k_acc_small<decltype(t), decltype(c)::value>, (int)b.total); });
+  else if (path == AccPath::RUN_COMBINE) sum_class_dispatch<unsigned long long>(b.cls, [&](auto t, auto c) { go(k_acc_update_add<decltype(t), decltype(c)::value>, b.total, ctx->d_flags); });
+  else hipLaunchKernelGGL(k_acc_update, row_grid(ctx, b.n), dim3(BLOCK), 0, ctx->stream, b.kind, b.cls, b.v, b.has_values, b.gids, b.fbits, b.fvalid, b.n, b.total, b.st.vals, b.st.counts, b.st.seen, 1, ctx->d_flags);
+}
+static void launch_lds_cache(dfgpu_ctx* ctx, const AccBatch& b) {
+  KernelTimer kt_(ctx, "k_acc_update");
+  const dim3 grid(grid_for(b.n, BLOCK * 32, ctx->num_cus * 4));         // >= 8192 rows per workgroup amortise the cache flush
+  const int has_values = b.plain && b.kind == DFGPU_AGG_COUNT ? 0 : b.has_values;      // plain COUNT(x) does not look at x
+  auto launch = [&](auto t, auto c, auto o) {
+    using T = decltype(t); constexpr int C = decltype(c)::value, O = decltype(o)::value;
+    hipLaunchKernelGGL((b.plain ? k_acc_cached<T, C, O, true> : k_acc_cached<T, C, O, false>), grid, dim3(BLOCK), 0, ctx->stream, b.kind, b.v, has_values, b.gids, b.fbits, b.fvalid, b.n, b.total, b.st.vals, b.st.counts, b.st.seen, 1, ctx->d_flags); };
+  auto extreme = [&](auto o) { if (b.cls == CLS_F64) launch(double{}, Int<CLS_F64>{}, o); else if (b.cls == CLS_U64) launch((unsigned long long)0, Int<CLS_U64>{}, o); else launch((long long)0, Int<CLS_I64>{}, o); };
+  if (sum_like(b.kind)) sum_class_dispatch<unsigned long long>(b.cls, [&](auto t, auto c) { launch(t, c, Int<OP_ADD>{}); });
+  else if (b.kind == DFGPU_AGG_MIN) extreme(Int<OP_MIN>{}); else extreme(Int<OP_MAX>{});
+}
+static void launch_run_combine_plain(dfgpu_ctx* ctx, const AccBatch& b, const DeferredIds* runs) {
+  KernelTimer kt_(ctx, "k_acc_update");
+  RunIds ri{}; if (runs) { ri.heads = (const uint64_t*)runs->heads->ptr; ri.prefix = (const uint32_t*)runs->prefix->ptr; ri.base = runs->base; }
+  auto launch = [&](auto t, auto c, auto hv) {
+    using T = decltype(t); constexpr int C = decltype(c)::value; constexpr bool HV = decltype(hv)::value;
+    hipLaunchKernelGGL((runs ? k_acc_add_plain<T, C, HV, true> : k_acc_add_plain<T, C, HV, false>), dim3(grid_for(b.n, BLOCK * ADD_ROWS)), dim3(BLOCK), 0, ctx->stream, b.kind, (const T*)(HV ? b.v.values : nullptr),
+                       b.gids, ri, b.n, b.total, b.st.vals, b.st.counts, b.st.seen, ctx->d_flags); };
+  if (b.kind == DFGPU_AGG_COUNT) launch((unsigned long long)0, Int<CLS_U64>{}, std::false_type{});
+  else sum_class_dispatch<unsigned long long>(b.cls, [&](auto t, auto c) { launch(t, c, std::true_type{}); });
+}
+// Decimal128 MIN / MAX: ROW_ATOMIC settles the high words; low words of groups whose high word moved start over and take the extreme among the rows that carry it
+static void row_atomic_minmax128(dfgpu_ctx* ctx, const AccBatch& b) {
+  const int is_min = b.kind == DFGPU_AGG_MIN ? 1 : 0; const dim3 per_group(grid_for(b.total, BLOCK));
+  BufferPtr old_hi = alloc_buffer(ctx, (size_t)b.total * 8);
+  hipLaunchKernelGGL(k_copy_hi, per_group, dim3(BLOCK), 0, ctx->stream, (const uint64_t*)b.st.vals, (uint64_t*)old_hi->ptr, b.total);
+  launch_per_row(ctx, AccPath::ROW_ATOMIC, b);
+  hipLaunchKernelGGL(k_minmax128_prepare, per_group, dim3(BLOCK), 0, ctx->stream, is_min, (uint64_t*)b.st.vals, (const uint64_t*)old_hi->ptr, b.total);
+  hipLaunchKernelGGL(k_acc_minmax128_lo, row_grid(ctx, b.n), dim3(BLOCK), 0, ctx->stream, is_min, b.v, b.gids, b.fbits, b.fvalid, b.n, (uint64_t*)b.st.vals);
+}
+// One batch into `st` as an accumulator of (kind, cls) takes it; the merges SUM partial counts into the count array this way
+static void update_state(dfgpu_ctx* ctx, int kind, int cls, const dfgpu_array* values, const dfgpu_array* gids, const dfgpu_array* filt, int64_t total, AccState st) {
+  check_batch_args(gids, values, filt);
+  const int64_t n = gids->length; const bool plain = plain_batch(kind, cls, values, filt);
+  const AccPath path = choose_path(kind, cls, plain, n, total);
+  // run numbers that were never written out are derived inside the plain combine kernel; every other kernel reads stored ids
+  std::shared_ptr<DeferredIds> runs = path == AccPath::RUN_COMBINE_PLAIN && gids->deferred_ids && gids->deferred_ids->kind == 1 ? gids->deferred_ids : nullptr;
+  if (!runs) materialize_ids(ctx, gids);
+  if (!n) return;
+  const AccBatch b{kind, cls, values ? make_view(values) : ColView{}, values ? 1 : 0, plain, (const uint32_t*)gids->values->ptr,
+                   filt ? (const uint64_t*)filt->values->ptr : nullptr, filt && filt->validity ? (const uint64_t*)filt->validity->ptr : nullptr, n, total, st};
+  if (path == AccPath::LDS_CACHE) launch_lds_cache(ctx, b); else if (path == AccPath::RUN_COMBINE_PLAIN) launch_run_combine_plain(ctx, b, runs.get());
+  else if (path == AccPath::ROW_ATOMIC && cls == CLS_I128 && total) row_atomic_minmax128(ctx, b); else launch_per_row(ctx, path, b);      // total 0: every id is out of range
+  KERNEL_CHECK();
+}
+// ------------------------------------------------------------ all accumulators of a batch at once
+struct MultiSlot { dfgpu_acc* acc; const dfgpu_array* values; const dfgpu_array* filter; bool follower; };
+// can accumulator a take part in a shared small-group pass over `values`?
+static bool multi_ok(const dfgpu_acc* a, const dfgpu_array* values, int64_t total) {
+  if (!a || !values || total > SMALL_G || (a->kind != DFGPU_AGG_SUM && a->kind != DFGPU_AGG_AVG)) return false;
+  return a->cls == CLS_F64 ? values->type == DFGPU_FLOAT64 : a->cls == CLS_I128 ? values->type == DFGPU_DECIMAL128 : (values->type == DFGPU_INT64 || values->type == DFGPU_UINT64);
+}
+// accumulators are independent: ordered by (shareable, value class, filter, value column), SUM(x) and AVG(x) become neighbours and share the pass and the load of x
+static std::vector<MultiSlot> multi_order(dfgpu_acc* const* accs, const dfgpu_array* const* values, const dfgpu_array* const* filters, int32_t n_accs, int64_t total) {
+  std::vector<MultiSlot> s; for (int32_t k = 0; k < n_accs; k++) s.push_back({accs[k], values[k], filters ? filters[k] : nullptr, false});
+  auto key = [&](const MultiSlot& m) { bool ok = multi_ok(m.acc, m.values, total); return std::make_tuple(ok ? 0 : 1, ok ? m.acc->cls : 0, (const void*)m.filter, (const void*)(ok ? m.values->values->ptr : nullptr)); };
+  std::stable_sort(s.begin(), s.end(), [&](const MultiSlot& x, const MultiSlot& y) { return key(x) < key(y); });
+  return s;
+}
+// COUNT(*) (or COUNT of a NULL-free column) counts exactly the rows an AVG over a NULL-free column with the same filter counts: with
+// many groups every state array costs one memory-side atomic per row, so the COUNT takes the AVG's per-group count delta of this
+// batch instead of its own pass over the rows.  Marks those COUNTs as followers and returns the AVG's slot, or -1 when there is no such pair.
+static int choose_count_donor(std::vector<MultiSlot>& s, const dfgpu_array* gids, int64_t total) {
+  if (total <= SMALL_G || gids->length < (1 << 20)) return -1;
+  auto null_free = [](const dfgpu_array* v) { return v && !v->validity && v->type != DFGPU_DICTIONARY; };
+  int donor = -1; bool any = false;
+  for (size_t k = 0; k < s.size() && donor < 0; k++) if (s[k].acc && s[k].acc->kind == DFGPU_AGG_AVG && null_free(s[k].values) && s[k].values->length == gids->length) donor = (int)k;
+  if (donor < 0) return -1;
+  for (MultiSlot& m : s) if (m.acc && m.acc->kind == DFGPU_AGG_COUNT && m.filter == s[(size_t)donor].filter && (!m.values || null_free(m.values))) m.follower = any = true;
+  return any ? donor : -1;
+}
+// one past the last slot that shares slot i's pass: neighbours of the same class and filter, up to 4 (2 of Decimal128: registers)
+static size_t shared_run_end(const std::vector<MultiSlot>& s, size_t i, const dfgpu_array* gids, int64_t total) {
+  if (!gids->length || !multi_ok(s[i].acc, s[i].values, total)) return i + 1;
+  size_t j = i + 1; const size_t cap = s[i].acc->cls == CLS_I128 ? 2 : MULTI_MAX;
+  while (j < s.size() && j - i < cap && multi_ok(s[j].acc, s[j].values, total) && s[j].acc->cls == s[i].acc->cls && s[j].filter == s[i].filter && s[j].values->length == gids->length) j++;
+  return j;
+}
+static void launch_shared_pass(dfgpu_ctx* ctx, const MultiSlot* s, int na, const dfgpu_array* gids, int64_t total) {
+  const dfgpu_array* f = s[0].filter; const int64_t n = gids->length;
+  for (int k = 0; k < na; k++) check_batch_args(gids, s[k].values, f);
+  const uint64_t* fb = f ? (const uint64_t*)f->values->ptr : nullptr; const uint64_t* fv = f && f->validity ? (const uint64_t*)f->validity->ptr : nullptr;
+  materialize_ids(ctx, gids); MultiArgs ma{}; bool plain = fv == nullptr;
+  for (int k = 0; k < na; k++) {
+    dfgpu_acc* a = s[k].acc; const dfgpu_array* v = s[k].values;
+    acc_resize(a, total); const AccState st = own_state(a);
+    ma.vals[k] = v->values->ptr; ma.valid[k] = v->validity ? (const uint64_t*)v->validity->ptr : nullptr;
+    ma.out_vals[k] = st.vals; ma.out_counts[k] = st.counts; ma.out_seen[k] = st.seen; ma.kind[k] = a->kind;
+    plain = plain && !v->validity;
   }
+  KernelTimer kt_(ctx, "k_acc_update");
+  auto launch = [&](auto t, auto c, auto count) {
+    using T = decltype(t); constexpr int C = decltype(c)::value, N = decltype(count)::value;
+    hipLaunchKernelGGL((plain ? k_acc_small_multi<T, C, N, true> : k_acc_small_multi<T, C, N, false>), row_grid(ctx, n), dim3(BLOCK), 0, ctx->stream, ma, (const uint32_t*)gids->values->ptr, fb, fv, n, (int)total); };
+  auto by_count = [&](auto t, auto c) { if (na == 2) launch(t, c, Int<2>{}); else if (na == 3) launch(t, c, Int<3>{}); else launch(t, c, Int<4>{}); };
+  const int cls = s[0].acc->cls;
+  if (cls == CLS_I128) launch(i128{}, Int<CLS_I128>{}, Int<2>{}); else if (cls == CLS_F64) by_count(double{}, Int<CLS_F64>{}); else by_count((unsigned long long)0, Int<CLS_U64>{});
   KERNEL_CHECK();
 }
 
@@ -646,106 +727,33 @@ dfgpu_status dfgpu_acc_update_batch(dfgpu_ctx* ctx, dfgpu_acc* a, const dfgpu_ar
       if (!ok) fail(DFGPU_INVALID_ARGUMENT, "accumulator created for input type %d got values of type %d", a->in_type, lt);
     }
     acc_resize(a, total);
-    bool mm128 = (a->kind == DFGPU_AGG_MIN || a->kind == DFGPU_AGG_MAX) && a->cls == CLS_I128;
-    BufferPtr old_hi;
-    if (mm128 && total) { old_hi = alloc_buffer(ctx, (size_t)total * 8); hipLaunchKernelGGL(k_copy_hi, dim3(grid_for(total, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)a->vals->ptr, (uint64_t*)old_hi->ptr, total); }
-    launch_update(a, a->kind, a->cls, values, gids, filt, total, a->vals ? a->vals->ptr : nullptr);
-    if (mm128 && total && gids->length) {
-      hipLaunchKernelGGL(k_minmax128_prepare, dim3(grid_for(total, BLOCK)), dim3(BLOCK), 0, ctx->stream, a->kind == DFGPU_AGG_MIN ? 1 : 0, (uint64_t*)a->vals->ptr, (const uint64_t*)old_hi->ptr, total);
-      ColView v = make_view(values);
-      hipLaunchKernelGGL(k_acc_minmax128_lo, dim3(grid_for(gids->length, BLOCK * 8, ctx->num_cus * 8)), dim3(BLOCK), 0, ctx->stream, a->kind == DFGPU_AGG_MIN ? 1 : 0, v, (const uint32_t*)gids->values->ptr,
-                         filt ? (const uint64_t*)filt->values->ptr : nullptr, filt && filt->validity ? (const uint64_t*)filt->validity->ptr : nullptr, gids->length, (uint64_t*)a->vals->ptr);
-      KERNEL_CHECK();
-    }
+    update_state(ctx, a->kind, a->cls, values, gids, filt, total, own_state(a));
     check_flags(ctx, "acc_update_batch");
   });
 }
 
-// can accumulator a take part in a shared small-group pass over `values`?
-static bool multi_ok(const dfgpu_acc* a, const dfgpu_array* values, int64_t total) {
-  if (!a || !values || total > SMALL_G || (a->kind != DFGPU_AGG_SUM && a->kind != DFGPU_AGG_AVG)) return false;
-  if (values->type == DFGPU_DICTIONARY) return false;
-  return a->cls == CLS_F64 ? values->type == DFGPU_FLOAT64 : a->cls == CLS_I128 ? values->type == DFGPU_DECIMAL128 : (values->type == DFGPU_INT64 || values->type == DFGPU_UINT64);
-}
 dfgpu_status dfgpu_acc_update_batch_multi(dfgpu_ctx* ctx, dfgpu_acc* const* accs, const dfgpu_array* const* values, const dfgpu_array* const* filters, int32_t n_accs,
                                           const dfgpu_array* gids, int64_t total) {
-  if (!accs || !values || !gids || n_accs < 0) { if (ctx) ctx->err = "acc_update_batch_multi: null argument"; return DFGPU_INVALID_ARGUMENT; }
-  // accumulators are independent of each other: visit them ordered by (shareable, value class, filter, value column) so that SUM(x) and
-  // AVG(x) become neighbours and share both the pass and the load of x
-  std::vector<int32_t> order((size_t)n_accs); for (int32_t k = 0; k < n_accs; k++) order[(size_t)k] = k;
-  auto key = [&](int32_t k) { bool ok = multi_ok(accs[k], values[k], total); return std::make_tuple(ok ? 0 : 1, ok ? accs[k]->cls : 0, (const void*)(filters ? filters[k] : nullptr), (const void*)(ok ? values[k]->values->ptr : nullptr)); };
-  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key(a) < key(b); });
-  std::vector<dfgpu_acc*> accs_o; std::vector<const dfgpu_array*> values_o, filters_o;
-  for (int32_t k : order) { accs_o.push_back(accs[k]); values_o.push_back(values[k]); filters_o.push_back(filters ? filters[k] : nullptr); }
-  accs = accs_o.data(); values = values_o.data(); filters = filters_o.data();
-  // COUNT(*) (or COUNT of a NULL-free column) counts exactly the rows an AVG over a NULL-free column with the same filter counts: with
-  // many groups every state array costs one memory-side atomic per row, so the COUNT takes the AVG's per-group count delta of this
-  // batch instead of its own pass over the rows.
-  int donor = -1; std::vector<int> followers; BufferPtr before;
-  if (total > SMALL_G && gids->length >= (1 << 20)) {
-    auto null_free = [](const dfgpu_array* v) { return v && !v->validity && v->type != DFGPU_DICTIONARY; };
-    for (int32_t k = 0; k < n_accs && donor < 0; k++) if (accs[k] && accs[k]->kind == DFGPU_AGG_AVG && null_free(values[k]) && values[k]->length == gids->length) donor = k;
-    if (donor >= 0) for (int32_t k = 0; k < n_accs; k++)
-      if (accs[k] && accs[k]->kind == DFGPU_AGG_COUNT && filters[k] == filters[donor] && (!values[k] || null_free(values[k]))) followers.push_back(k);
-    if (!followers.empty()) {
-      dfgpu_status st = guard(ctx, [&] {
-        acc_resize(accs[donor], total);
-        before = alloc_buffer(ctx, (size_t)total * 8);
-        HIP_CHECK(hipMemcpyAsync(before->ptr, accs[donor]->counts->ptr, (size_t)total * 8, hipMemcpyDeviceToDevice, ctx->stream));
-      });
-      if (st != DFGPU_OK) return st;
+  return guard(ctx, [&] {         // the first failing accumulator's status is the answer; nothing after it runs, the followers' deltas included
+    if (!accs || !values || !gids || n_accs < 0) fail(DFGPU_INVALID_ARGUMENT, "acc_update_batch_multi: null argument");
+    std::vector<MultiSlot> s = multi_order(accs, values, filters, n_accs, total);
+    const int donor = choose_count_donor(s, gids, total); BufferPtr before;                 // before: the donor's counts in front of this batch
+    if (donor >= 0) {
+      acc_resize(s[(size_t)donor].acc, total); before = alloc_buffer(ctx, (size_t)total * 8);
+      HIP_CHECK(hipMemcpyAsync(before->ptr, s[(size_t)donor].acc->counts->ptr, (size_t)total * 8, hipMemcpyDeviceToDevice, ctx->stream));
     }
-  }
-  auto is_follower = [&](int32_t k) { return std::find(followers.begin(), followers.end(), (int)k) != followers.end(); };
-  struct AddDeltas { dfgpu_ctx* ctx; dfgpu_acc* const* accs; const std::vector<int>& fol; int donor; const BufferPtr& before; int64_t total;
-    dfgpu_status run() const { if (fol.empty()) return DFGPU_OK; return guard(ctx, [&] {
-      for (int k : fol) { acc_resize(accs[k], total);
-        hipLaunchKernelGGL(k_add_count_delta, dim3(grid_for(total, BLOCK)), dim3(BLOCK), 0, ctx->stream, (uint64_t*)accs[k]->counts->ptr, (const uint64_t*)accs[donor]->counts->ptr, (const uint64_t*)before->ptr, total); }
-      KERNEL_CHECK(); }); } } add_deltas{ctx, accs, followers, donor, before, total};
-  int32_t i = 0;
-  while (i < n_accs) {
-    if (is_follower(i)) { i++; continue; }
-    const dfgpu_array* f = filters ? filters[i] : nullptr;
-    int32_t j = i;
-    int cap = accs[i] && accs[i]->cls == CLS_I128 ? 2 : MULTI_MAX;
-    if (gids->length && multi_ok(accs[i], values[i], total))
-      while (j + 1 < n_accs && j + 1 - i < cap && multi_ok(accs[j + 1], values[j + 1], total) && accs[j + 1]->cls == accs[i]->cls && (filters ? filters[j + 1] : nullptr) == f &&
-             values[j + 1]->length == gids->length) j++;
-    if (j == i) {                 // alone: the single-accumulator path
-      dfgpu_status st = dfgpu_acc_update_batch(ctx, accs[i], values[i], gids, f, total);
-      if (st != DFGPU_OK) return st;
-      i++; continue;
+    for (size_t i = 0; i < s.size();) {
+      if (s[i].follower) { i++; continue; }
+      const size_t end = shared_run_end(s, i, gids, total);
+      if (end - i == 1) must(ctx, dfgpu_acc_update_batch(ctx, s[i].acc, s[i].values, gids, s[i].filter, total));       // alone: the single-accumulator path
+      else launch_shared_pass(ctx, &s[i], (int)(end - i), gids, total);
+      i = end;
     }
-    dfgpu_status st = guard(ctx, [&] {
-      int64_t n = gids->length;
-      if (gids->type != DFGPU_UINT32) fail(DFGPU_INVALID_ARGUMENT, "group ids must be a UINT32 array");
-      materialize_ids(ctx, gids);
-      if (f && (f->type != DFGPU_BOOL || f->length != n)) fail(DFGPU_INVALID_ARGUMENT, "opt_filter must be a Boolean array of the batch length");
-      MultiArgs ma{}; int na = j - i + 1;
-      for (int s = 0; s < na; s++) {
-        dfgpu_acc* a = accs[i + s]; const dfgpu_array* v = values[i + s];
-        if (v->length != n) fail(DFGPU_INVALID_ARGUMENT, "values (%lld rows) and group ids (%lld rows) differ in length", (long long)v->length, (long long)n);
-        acc_resize(a, total);
-        ma.vals[s] = v->values->ptr; ma.valid[s] = v->validity ? (const uint64_t*)v->validity->ptr : nullptr;
-        ma.out_vals[s] = a->vals->ptr; ma.out_counts[s] = (uint64_t*)a->counts->ptr; ma.out_seen[s] = (uint8_t*)a->seen->ptr; ma.kind[s] = a->kind;
-      }
-      const uint64_t* fb = f ? (const uint64_t*)f->values->ptr : nullptr; const uint64_t* fv = f && f->validity ? (const uint64_t*)f->validity->ptr : nullptr;
-      int blocks = grid_for(n, BLOCK * 8, ctx->num_cus * 8);
-      KernelTimer kt_(ctx, "k_acc_update");
-      bool plain = fv == nullptr; for (int s2 = 0; s2 < na; s2++) plain = plain && ma.valid[s2] == nullptr;
-#define MULTI(T, C, N) do { if (plain) hipLaunchKernelGGL((k_acc_small_multi<T, C, N, true>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, ma, (const uint32_t*)gids->values->ptr, fb, fv, n, (int)total); \
-                            else hipLaunchKernelGGL((k_acc_small_multi<T, C, N, false>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, ma, (const uint32_t*)gids->values->ptr, fb, fv, n, (int)total); } while (0)
-      int cls = accs[i]->cls;
-      if (cls == CLS_I128) MULTI(i128, CLS_I128, 2);
-      else if (cls == CLS_F64) { if (na == 2) MULTI(double, CLS_F64, 2); else if (na == 3) MULTI(double, CLS_F64, 3); else MULTI(double, CLS_F64, 4); }
-      else { if (na == 2) MULTI(unsigned long long, CLS_U64, 2); else if (na == 3) MULTI(unsigned long long, CLS_U64, 3); else MULTI(unsigned long long, CLS_U64, 4); }
-#undef MULTI
-      KERNEL_CHECK();
-    });
-    if (st != DFGPU_OK) return st;
-    i = j + 1;
-  }
-  return add_deltas.run();
+    for (const MultiSlot& m : s) if (m.follower) {
+      acc_resize(m.acc, total);
+      hipLaunchKernelGGL(k_add_count_delta, dim3(grid_for(total, BLOCK)), dim3(BLOCK), 0, ctx->stream, (uint64_t*)m.acc->counts->ptr, (const uint64_t*)s[(size_t)donor].acc->counts->ptr, (const uint64_t*)before->ptr, total); }
+    if (donor >= 0) KERNEL_CHECK();
+  });
 }
 
 // ------------------------------------------------------------------ fused "evaluate arguments + accumulate" (run-time compiled)
@@ -930,9 +938,8 @@ dfgpu_status dfgpu_acc_update_batch_fused(dfgpu_ctx* ctx, dfgpu_acc* const* accs
     if (!accs || !acc_nodes || n_accs < 1 || !gids || (n_nodes > 0 && (!nodes || !cols))) fail(DFGPU_INVALID_ARGUMENT, "acc_update_batch_fused: null argument");
     if (n_accs > FUSED_MAX || n_cols > FUSED_MAX || n_nodes > 64) fail(DFGPU_NOT_IMPLEMENTED, "acc_update_batch_fused: more than %d accumulators / columns or 64 nodes", FUSED_MAX);
     if (total < 1 || total > SMALL_G) fail(DFGPU_NOT_IMPLEMENTED, "acc_update_batch_fused: %lld groups (register partials hold up to %d)", (long long)total, SMALL_G);
-    if (gids->type != DFGPU_UINT32) fail(DFGPU_INVALID_ARGUMENT, "group ids must be a UINT32 array");
+    check_batch_args(gids, nullptr, filt);
     int64_t n = gids->length;
-    if (filt && (filt->type != DFGPU_BOOL || filt->length != n)) fail(DFGPU_INVALID_ARGUMENT, "opt_filter must be a Boolean array of the batch length");
     if (filt && filt->validity) fail(DFGPU_NOT_IMPLEMENTED, "acc_update_batch_fused: nullable filter");
     // one arithmetic class for the whole DAG: Float64, or Decimal128 with arrow-arith's result types per node
     int32_t cls_type = 0; std::vector<FusedNodeInfo> info((size_t)n_nodes);
@@ -1022,62 +1029,55 @@ dfgpu_status dfgpu_jit_selftest(const char* arch, char* log, int64_t log_cap) {
 
 // merge_batch of states that carry group i in row i (ids 0 .. total-1, flagged as the identity) into an accumulator that holds nothing yet -- the partial rows of a first,
 // fully pre-aggregated batch (AggregateExec::merge_partial): the states ARE the accumulator's new contents, so they are copied in instead of being added row by row
-static bool acc_adopt_identity(dfgpu_ctx* ctx, dfgpu_acc* a, const dfgpu_array* const* st, int32_t nst, const dfgpu_array* gids, const dfgpu_array* filt, int64_t total) {
+static bool acc_adopt_identity(dfgpu_acc* a, const dfgpu_array* const* st, int32_t nst, const dfgpu_array* gids, const dfgpu_array* filt, int64_t total) {
   if (a->n != 0 || filt || !gids || !gids->identity || gids->length != total || total <= 0) return false;
-  if (a->kind == DFGPU_AGG_AVG) return false;            // its `seen` is count > 0 per group: left to the row-by-row merge
-  const int want = 1; if (nst != want) return false;
-  for (int i = 0; i < nst; i++) if (!st[i] || st[i]->validity || st[i]->length != total || st[i]->type == DFGPU_DICTIONARY || !st[i]->values) return false;
-  const dfgpu_array* vals = a->kind == DFGPU_AGG_COUNT ? nullptr : st[nst - 1];
-  if (a->kind == DFGPU_AGG_COUNT && st[0]->type != DFGPU_INT64) return false;
-  if (a->kind == DFGPU_AGG_AVG && st[0]->type != DFGPU_UINT64) return false;
-  if (vals && (vals->type != a->state_type || type_width(vals->type) != a->width)) return false;
+  if (a->kind == DFGPU_AGG_AVG || nst != 1) return false;            // AVG's `seen` is count > 0 per group: left to the row-by-row merge
+  const dfgpu_array* s0 = st[0]; const bool count = a->kind == DFGPU_AGG_COUNT;
+  if (!s0 || s0->validity || s0->length != total || s0->type == DFGPU_DICTIONARY || !s0->values) return false;
+  if (count ? s0->type != DFGPU_INT64 : (s0->type != a->state_type || type_width(s0->type) != a->width)) return false;
   // nothing is copied here: 20 M groups x (SUM, COUNT) were 0.35 ms of copies and fills per step, written only to be copied out again by the evaluation that follows a
   // single-batch aggregation (profiles/r04_n_timeline_gb20.txt)
-  a->lazy = true; a->lazy_vals = vals ? vals->values : BufferPtr(); a->lazy_counts = a->kind == DFGPU_AGG_COUNT ? st[0]->values : BufferPtr();
+  a->lazy = true; a->lazy_vals = count ? BufferPtr() : s0->values; a->lazy_counts = count ? s0->values : BufferPtr();
   a->vals.reset(); a->counts.reset(); a->seen.reset(); a->cap = 0;
   a->n = total;
   return true;
 }
 dfgpu_status dfgpu_acc_merge_batch(dfgpu_ctx* ctx, dfgpu_acc* a, const dfgpu_array* const* st, int32_t nst, const dfgpu_array* gids, const dfgpu_array* filt, int64_t total) {
-  if (!a || !st) return DFGPU_INVALID_ARGUMENT;
-  { bool adopted = false; dfgpu_status rc = guard(ctx, [&] { adopted = acc_adopt_identity(ctx, a, st, nst, gids, filt, total); }); if (rc != DFGPU_OK || adopted) return rc; }
-  if (a->kind == DFGPU_AGG_COUNT) {         // count.rs:135-170: add the partial counts (never null)
-    return guard(ctx, [&] {
-      if (nst != 1 || st[0]->type != DFGPU_INT64) fail(DFGPU_INVALID_ARGUMENT, "COUNT merge expects one Int64 state");
-      acc_resize(a, total);
-      launch_update(a, DFGPU_AGG_SUM, CLS_I64, st[0], gids, filt, total, a->counts->ptr);     // sum into counts; `seen` is unused by COUNT
-      check_flags(ctx, "acc_merge_batch");
-    });
-  }
-  if (a->kind == DFGPU_AGG_AVG) {           // average.rs:472-509
-    return guard(ctx, [&] {
-      if (nst != 2 || st[0]->type != DFGPU_UINT64) fail(DFGPU_INVALID_ARGUMENT, "AVG merge expects (UInt64 counts, sums)");
-      acc_resize(a, total);
+  if (!a || !st || !gids) return DFGPU_INVALID_ARGUMENT;
+  { bool adopted = false; dfgpu_status rc = guard(ctx, [&] { adopted = acc_adopt_identity(a, st, nst, gids, filt, total); }); if (rc != DFGPU_OK || adopted) return rc; }
+  if (a->kind == DFGPU_AGG_COUNT || a->kind == DFGPU_AGG_AVG) return guard(ctx, [&] {
+    if (a->kind == DFGPU_AGG_COUNT) {         // count.rs:135-170: add the partial counts (never null); `seen` is unused by COUNT
+      if (nst != 1 || !st[0] || st[0]->type != DFGPU_INT64) fail(DFGPU_INVALID_ARGUMENT, "COUNT merge expects one Int64 state");
+      acc_resize(a, total); const AccState own = own_state(a);
+      update_state(ctx, DFGPU_AGG_SUM, CLS_I64, st[0], gids, filt, total, {own.counts, own.counts, own.seen});
+    } else {                                  // average.rs:472-509
+      if (nst != 2 || !st[0] || !st[1] || st[0]->type != DFGPU_UINT64) fail(DFGPU_INVALID_ARGUMENT, "AVG merge expects (UInt64 counts, sums)");
+      // acc_cell_f64 / acc_cell_int read the sums as the state type, and the first merge below must not run when the second cannot
+      if (logical_type(st[1]) != a->state_type) fail(DFGPU_INVALID_ARGUMENT, "AVG merge expects sums of type %d (got %d)", a->state_type, logical_type(st[1]));
+      check_batch_args(gids, st[0], filt); check_batch_args(gids, st[1], filt);
+      acc_resize(a, total); const AccState own = own_state(a);
       // the counts are summed without touching the null state (accumulate_indices, average.rs:489-497); only a non-NULL partial sum marks its group as seen (:499-507) -- a
       // partial state of count 0 and a NULL sum (a group whose argument was NULL in every row) must leave the group NULL
-      { BufferPtr seen = a->seen; a->seen = alloc_buffer(ctx, (size_t)a->cap + 64);
-        struct Restore { dfgpu_acc* a; BufferPtr s; ~Restore() { a->seen = s; } } restore{a, seen};
-        launch_update(a, DFGPU_AGG_SUM, CLS_U64, st[0], gids, filt, total, a->counts->ptr); }
-      launch_update(a, DFGPU_AGG_SUM, a->cls, st[1], gids, filt, total, a->vals->ptr);
-      check_flags(ctx, "acc_merge_batch");
-    });
-  }
+      BufferPtr scratch_seen = alloc_buffer(ctx, (size_t)a->cap + 64);
+      update_state(ctx, DFGPU_AGG_SUM, CLS_U64, st[0], gids, filt, total, {own.counts, own.counts, (uint8_t*)scratch_seen->ptr});
+      update_state(ctx, DFGPU_AGG_SUM, a->cls, st[1], gids, filt, total, own);
+    }
+    check_flags(ctx, "acc_merge_batch");
+  });
   if (nst != 1) { if (ctx) ctx->err = "merge expects one state column"; return DFGPU_INVALID_ARGUMENT; }
   return dfgpu_acc_update_batch(ctx, a, st[0], gids, filt, total);     // prim_op.rs:119-127: update / merge are the same
 }
 
-static dfgpu_array* emit_values(dfgpu_ctx* ctx, dfgpu_acc* a, int32_t type, int32_t p, int32_t s, const void* src, bool with_seen) {
-  if (a->lazy) {            // adopted states, every group seen: the adopted buffer is the result (or its narrowed copy)
-    const BufferPtr& buf = a->kind == DFGPU_AGG_COUNT ? a->lazy_counts : a->lazy_vals;
-    if (type_width(type) == a->width || a->cls == CLS_I128 || a->kind == DFGPU_AGG_COUNT) { ArrayHolder h(new_array(ctx, type, a->n, p, s)); h.get()->values = buf; h.get()->null_count = 0; return h.release(); }
-    ArrayHolder h(new_fixed(ctx, type, a->n, p, s, false));
-    hipLaunchKernelGGL(k_narrow, dim3(grid_for(a->n, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)buf->ptr, a->n, type, h.get()->values->ptr); KERNEL_CHECK();
-    return h.release();
-  }
+// One state array (the values, or the counts) as an output array of `type`.  An 8-byte state word narrows where the type is narrower (MIN / MAX of a small integer or
+// Float32); everything else leaves as it is stored.
+static dfgpu_array* emit_values(dfgpu_ctx* ctx, dfgpu_acc* a, int32_t type, int32_t p, int32_t s, bool from_counts, bool with_seen) {
+  const BufferPtr& src = a->lazy ? (from_counts ? a->lazy_counts : a->lazy_vals) : (from_counts ? a->counts : a->vals);
+  const bool narrow = type_width(type) != a->width && a->cls != CLS_I128; if (a->lazy) with_seen = false;           // adopted states: every group seen
+  if (a->lazy && !narrow) { ArrayHolder h(new_array(ctx, type, a->n, p, s)); h.get()->values = src; h.get()->null_count = 0; return h.release(); }     // the adopted buffer is the result
   ArrayHolder h(new_fixed(ctx, type, a->n, p, s, with_seen));
   if (a->n) {
-    if (type_width(type) == a->width || a->cls == CLS_I128) HIP_CHECK(hipMemcpyAsync(h.get()->values->ptr, src, (size_t)a->n * type_width(type), hipMemcpyDeviceToDevice, ctx->stream));
-    else hipLaunchKernelGGL(k_narrow, dim3(grid_for(a->n, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)src, a->n, type, h.get()->values->ptr);
+    if (narrow) hipLaunchKernelGGL(k_narrow, dim3(grid_for(a->n, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)src->ptr, a->n, type, h.get()->values->ptr);
+    else HIP_CHECK(hipMemcpyAsync(h.get()->values->ptr, src->ptr, (size_t)a->n * type_width(type), hipMemcpyDeviceToDevice, ctx->stream));
     if (with_seen) hipLaunchKernelGGL(k_seen_to_bits, dim3(grid_for(a->n, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint8_t*)a->seen->ptr, a->n, (uint64_t*)h.get()->validity->ptr);
     KERNEL_CHECK();
   }
@@ -1088,8 +1088,8 @@ static dfgpu_array* emit_values(dfgpu_ctx* ctx, dfgpu_acc* a, int32_t type, int3
 dfgpu_status dfgpu_acc_evaluate(dfgpu_ctx* ctx, dfgpu_acc* a, dfgpu_array** out) {
   return guard(ctx, [&] {
     if (!a || !out) fail(DFGPU_INVALID_ARGUMENT, "acc_evaluate: null argument");
-    if (a->kind == DFGPU_AGG_COUNT) { *out = emit_values(ctx, a, DFGPU_INT64, 0, 0, a->counts ? a->counts->ptr : nullptr, false); return; }
-    if (a->kind != DFGPU_AGG_AVG) { *out = emit_values(ctx, a, a->out_type, a->out_precision, a->out_scale, a->vals ? a->vals->ptr : nullptr, true); return; }
+    if (a->kind == DFGPU_AGG_COUNT) { *out = emit_values(ctx, a, DFGPU_INT64, 0, 0, true, false); return; }
+    if (a->kind != DFGPU_AGG_AVG) { *out = emit_values(ctx, a, a->out_type, a->out_precision, a->out_scale, false, true); return; }
     ArrayHolder h(new_fixed(ctx, a->out_type, a->n, a->out_precision, a->out_scale, true));
     if (a->n) {
       dim3 grid(grid_for(a->n, BLOCK)), block(BLOCK);
@@ -1110,8 +1110,8 @@ dfgpu_status dfgpu_acc_state(dfgpu_ctx* ctx, dfgpu_acc* a, dfgpu_array** out_sta
   if (!a || !out_states || !n_states) return DFGPU_INVALID_ARGUMENT;
   if (a->kind != DFGPU_AGG_AVG) { *n_states = 1; return dfgpu_acc_evaluate(ctx, a, &out_states[0]); }
   return guard(ctx, [&] {
-    ArrayHolder c(emit_values(ctx, a, DFGPU_UINT64, 0, 0, a->counts ? a->counts->ptr : nullptr, true));
-    ArrayHolder s(emit_values(ctx, a, a->state_type, a->state_precision, a->state_scale, a->vals ? a->vals->ptr : nullptr, true));
+    ArrayHolder c(emit_values(ctx, a, DFGPU_UINT64, 0, 0, true, true));
+    ArrayHolder s(emit_values(ctx, a, a->state_type, a->state_precision, a->state_scale, false, true));
     out_states[0] = c.release(); out_states[1] = s.release(); *n_states = 2;
   });
 }
@@ -1122,21 +1122,19 @@ dfgpu_status dfgpu_acc_emit_first(dfgpu_ctx* ctx, dfgpu_acc* a, int64_t n, int32
     if (!a || !out || n < 0) fail(DFGPU_INVALID_ARGUMENT, "acc_emit_first: bad argument");
     const int64_t total = a->n, k = n < total ? n : total;
     dfgpu_array* st[2] = {nullptr, nullptr}; int32_t ns = 0;
-    dfgpu_status rc = dfgpu_acc_state(ctx, a, st, &ns); if (rc != DFGPU_OK) fail(rc, "%s", ctx->err.c_str());
+    must(ctx, dfgpu_acc_state(ctx, a, st, &ns));
     ArrayHolder s0(st[0]), s1(st[1]);
-    ArrayHolder ev; if (!as_state) { dfgpu_array* e = nullptr; rc = dfgpu_acc_evaluate(ctx, a, &e); if (rc != DFGPU_OK) fail(rc, "%s", ctx->err.c_str()); ev.a = e; }
-    auto slice = [&](const dfgpu_array* x, int64_t off, int64_t len) { dfgpu_array* o = nullptr; dfgpu_status r2 = dfgpu_array_slice(ctx, x, off, len, &o); if (r2 != DFGPU_OK) fail(r2, "%s", ctx->err.c_str()); return o; };
+    ArrayHolder ev; if (!as_state) must(ctx, dfgpu_acc_evaluate(ctx, a, &ev.a));
+    auto slice = [&](const dfgpu_array* x, int64_t off, int64_t len) { dfgpu_array* o = nullptr; must(ctx, dfgpu_array_slice(ctx, x, off, len, &o)); return o; };
     ArrayHolder o0, o1;
     if (as_state) { o0.a = slice(s0.get(), 0, k); if (ns > 1) o1.a = slice(s1.get(), 0, k); } else o0.a = slice(ev.get(), 0, k);
     // the groups that stay are renumbered from 0 (EmitTo::take_needed): their states are merged into the emptied accumulator under ids 0 .. total - k - 1
-    const int kind = a->kind; const int32_t it = a->in_type, ip = a->in_precision, is = a->in_scale;
     a->n = 0; a->cap = 0; a->vals.reset(); a->counts.reset(); a->seen.reset(); a->lazy = false; a->lazy_vals.reset(); a->lazy_counts.reset();
-    (void)kind; (void)it; (void)ip; (void)is;
     if (k < total) {
       ArrayHolder r0(slice(s0.get(), k, total - k)), r1; if (ns > 1) r1.a = slice(s1.get(), k, total - k);
-      dfgpu_array* ids = nullptr; rc = dfgpu_array_iota(ctx, total - k, &ids); if (rc != DFGPU_OK) fail(rc, "%s", ctx->err.c_str()); ArrayHolder idh(ids);
+      ArrayHolder ids; must(ctx, dfgpu_array_iota(ctx, total - k, &ids.a));
       const dfgpu_array* sp[2] = { r0.get(), r1.get() };
-      rc = dfgpu_acc_merge_batch(ctx, a, sp, ns, idh.get(), nullptr, total - k); if (rc != DFGPU_OK) fail(rc, "%s", ctx->err.c_str());
+      must(ctx, dfgpu_acc_merge_batch(ctx, a, sp, ns, ids.get(), nullptr, total - k));
     }
     out[0] = o0.release(); if (as_state && ns > 1) out[1] = o1.release();
     if (n_out) *n_out = as_state ? ns : 1;

@@ -748,3 +748,172 @@ def test_group_values_moves_between_representations_like_the_oracle(ctx, name):
         ctx.profile_enable(False)
     for a, w in zip(gv.emit(), og.emit()):
         assert a.to_arrow().equals(w)
+
+
+# ------------------------------------------------------------------ the edges of acc.hip's choose_path
+# A batch of n rows over `total` groups goes to: REGISTERS (k_acc_small) when total <= 8 and the kind is SUM / AVG / COUNT; LDS_CACHE (k_acc_cached, PLAIN or not) when
+# n >= 8 * total (not Decimal128 MIN / MAX); else RUN_COMBINE_PLAIN (k_acc_add_plain: no filter, values stored as the state type without NULLs), RUN_COMBINE
+# (k_acc_update_add) or, for MIN / MAX, ROW_ATOMIC (k_acc_update; Decimal128 with its two extra passes).  No test can observe the kernel: the shapes below reach the
+# named ones by construction from that rule.
+def _acc_pair(ctx, fun, sample):
+    import dfgpu
+    f = dfgpu.operators.field_of_array("v", ctx.from_arrow(sample))
+    return dfgpu.GroupsAccumulator(ctx, KIND[fun], f.dtype, f.precision, f.scale), po.Acc(fun, sample.type)
+
+
+def _ids(total, n):
+    """n ids that cover every group, a few of them 0xFFFFFFFF (rows of no group)"""
+    g = np.concatenate([np.arange(total), RNG.integers(0, total, n - total)]).astype(np.int64)
+    RNG.shuffle(g)
+    g[RNG.integers(0, n, 3)] = 0xFFFFFFFF
+    return g
+
+
+def _update_both(ctx, acc, oacc, v, g, filt, total):
+    """the oracle takes no 0xFFFFFFFF ids: it gets the batch without those rows"""
+    acc.update_batch(ctx.from_arrow(v), ctx.from_arrow(pa.array(g.astype(np.uint32))), ctx.from_arrow(filt) if filt is not None else None, total)
+    keep = pa.array(g != 0xFFFFFFFF)
+    oacc.update_batch(v.filter(keep), g[g != 0xFFFFFFFF], filt.filter(keep) if filt is not None else None, total)
+
+
+def _check_acc(acc, oacc, floats):
+    st, ost = acc.state(), oacc.state()
+    assert len(st) == len(ost)
+    for a, b in zip(st, ost):
+        check_equal(a.to_arrow(), b, floats)
+    check_equal(acc.evaluate().to_arrow(), oacc.evaluate(), floats)
+    return st, ost
+
+
+def _is_float_sum(fun, kind):
+    return kind.startswith("float") and fun in ("SUM", "AVG")
+
+
+@pytest.mark.parametrize("total,n", [(8, 71), (9, 71), (9, 72), (300, 2399), (300, 2400)])
+@pytest.mark.parametrize("fun,kind", AGG_CASES, ids=[f"{f}-{k}" for f, k in AGG_CASES])
+def test_accumulator_dispatch_edges(ctx, fun, kind, total, n):
+    """One batch on each side of the two thresholds, with and without a filter (its own NULLs included) and value NULLs, a few rows of no group:
+    (8, 71) k_acc_small, MIN / MAX k_acc_cached; (9, 71) and (300, 2399) k_acc_add_plain without filter and NULLs when the values are stored as the state type
+    (Int64, UInt64, Float64, Decimal128 sums, every COUNT), else k_acc_update_add, MIN / MAX k_acc_update (Decimal128: two passes); (9, 72) and (300, 2400)
+    k_acc_cached, PLAIN on the same condition -- MIN / MAX over Int64, Float64 too -- and Decimal128 MIN / MAX still k_acc_update."""
+    for use_filter in (False, True):
+        for nulls in (False, True):
+            v = rand_array(kind, n, 0.15 if nulls else 0, RNG)
+            acc, oacc = _acc_pair(ctx, fun, v)
+            filt = pa.array(RNG.random(n) < 0.7, mask=RNG.random(n) < 0.05) if use_filter else None
+            _update_both(ctx, acc, oacc, v, _ids(total, n), filt, total)
+            _check_acc(acc, oacc, _is_float_sum(fun, kind))
+
+
+@pytest.mark.parametrize("sequence", ["cache_then_combine", "registers_then_combine"])
+@pytest.mark.parametrize("fun,kind", AGG_CASES, ids=[f"{f}-{k}" for f, k in AGG_CASES])
+def test_accumulator_takes_two_paths_in_a_row(ctx, fun, kind, sequence):
+    """The same accumulator through two kernels in a row, then state -> merge -> evaluate.  cache_then_combine: 2400 rows over 300 groups (k_acc_cached), then 2399
+    (k_acc_add_plain / k_acc_update_add; MIN / MAX k_acc_update).  registers_then_combine: 71 rows over 8 groups (k_acc_small; MIN / MAX k_acc_cached), then the group
+    count grows to 300 under 500 rows (k_acc_add_plain / k_acc_update_add / k_acc_update).  Without and with value NULLs (plain and general kernels)."""
+    batches = [(300, 2400), (300, 2399)] if sequence == "cache_then_combine" else [(8, 71), (300, 500)]
+    floats = _is_float_sum(fun, kind)
+    for nulls in (False, True):
+        acc = oacc = None
+        for total, n in batches:
+            v = rand_array(kind, n, 0.15 if nulls else 0, RNG)
+            if acc is None:
+                acc, oacc = _acc_pair(ctx, fun, v)
+            _update_both(ctx, acc, oacc, v, _ids(total, n), None, total)
+        st, ost = _check_acc(acc, oacc, floats)
+        fin, ofin = _acc_pair(ctx, fun, v)
+        perm = RNG.permutation(300)
+        fin.merge_batch(st, ctx.from_arrow(pa.array(perm.astype(np.uint32))), None, 300)
+        ofin.merge_batch(ost, perm, None, 300)
+        _check_acc(fin, ofin, floats)
+
+
+def _merge_states(what, n, total, ids, scale):
+    """partial-state columns of n rows as a Partial stage emits them"""
+    if what == "count":
+        return [pa.array(RNG.integers(0, 1000, n).astype(np.int64))]
+    if what.startswith("avg"):
+        # group 0 meets only partial rows of a group whose argument was NULL in every row: count 0 and sum under NULL bits, as state() emits them
+        # avg_float64_no_nulls: no such rows and no validity bitmaps, so counts and sums both take the plain kernels
+        empty = (ids == 0) | (RNG.random(n) < 0.1) if what != "avg_float64_no_nulls" else np.zeros(n, dtype=bool)
+        counts = pa.array(np.where(empty, 0, RNG.integers(1, 50, n)).astype(np.uint64), mask=empty if empty.any() else None)
+        if what == "avg_float64_no_nulls":
+            return [counts, pa.array(RNG.normal(size=n) * 1e3)]
+        if what == "avg_float64":
+            return [counts, pa.array(np.where(empty, 0.0, RNG.normal(size=n) * 1e3), mask=empty)]
+        return [counts, pa.array([None if e else decimal.Decimal(int(x)).scaleb(-2) for e, x in zip(empty, RNG.integers(-10**12, 10**12, n))], type=pa.decimal128(25, 2))]
+    # MIN / MAX Decimal128: |value| < 10^15 (high word 0 or -1) in the first batch, up to 10^30 in the second -- the extreme's high word moves
+    return [pa.array([decimal.Decimal(int(x) * scale + int(y)) for x, y in zip(RNG.integers(-10**15, 10**15, n), RNG.integers(0, 10**15, n))], type=pa.decimal128(38, 0))]
+
+
+@pytest.mark.parametrize("total", [9, 300])
+@pytest.mark.parametrize("side", [-1, 0], ids=["below_8_per_group", "at_8_per_group"])
+@pytest.mark.parametrize("what", ["count", "avg_float64", "avg_float64_no_nulls", "avg_decimal", "min_decimal", "max_decimal"])
+def test_merge_dispatch_edges(ctx, what, side, total):
+    """merge_batch of two batches of n = 8 * total - 1 / 8 * total partial rows whose ids are a permutation of 0 .. total-1 repeated, the second one under a filter.
+    COUNT sums Int64 counts into its count array (below: k_acc_add_plain, at: k_acc_cached PLAIN; filtered: k_acc_update_add / k_acc_cached); AVG sums UInt64 counts
+    beside a scratch null state, then the sums into its own (NULL rows: k_acc_update_add / k_acc_cached; avg_float64_no_nulls, unfiltered: k_acc_add_plain / k_acc_cached
+    PLAIN for both); a group that only meets (count 0, NULL sum) rows stays NULL beside seen groups.  MIN / MAX Decimal128 merge like an update: k_acc_update and the two passes around it on either side, the extreme's high word moving."""
+    n = 8 * total + side
+    fun = {"count": "COUNT", "avg_float64": "AVG", "avg_float64_no_nulls": "AVG", "avg_decimal": "AVG", "min_decimal": "MIN", "max_decimal": "MAX"}[what]
+    in_type = {"count": pa.int64(), "avg_float64": pa.float64(), "avg_float64_no_nulls": pa.float64(), "avg_decimal": pa.decimal128(15, 2)}.get(what, pa.decimal128(38, 0))
+    acc, oacc = _acc_pair(ctx, fun, pa.array([], type=in_type))
+    for scale, use_filter in ((1, False), (10**15, True)):
+        ids = RNG.permutation(np.arange(n) % total)
+        st = _merge_states(what, n, total, ids, scale)
+        filt = pa.array(RNG.random(n) < 0.7, mask=RNG.random(n) < 0.05) if use_filter else None
+        acc.merge_batch([ctx.from_arrow(s) for s in st], ctx.from_arrow(pa.array(ids.astype(np.uint32))), ctx.from_arrow(filt) if use_filter else None, total)
+        oacc.merge_batch(st, ids, filt, total)
+        _check_acc(acc, oacc, what.startswith("avg_float64"))
+    if fun == "AVG" and what != "avg_float64_no_nulls":
+        assert acc.evaluate().to_arrow()[0].as_py() is None and acc.evaluate().to_arrow().null_count < total
+
+
+@pytest.mark.parametrize("bad", ["int32", "short"])
+def test_avg_merge_rejects_sums_of_another_type_or_length(ctx, bad):
+    """AVG's merge reads the partial sums as its state type: an Int32 column or one shorter than the batch answers INVALID_ARGUMENT before anything is merged -- the
+    counts are not added either -- and the accumulator takes a well-formed merge afterwards."""
+    import dfgpu
+    v = rand_array("float64", 500, 0.1, RNG)
+    acc, oacc = _acc_pair(ctx, "AVG", v)
+    g = RNG.integers(0, 20, 500)
+    _update_both(ctx, acc, oacc, v, g, None, 20)
+    counts = pa.array(RNG.integers(1, 9, 40).astype(np.uint64))
+    gids = ctx.from_arrow(pa.array((np.arange(40) % 20).astype(np.uint32)))
+    sums = pa.array(np.arange(40, dtype=np.int32)) if bad == "int32" else pa.array(RNG.normal(size=39))
+    with pytest.raises(dfgpu.DfgpuError) as e:
+        acc.merge_batch([ctx.from_arrow(counts), ctx.from_arrow(sums)], gids, None, 25)
+    assert e.value.kind == "InvalidArgument"
+    _check_acc(acc, oacc, True)                         # unchanged: still 20 groups, the counts not merged
+    good = pa.array(RNG.normal(size=40))
+    acc.merge_batch([ctx.from_arrow(counts), ctx.from_arrow(good)], gids, None, 25)
+    oacc.merge_batch([counts, good], np.arange(40) % 20, None, 25)
+    _check_acc(acc, oacc, True)
+
+
+@pytest.mark.parametrize("total,n", [(8, 71), (9, 71), (9, 72)])
+def test_count_skips_null_dictionary_values_on_every_path(ctx, total, n):
+    """COUNT(x) over a dictionary column whose codes are all valid but whose dictionary holds a NULL value: the rows of that code are NULL (logical nulls, count.rs:125)
+    whichever kernel takes the batch -- k_acc_small, k_acc_update_add (such a column is not "plain": k_acc_add_plain would count every row), k_acc_cached."""
+    col = pa.DictionaryArray.from_arrays(pa.array(RNG.integers(0, 3, n).astype(np.int32)), pa.array(["a", None, "b"], type=pa.utf8()))
+    import dfgpu
+    acc, oacc = dfgpu.GroupsAccumulator(ctx, KIND["COUNT"], dfgpu.capi.INT64), po.Acc("COUNT", pa.int64())
+    _update_both(ctx, acc, oacc, col, _ids(total, n), None, total)
+    _check_acc(acc, oacc, False)
+
+
+def test_update_with_rows_but_no_known_group_is_an_error_not_a_crash(ctx):
+    """total_num_groups = 0 with a non-empty batch: the accumulator has no state arrays yet.  k_acc_cached (MIN: 5 rows >= 8 * 0) reports every id as out of range;
+    k_acc_small (SUM) drops ids beyond the group count as it always does.  Neither touches a state array, and both accumulators work afterwards.  (What this guards
+    is host code: the launch once read a->counts->ptr of an accumulator without arrays, a null dereference on the host; no device fault is involved.)"""
+    import dfgpu
+    v, g = ctx.from_arrow(pa.array(np.arange(5, dtype=np.int64))), ctx.from_arrow(pa.array(np.zeros(5, dtype=np.uint32)))
+    mn, sm = dfgpu.GroupsAccumulator(ctx, KIND["MIN"], dfgpu.capi.INT64), dfgpu.GroupsAccumulator(ctx, KIND["SUM"], dfgpu.capi.INT64)
+    with pytest.raises(dfgpu.DfgpuError) as e:
+        mn.update_batch(v, g, None, 0)
+    assert "out of bounds" in str(e.value)
+    sm.update_batch(v, g, None, 0)
+    assert len(sm.evaluate().to_arrow()) == 0
+    mn.update_batch(v, g, None, 1)
+    sm.update_batch(v, g, None, 1)
+    assert mn.evaluate().to_arrow().to_pylist() == [0] and sm.evaluate().to_arrow().to_pylist() == [10]
