@@ -91,6 +91,8 @@ PROTOTYPES = {
     "dfgpu_ctx_stream": (_P, [_P]),
     "dfgpu_version": (C.c_char_p, []),
     "dfgpu_ctx_set_row_selection": (C.c_int32, [_P, _P]),
+    "dfgpu_ctx_push_row_selection": (C.c_int32, [_P, _P]),
+    "dfgpu_ctx_pop_row_selection": (C.c_int32, [_P]),
     "dfgpu_mask_count": (C.c_int32, [_P, _P, C.POINTER(C.c_int64)]),
     "dfgpu_profile_enable": (C.c_int32, [_P, C.c_int32]),
     "dfgpu_profile_select": (C.c_int32, [_P, C.c_char_p]),
@@ -125,6 +127,7 @@ PROTOTYPES = {
     "dfgpu_negative": (C.c_int32, [_P, _P, _PP]),
     "dfgpu_cast": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _PP]),
     "dfgpu_in_list": (C.c_int32, [_P, _P, _P, C.c_int32, _PP]),
+    "dfgpu_case": (C.c_int32, [_P, _PP, _PP, C.POINTER(C.c_int32), C.c_int32, _P, C.c_int32, _PP]),
     "dfgpu_join_build": (C.c_int32, [_P, _PP, C.c_int32, _P, C.c_int32, _PP]),
     "dfgpu_join_table_free": (None, [_P]),
     "dfgpu_join_table_num_rows": (C.c_int64, [_P]),
@@ -210,6 +213,7 @@ PROTOTYPES.update({
     "dfgpu_expr_negative": (C.c_int32, [_P, _PP]),
     "dfgpu_expr_cast": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, _PP]),
     "dfgpu_expr_in_list": (C.c_int32, [_P, _P, C.c_int32, _PP]),
+    "dfgpu_expr_case": (C.c_int32, [_P, _PP, _PP, C.c_int32, _P, _PP]),
     "dfgpu_expr_free": (None, [_P]),
     "dfgpu_plan_memory": (C.c_int32, [_PP, _I32P, C.c_int32, _PP]),
     "dfgpu_plan_memory_replace": (C.c_int32, [_P, _PP, _I32P, C.c_int32]),

@@ -513,8 +513,33 @@ dfgpu_status dfgpu_ctx_get_option(dfgpu_ctx* ctx, const char* key, int64_t* out)
 
 dfgpu_status dfgpu_ctx_set_row_selection(dfgpu_ctx* ctx, const dfgpu_array* mask) {
   return guard(ctx, [&] {
+    ctx->row_selection_stack.clear();                      // whatever was pushed narrowed the selection this call replaces
     if (!mask) { ctx->row_selection.reset(); ctx->row_selection_len = 0; return; }
     ctx->row_selection = effective_mask(ctx, mask, mask->length); ctx->row_selection_len = mask->length;
+  });
+}
+dfgpu_status dfgpu_ctx_push_row_selection(dfgpu_ctx* ctx, const dfgpu_array* mask) {
+  return guard(ctx, [&] {
+    if (!mask) fail(DFGPU_INVALID_ARGUMENT, "push_row_selection: null mask");
+    if (ctx->row_selection && ctx->row_selection_len != mask->length)
+      fail(DFGPU_INVALID_ARGUMENT, "push_row_selection: mask of %lld rows over a selection of %lld rows", (long long)mask->length, (long long)ctx->row_selection_len);
+    BufferPtr m = effective_mask(ctx, mask, mask->length);
+    if (ctx->row_selection) {
+      const int64_t nw = (mask->length + 63) / 64;
+      BufferPtr both = alloc_buffer(ctx, (size_t)nw * 8);
+      if (nw) hipLaunchKernelGGL(k_and_words, dim3(grid_for(nw, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)ctx->row_selection->ptr, (const uint64_t*)m->ptr, (uint64_t*)both->ptr, nw);
+      KERNEL_CHECK();
+      m = both;
+    }
+    ctx->row_selection_stack.emplace_back(ctx->row_selection, ctx->row_selection_len);
+    ctx->row_selection = m; ctx->row_selection_len = mask->length;
+  });
+}
+dfgpu_status dfgpu_ctx_pop_row_selection(dfgpu_ctx* ctx) {
+  return guard(ctx, [&] {
+    if (ctx->row_selection_stack.empty()) fail(DFGPU_INVALID_ARGUMENT, "pop_row_selection: nothing was pushed");
+    ctx->row_selection = ctx->row_selection_stack.back().first; ctx->row_selection_len = ctx->row_selection_stack.back().second;
+    ctx->row_selection_stack.pop_back();
   });
 }
 dfgpu_status dfgpu_mask_count(dfgpu_ctx* ctx, const dfgpu_array* mask, int64_t* out) {

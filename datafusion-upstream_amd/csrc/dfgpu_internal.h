@@ -69,6 +69,8 @@ struct dfgpu_ctx {
   // row selection of the running operator (dfgpu_ctx_set_row_selection): expression kernels evaluate every row of full-length
   // columns but raise errors only for selected rows
   std::shared_ptr<dfgpu::Buffer> row_selection; int64_t row_selection_len = 0;
+  // dfgpu_ctx_push_row_selection: the selections the pushed masks narrowed, innermost last (row_selection is always the effective one, so no kernel looks here)
+  std::vector<std::pair<std::shared_ptr<dfgpu::Buffer>, int64_t>> row_selection_stack;
   // kernel error flags (overflow, divide by zero, cast range, index bounds): checked after the raising call, or -- inside one
   // poll of a plan's output stream -- once before the batch is handed out (saves a stream sync per kernel-level call)
   int defer_flag_checks = 0; bool flags_pending = false; std::string flags_what;

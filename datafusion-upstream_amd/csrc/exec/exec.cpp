@@ -296,6 +296,78 @@ struct UnaryExpr : Expr {
   void columns(std::set<int>& out) const override { e->columns(out); }
 };
 
+static ArrayRef known_mask(const TaskContext& tc, const ArrayRef& m);
+struct CaseExpr : Expr {          // expressions/case.rs:64-120; evaluate :289-305
+  ExprPtr base, else_expr; std::vector<ExprPtr> whens, thens;       // thens[k] empty: the untyped NULL literal
+  // evaluate_selection (case.rs:147, :216): the pushed mask narrows the context's row selection until the guard goes, also when a child throws
+  struct Narrow {
+    dfgpu_ctx* c = nullptr;
+    Narrow(const TaskContext& tc, const ArrayRef& mask) { if (mask) { tc.check(dfgpu_ctx_push_row_selection(tc.ctx, mask.a)); c = tc.ctx; } }
+    ~Narrow() { if (c) dfgpu_ctx_pop_row_selection(c); }
+    Narrow(const Narrow&) = delete; Narrow& operator=(const Narrow&) = delete;
+  };
+  static ArrayRef bin(const TaskContext& tc, int op, const Value& x, const Value& y) {
+    dfgpu_array* o = nullptr; tc.check(dfgpu_binary(tc.ctx, op, x.arr.a, x.scalar, y.arr.a, y.scalar, &o)); return ArrayRef::adopt(o);
+  }
+  // WHEN k as a Boolean column: the condition itself, or base = when_k (case.rs:141-146; a NULL base gives NULL, which never matches)
+  ArrayRef when_column(const TaskContext& tc, Batch& b, size_t k, const Value& bv) const {
+    Value w = whens[k]->eval(tc, b);
+    if (base) w = Value{bin(tc, DFGPU_OP_EQ, bv, w), bv.scalar && w.scalar};
+    return into_array(tc, w, b.base_rows);
+  }
+  Value select(const TaskContext& tc, const std::vector<ArrayRef>& masks, const std::vector<Value>& tv, const Value& ev) const {
+    std::vector<const dfgpu_array*> wp, tp; std::vector<int32_t> ts;
+    for (size_t k = 0; k < masks.size(); k++) { wp.push_back(masks[k].a); tp.push_back(tv[k].arr.a); ts.push_back(tv[k].scalar ? 1 : 0); }
+    dfgpu_array* o = nullptr; tc.check(dfgpu_case(tc.ctx, wp.data(), tp.data(), ts.data(), (int32_t)wp.size(), ev.arr.a, ev.scalar ? 1 : 0, &o));
+    return Value{ArrayRef::adopt(o), false};
+  }
+  Value eval(const TaskContext& tc, Batch& b) const override {
+    const size_t nb = whens.size();
+    Value bv; if (base) bv = base->eval(tc, b);
+    std::vector<ArrayRef> masks(nb); std::vector<Value> tv(nb); Value ev;
+    bool all_safe = !else_expr || else_expr->safe();
+    for (size_t k = 0; k < nb; k++) all_safe = all_safe && whens[k]->safe() && (!thens[k] || thens[k]->safe());
+    if (all_safe) {               // nothing can raise: every child over every row, and the kernel finds the first match from the raw WHEN bitmaps
+      for (size_t k = 0; k < nb; k++) { masks[k] = when_column(tc, b, k, bv); if (thens[k]) tv[k] = thens[k]->eval(tc, b); }
+      if (else_expr) ev = else_expr->eval(tc, b);
+      return select(tc, masks, tv, ev);
+    }
+    // Some branch can raise: each child runs under the rows that reach it.  remainder = rows no branch has taken yet (empty: all of them); masks[k] = the rows
+    // branch k takes, disjoint, so the one select at the end sees the same first match.  No count is read back: under a selection an empty branch is no special case.
+    ArrayRef remainder, base_null;
+    if (base) {                   // only non-NULL base values are compared with the WHENs (case.rs:130-135); the NULL ones go to the ELSE (:180)
+      dfgpu_array_desc d; dfgpu_array_describe(bv.arr.a, &d);
+      if (d.validity || (d.dictionary && d.dictionary->validity)) {
+        dfgpu_array *isn = nullptr, *notn = nullptr;
+        tc.check(dfgpu_is_null(tc.ctx, bv.arr.a, 0, &isn)); base_null = into_array(tc, Value{ArrayRef::adopt(isn), bv.scalar}, b.base_rows);
+        tc.check(dfgpu_not(tc.ctx, base_null.a, &notn)); remainder = ArrayRef::adopt(notn);
+      }
+    }
+    for (size_t k = 0; k < nb; k++) {
+      ArrayRef w; { Narrow rows(tc, remainder); w = when_column(tc, b, k, bv); }
+      ArrayRef m = known_mask(tc, w);                                              // WHEN k IS TRUE
+      if (remainder) m = bin(tc, DFGPU_OP_AND, Value{m, false}, Value{remainder, false});
+      if (thens[k]) { Narrow rows(tc, m); tv[k] = thens[k]->eval(tc, b); }
+      dfgpu_array* nm = nullptr; tc.check(dfgpu_not(tc.ctx, m.a, &nm)); ArrayRef not_m = ArrayRef::adopt(nm);
+      remainder = remainder ? bin(tc, DFGPU_OP_AND, Value{remainder, false}, Value{not_m, false}) : not_m;
+      masks[k] = m;
+    }
+    if (base_null) remainder = bin(tc, DFGPU_OP_OR, Value{remainder, false}, Value{base_null, false});
+    Narrow rows(tc, remainder);       // kept over the select: the cast of an ELSE to the result type must not raise on rows a branch took either
+    if (else_expr) ev = else_expr->eval(tc, b);
+    return select(tc, masks, tv, ev);
+  }
+  bool safe() const override {
+    bool s = (!base || base->safe()) && (!else_expr || else_expr->safe());
+    for (size_t k = 0; k < whens.size(); k++) s = s && whens[k]->safe() && (!thens[k] || thens[k]->safe());
+    return s;
+  }
+  void columns(std::set<int>& out) const override {
+    if (base) base->columns(out); if (else_expr) else_expr->columns(out);
+    for (size_t k = 0; k < whens.size(); k++) { whens[k]->columns(out); if (thens[k]) thens[k]->columns(out); }
+  }
+};
+
 // ------------------------------------------------------------------ ExecutionPlan
 struct Stream { virtual ~Stream() = default; virtual bool next(Batch& out) = 0; };     // poll_next: false = end of stream
 struct Plan;
@@ -2169,6 +2241,17 @@ dfgpu_status dfgpu_expr_is_null(const dfgpu_expr* e, int32_t negated, dfgpu_expr
 dfgpu_status dfgpu_expr_negative(const dfgpu_expr* e, dfgpu_expr** out) { return unary(e, 3, 0, 0, 0, nullptr, out); }
 dfgpu_status dfgpu_expr_cast(const dfgpu_expr* e, int32_t t, int32_t p, int32_t s, dfgpu_expr** out) { return unary(e, 4, t, p, s, nullptr, out); }
 dfgpu_status dfgpu_expr_in_list(const dfgpu_expr* e, const dfgpu_array* list, int32_t negated, dfgpu_expr** out) { return unary(e, negated ? 6 : 5, 0, 0, 0, list, out); }
+dfgpu_status dfgpu_expr_case(const dfgpu_expr* base, const dfgpu_expr* const* whens, const dfgpu_expr* const* thens, int32_t n, const dfgpu_expr* else_expr, dfgpu_expr** out) {
+  return guard([&] {
+    if (!whens || !thens || !out) fail(DFGPU_INVALID_ARGUMENT, "expr_case: null argument");
+    if (n < 1) fail(DFGPU_INVALID_ARGUMENT, "There must be at least one WHEN clause");
+    auto c = std::make_shared<CaseExpr>();
+    if (base) c->base = base->e;
+    if (else_expr) c->else_expr = else_expr->e;
+    for (int k = 0; k < n; k++) { c->whens.push_back(ex(whens[k])); c->thens.push_back(thens[k] ? thens[k]->e : ExprPtr()); }
+    *out = new dfgpu_expr{c};
+  });
+}
 void dfgpu_expr_free(dfgpu_expr* e) { delete e; }
 
 dfgpu_status dfgpu_plan_memory(const dfgpu_batch* const* batches, const int32_t* sizes, int32_t nparts, dfgpu_plan** out) {

@@ -351,10 +351,196 @@ __global__ void __launch_bounds__(BLOCK) k_in_list(ColView c, ColView list, int6
   if (lane_id() == 0 && (i >> 6) < ((n + 63) >> 6)) { out_bits[i >> 6] = mv; out_valid[i >> 6] = mo; }
 }
 
+// ---------------------------------------------------------------- CASE WHEN: first matching branch per row (case.rs:125-259)
+// One launch takes up to 8 WHEN / THEN pairs and the ELSE; longer CASEs are chained on the host (dfgpu_case).  A WHEN is a bitmap (value words, optional
+// validity words: NULL counts as false).  An operand (THEN k, ELSE) is a column, one cell read at row 0, or absent (the untyped NULL literal / no ELSE).
+constexpr int CASE_BRANCHES = 8;
+enum : int32_t { CASE_ABSENT = 0, CASE_COLUMN = 1, CASE_SCALAR = 2 };
+struct CaseArgs {
+  int32_t nb, else_kind;
+  const uint64_t* when_v[CASE_BRANCHES]; const uint64_t* when_ok[CASE_BRANCHES];
+  const void* then_v[CASE_BRANCHES]; const uint64_t* then_ok[CASE_BRANCHES]; int32_t then_kind[CASE_BRANCHES];
+  const void* else_v; const uint64_t* else_ok;
+  uint32_t then_base[CASE_BRANCHES], else_base;      // k_case_index: first row of the operand in the concatenation of the operands
+};
+// the rows of 64-row group g that exist: in a view the bits past `n` in the last word of a bitmap are the parent's live bits
+__device__ inline uint64_t case_live(int64_t g, int64_t n) { const int64_t left = n - (g << 6); return left >= 64 ? ~0ull : (left <= 0 ? 0ull : (1ull << left) - 1ull); }
+// m[k]: the rows of group g that take branch k (the first WHEN that is valid and true); returns the rows no branch took.  Everything here is the same in
+// every lane of a wave that works on one group: the words are loaded once per group and the masks live in scalar registers.
+__device__ inline uint64_t case_match(const CaseArgs& a, int64_t g, uint64_t live, uint64_t* m) {
+  uint64_t rest = live;
+#pragma unroll
+  for (int k = 0; k < CASE_BRANCHES; k++) {
+    m[k] = 0;
+    if (k < a.nb) { uint64_t w = a.when_v[k][g]; if (a.when_ok[k]) w &= a.when_ok[k][g]; m[k] = w & rest; rest &= ~m[k]; }
+  }
+  return rest;
+}
+// validity / Boolean value word of an operand for group g
+__device__ inline uint64_t case_ok_word(int32_t kind, const uint64_t* ok, int64_t g) {
+  if (kind == CASE_ABSENT) return 0ull;
+  if (!ok) return ~0ull;
+  return kind == CASE_SCALAR ? ((ok[0] & 1ull) ? ~0ull : 0ull) : ok[g];
+}
+__device__ inline uint64_t case_bit_word(int32_t kind, const void* v, int64_t g) {
+  if (kind == CASE_ABSENT) return 0ull;
+  return kind == CASE_SCALAR ? ((((const uint64_t*)v)[0] & 1ull) ? ~0ull : 0ull) : ((const uint64_t*)v)[g];
+}
+
+// Fixed-width results.  T is an unsigned integer of the element width (the value is moved, never interpreted); 16-byte elements move as one 16-byte load when
+// every value pointer is 16-byte aligned (Case16) and as two 8-byte loads otherwise (Case16u: a view, or imported memory, is aligned to 8 bytes only).
+// One wave owns case_rows<T>() consecutive 64-row groups, one row per lane and group.  A lane loads from the operand of ITS branch only -- its source address is
+// picked with the masks first -- so a branch no row of the group took costs no load, and the loads of the whole chunk are issued before the first store.
+// FULL (the whole chunk inside n) is compile-time, as in k_compare_scalar_fast: the tail variant's bounds checks would put a wait behind every load.
+struct alignas(16) Case16 { uint64_t lo, hi; };
+struct Case16u { uint64_t lo, hi; };
+template <typename T> constexpr int case_rows() { return sizeof(T) >= 16 ? 4 : 8; }
+template <typename T, bool FULL>
+__device__ inline void case_select_chunk(const CaseArgs& a, int64_t n, T* out, uint64_t* out_ok, int64_t g0, int lane) {
+  constexpr int ROWS = case_rows<T>();
+  const T* src[ROWS]; uint64_t okw[ROWS], rest[ROWS];         // rest: the rows of each group no branch has taken yet (wave-uniform, like okw)
+#pragma unroll
+  for (int r = 0; r < ROWS; r++) { rest[r] = FULL ? ~0ull : case_live(g0 + r, n); src[r] = nullptr; okw[r] = 0; }
+  for (int k = 0; k < a.nb; k++) {
+    const uint64_t* wv = a.when_v[k] + g0; const uint64_t* wo = a.when_ok[k] ? a.when_ok[k] + g0 : nullptr;       // the chunk's words of one WHEN lie side by side
+    const int32_t kind = a.then_kind[k]; const T* tv = (const T*)a.then_v[k]; const uint64_t* tok = a.then_ok[k];
+    uint64_t m[ROWS];
+#pragma unroll
+    for (int r = 0; r < ROWS; r++) {
+      uint64_t w = 0;
+      if (FULL || rest[r]) { w = wv[r]; if (wo) w &= wo[r]; }             // the tail variant reads no word past the bitmap: rest is 0 there
+      m[r] = w & rest[r]; rest[r] &= ~m[r];
+    }
+#pragma unroll
+    for (int r = 0; r < ROWS; r++) if (m[r]) {                           // wave-uniform: a branch no row of the group took costs nothing more
+      if ((m[r] >> lane) & 1ull) src[r] = kind == CASE_ABSENT ? nullptr : tv + (kind == CASE_SCALAR ? 0 : ((g0 + r) << 6) + lane);
+      okw[r] |= m[r] & case_ok_word(kind, tok, g0 + r);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < ROWS; r++) if (rest[r]) {
+    if ((rest[r] >> lane) & 1ull) src[r] = a.else_kind == CASE_ABSENT ? nullptr : (const T*)a.else_v + (a.else_kind == CASE_SCALAR ? 0 : ((g0 + r) << 6) + lane);
+    okw[r] |= rest[r] & case_ok_word(a.else_kind, a.else_ok, g0 + r);
+  }
+  T x[ROWS];
+#pragma unroll
+  for (int r = 0; r < ROWS; r++) x[r] = src[r] ? *src[r] : T{};          // a NULL row keeps defined bytes
+#pragma unroll
+  for (int r = 0; r < ROWS; r++) {
+    const int64_t g = g0 + r, i = (g << 6) + lane;
+    if (FULL || i < n) out[i] = x[r];
+    if (out_ok && lane == 0 && (FULL || (g << 6) < n)) out_ok[g] = okw[r];
+  }
+}
+template <typename T>
+__global__ void __launch_bounds__(BLOCK) k_case_select(CaseArgs a, int64_t n, T* out, uint64_t* out_ok) {
+  const int lane = lane_id();
+  const int64_t g0 = ((int64_t)blockIdx.x * (BLOCK / WAVE) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * case_rows<T>();
+  if (((g0 + case_rows<T>()) << 6) <= n) case_select_chunk<T, true>(a, n, out, out_ok, g0, lane);
+  else if ((g0 << 6) < n) case_select_chunk<T, false>(a, n, out, out_ok, g0, lane);
+}
+// Boolean results: values are bits, so a whole group is word arithmetic on the masks -- one lane per 64 rows, no ballot to take.  Bits past n stay zero.
+__global__ void __launch_bounds__(BLOCK) k_case_select_bits(CaseArgs a, int64_t n, uint64_t* out, uint64_t* out_ok) {
+  const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  const uint64_t live = case_live(g, n);
+  if (!live) return;
+  uint64_t m[CASE_BRANCHES]; const uint64_t rest = case_match(a, g, live, m);
+  uint64_t v = rest & case_bit_word(a.else_kind, a.else_v, g), ok = rest & case_ok_word(a.else_kind, a.else_ok, g);
+#pragma unroll
+  for (int k = 0; k < CASE_BRANCHES; k++) if (m[k]) { v |= m[k] & case_bit_word(a.then_kind[k], a.then_v[k], g); ok |= m[k] & case_ok_word(a.then_kind[k], a.then_ok[k], g); }
+  out[g] = v & ok;
+  if (out_ok) out_ok[g] = ok;
+}
+// Utf8 / list / dictionary results: the same first match as one UInt32 row number into the concatenation of the operands (dfgpu_take gathers the result);
+// a row that takes the NULL literal, or no branch without an ELSE, gets a NULL index.
+__global__ void __launch_bounds__(BLOCK) k_case_index(CaseArgs a, int64_t n, uint32_t* out, uint64_t* out_ok) {
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x, g = i >> 6;
+  const int lane = lane_id();
+  const uint64_t live = case_live(g, n);
+  if (!live) return;
+  uint64_t m[CASE_BRANCHES]; const uint64_t rest = case_match(a, g, live, m);
+  uint32_t idx = 0; uint64_t ok = a.else_kind == CASE_ABSENT ? 0ull : rest;
+  if ((rest >> lane) & 1ull) idx = a.else_kind == CASE_COLUMN ? a.else_base + (uint32_t)i : a.else_base;
+#pragma unroll
+  for (int k = 0; k < CASE_BRANCHES; k++) if (m[k]) {
+    if ((m[k] >> lane) & 1ull) idx = a.then_kind[k] == CASE_COLUMN ? a.then_base[k] + (uint32_t)i : a.then_base[k];
+    if (a.then_kind[k] != CASE_ABSENT) ok |= m[k];
+  }
+  if (i < n) out[i] = idx;
+  if (out_ok && lane == 0) out_ok[g] = ok;
+}
+
 static bool may_have_nulls(const dfgpu_array* a) { return a->validity != nullptr || (a->dictionary && a->dictionary->validity != nullptr); }
 static Operand make_operand(const dfgpu_array* a, int scalar) {
   if (scalar && a->length != 1) fail(DFGPU_INVALID_ARGUMENT, "scalar operand must have length 1");
   return Operand{ make_view(a), scalar ? 1 : 0 };
+}
+
+// ---- CASE.  data_type() (case.rs:268-286): the type of the first THEN that is not the untyped NULL, else the ELSE's
+struct CaseType { int32_t type, logical, precision, scale, key_type; };
+static CaseType case_type_of(const dfgpu_array* a) {
+  const dfgpu_array* d = a->type == DFGPU_DICTIONARY ? a->dictionary : a;
+  return CaseType{a->type, d->type, d->precision, d->scale, a->type == DFGPU_DICTIONARY ? a->key_type : 0};
+}
+static bool case_same_type(const CaseType& x, const CaseType& y) {
+  return x.type == y.type && x.logical == y.logical && x.key_type == y.key_type && (x.logical != DFGPU_DECIMAL128 || (x.precision == y.precision && x.scale == y.scale));
+}
+static int32_t case_kind(const dfgpu_array* a, int scalar) { return !a ? CASE_ABSENT : (scalar ? CASE_SCALAR : CASE_COLUMN); }
+template <typename T>
+static void launch_case_select(dfgpu_ctx* ctx, const CaseArgs& a, int64_t n, void* out, uint64_t* out_ok) {
+  hipLaunchKernelGGL((k_case_select<T>), dim3(grid_for(n, BLOCK * case_rows<T>())), dim3(BLOCK), 0, ctx->stream, a, n, (T*)out, out_ok);
+}
+// one launch: at most CASE_BRANCHES branches over operands that all have the result type
+static dfgpu_array* case_launch(dfgpu_ctx* ctx, const dfgpu_array* const* whens, const dfgpu_array* const* thens, const int32_t* then_is_scalar, int nb,
+                                const dfgpu_array* els, int else_is_scalar, const CaseType& rt, int64_t n) {
+  CaseArgs a{}; a.nb = nb; a.else_kind = case_kind(els, else_is_scalar);
+  bool some_absent = !els, some_nullable = els && els->validity;
+  for (int k = 0; k < nb; k++) {
+    a.when_v[k] = (const uint64_t*)whens[k]->values->ptr; a.when_ok[k] = whens[k]->validity ? (const uint64_t*)whens[k]->validity->ptr : nullptr;
+    a.then_kind[k] = case_kind(thens[k], then_is_scalar && then_is_scalar[k]);
+    if (!thens[k]) { some_absent = true; continue; }
+    a.then_v[k] = thens[k]->values ? thens[k]->values->ptr : nullptr; a.then_ok[k] = thens[k]->validity ? (const uint64_t*)thens[k]->validity->ptr : nullptr;
+    some_nullable |= thens[k]->validity != nullptr;
+  }
+  if (els) { a.else_v = els->values ? els->values->ptr : nullptr; a.else_ok = els->validity ? (const uint64_t*)els->validity->ptr : nullptr; }
+  if (rt.type != DFGPU_UTF8 && rt.type != DFGPU_DICTIONARY) {
+    const bool need_ok = some_absent || some_nullable;
+    ArrayHolder h(new_fixed(ctx, rt.type, n, rt.precision, rt.scale, need_ok));
+    void* o = h.get()->values->ptr; uint64_t* ok = need_ok ? (uint64_t*)h.get()->validity->ptr : nullptr;
+    if (n) {
+      KernelTimer kt_(ctx, "k_case_select");
+      bool aligned16 = ((uintptr_t)o & 15) == 0 && ((uintptr_t)a.else_v & 15) == 0;
+      for (int k = 0; k < nb; k++) aligned16 = aligned16 && ((uintptr_t)a.then_v[k] & 15) == 0;
+      switch (rt.type == DFGPU_BOOL ? 0 : type_width(rt.type)) {
+        case 0: hipLaunchKernelGGL(k_case_select_bits, dim3(grid_for((n + 63) / 64, BLOCK)), dim3(BLOCK), 0, ctx->stream, a, n, (uint64_t*)o, ok); break;
+        case 1: launch_case_select<uint8_t>(ctx, a, n, o, ok); break;
+        case 2: launch_case_select<uint16_t>(ctx, a, n, o, ok); break;
+        case 4: launch_case_select<uint32_t>(ctx, a, n, o, ok); break;
+        case 8: launch_case_select<uint64_t>(ctx, a, n, o, ok); break;
+        default: if (aligned16) launch_case_select<Case16>(ctx, a, n, o, ok); else launch_case_select<Case16u>(ctx, a, n, o, ok); break;
+      }
+      KERNEL_CHECK();
+    }
+    if (need_ok) h.get()->null_count = -1;
+    return h.release();
+  }
+  // variable-width and dictionary results: row numbers into the concatenation of the operands, then one gather
+  std::vector<const dfgpu_array*> parts; int64_t rows = 0;
+  for (int k = 0; k < nb; k++) if (thens[k]) { a.then_base[k] = (uint32_t)rows; parts.push_back(thens[k]); rows += thens[k]->length; }
+  if (els) { a.else_base = (uint32_t)rows; parts.push_back(els); rows += els->length; }
+  if (rows > 0xFFFFFFF0ll) fail(DFGPU_NOT_IMPLEMENTED, "case: operands above 2^32-16 rows");
+  ArrayHolder idx(new_fixed(ctx, DFGPU_UINT32, n, 0, 0, some_absent));
+  if (n) {
+    KernelTimer kt_(ctx, "k_case_index");
+    hipLaunchKernelGGL(k_case_index, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, a, n, (uint32_t*)idx.get()->values->ptr, some_absent ? (uint64_t*)idx.get()->validity->ptr : nullptr);
+    KERNEL_CHECK();
+  }
+  if (some_absent) idx.get()->null_count = -1;
+  ArrayHolder cat;
+  if (parts.size() > 1) { dfgpu_status st = dfgpu_concat(ctx, parts.data(), (int32_t)parts.size(), &cat.a); if (st != DFGPU_OK) fail(st, "%s", ctx->err.c_str()); }
+  dfgpu_array* res = nullptr;
+  dfgpu_status st = dfgpu_take(ctx, cat.get() ? cat.get() : parts[0], idx.get(), &res); if (st != DFGPU_OK) fail(st, "%s", ctx->err.c_str());
+  return res;
 }
 
 }  // namespace dfgpu
@@ -571,6 +757,54 @@ dfgpu_status dfgpu_in_list(dfgpu_ctx* ctx, const dfgpu_array* a, const dfgpu_arr
                                       (uint64_t*)h.get()->values->ptr, (uint64_t*)h.get()->validity->ptr);
     KERNEL_CHECK(); h.get()->null_count = -1;
     *out = h.release();
+  });
+}
+
+dfgpu_status dfgpu_case(dfgpu_ctx* ctx, const dfgpu_array* const* whens, const dfgpu_array* const* thens, const int32_t* then_is_scalar, int32_t n_branches,
+                        const dfgpu_array* else_value, int32_t else_is_scalar, dfgpu_array** out) {
+  return guard(ctx, [&] {
+    if (!whens || !thens || !out) fail(DFGPU_INVALID_ARGUMENT, "case: null argument");
+    if (n_branches < 1) fail(DFGPU_INVALID_ARGUMENT, "case: There must be at least one WHEN clause");
+    if (!whens[0]) fail(DFGPU_INVALID_ARGUMENT, "case: null WHEN");
+    const int64_t n = whens[0]->length;
+    const dfgpu_array* typed = nullptr;
+    for (int k = 0; k < n_branches; k++) {
+      const dfgpu_array* w = whens[k]; const dfgpu_array* t = thens[k];
+      if (!w) fail(DFGPU_INVALID_ARGUMENT, "case: null WHEN");
+      if (w->type != DFGPU_BOOL) fail(DFGPU_INVALID_ARGUMENT, "case: WHEN %d is not a Boolean array (type %d)", k, w->type);
+      if (w->length != n) fail(DFGPU_INVALID_ARGUMENT, "case: WHEN %d has %lld rows, expected %lld", k, (long long)w->length, (long long)n);
+      if (!t) continue;
+      const int64_t want = then_is_scalar && then_is_scalar[k] ? 1 : n;
+      if (t->length != want) fail(DFGPU_INVALID_ARGUMENT, "case: THEN %d has %lld rows, expected %lld", k, (long long)t->length, (long long)want);
+      if (!typed) typed = t;
+    }
+    if (else_value && else_value->length != (else_is_scalar ? 1 : n)) fail(DFGPU_INVALID_ARGUMENT, "case: ELSE has %lld rows, expected %lld", (long long)else_value->length, (long long)(else_is_scalar ? 1 : n));
+    if (!typed) typed = else_value;
+    if (!typed) fail(DFGPU_INVALID_ARGUMENT, "case: every THEN and the ELSE is the untyped NULL literal, so the result has no type");
+    const CaseType rt = case_type_of(typed);
+    for (int k = 0; k < n_branches; k++) {
+      if (!thens[k]) continue;
+      const CaseType t = case_type_of(thens[k]);
+      if (case_same_type(t, rt)) continue;
+      if (t.type == rt.type && t.logical == rt.logical && rt.logical == DFGPU_DECIMAL128)
+        fail(DFGPU_INVALID_ARGUMENT, "case: THEN %d is Decimal128(%d, %d), expected Decimal128(%d, %d); the planner coerces first", k, t.precision, t.scale, rt.precision, rt.scale);
+      fail(DFGPU_INVALID_ARGUMENT, "case: THEN %d has type %d, expected %d; the planner coerces first", k, t.logical, rt.logical);
+    }
+    ArrayHolder casted;                                     // try_cast of the ELSE to the return type (case.rs:177, :250)
+    if (else_value && !case_same_type(case_type_of(else_value), rt)) {
+      if (rt.type == DFGPU_UTF8 || rt.type == DFGPU_DICTIONARY) fail(DFGPU_NOT_IMPLEMENTED, "case: cast of the ELSE (type %d) to result type %d", logical_type(else_value), rt.type);
+      dfgpu_status st = dfgpu_cast(ctx, else_value, rt.logical, rt.precision, rt.scale, &casted.a); if (st != DFGPU_OK) fail(st, "%s", ctx->err.c_str());
+      else_value = casted.get();
+    }
+    // more than CASE_BRANCHES branches: CASE w1..w8 ELSE (CASE w9..w16 ELSE e) is the same expression, so the launches run back to front and each result is
+    // the ELSE column of the launch in front of it
+    std::vector<ArrayHolder> results;
+    for (int first = ((n_branches - 1) / CASE_BRANCHES) * CASE_BRANCHES; first >= 0; first -= CASE_BRANCHES) {
+      const int nb = n_branches - first < CASE_BRANCHES ? n_branches - first : CASE_BRANCHES;
+      results.emplace_back(case_launch(ctx, whens + first, thens + first, then_is_scalar ? then_is_scalar + first : nullptr, nb, else_value, else_is_scalar, rt, n));
+      else_value = results.back().get(); else_is_scalar = 0;
+    }
+    *out = results.back().release();
   });
 }
 

@@ -230,6 +230,25 @@ class Context:
         self.check(self.lib.dfgpu_in_list(self.h, a.h, lst.h, int(negated), C.byref(out)))
         return self._wrap(out)
 
+    def case(self, whens: Sequence["Array"], thens: Sequence[Optional["Array"]], else_: Optional["Array"] = None,
+             then_scalar: Optional[Sequence[bool]] = None, else_scalar: bool = False) -> "Array":
+        """dfgpu_case: row i takes thens[k][i] of the first k whose whens[k][i] is true and not NULL, else else_[i], else NULL.
+        thens[k] None = the untyped NULL literal; then_scalar[k] / else_scalar mark length-1 operands."""
+        n = len(whens)
+        wh = (C.c_void_p * max(n, 1))(*[w.h.value for w in whens])
+        th = (C.c_void_p * max(n, 1))(*[(t.h.value if t is not None else None) for t in thens])
+        ts = (C.c_int32 * max(n, 1))(*[int(bool(x)) for x in (then_scalar if then_scalar is not None else [False] * n)])
+        out = C.c_void_p()
+        self.check(self.lib.dfgpu_case(self.h, wh, th, ts, n, else_.h if else_ is not None else None, int(else_scalar), C.byref(out)))
+        return self._wrap(out)
+
+    def push_row_selection(self, mask: "Array"):
+        """dfgpu_ctx_push_row_selection: narrow the row selection to (current AND mask) until pop_row_selection"""
+        self.check(self.lib.dfgpu_ctx_push_row_selection(self.h, mask.h if mask is not None else None))
+
+    def pop_row_selection(self):
+        self.check(self.lib.dfgpu_ctx_pop_row_selection(self.h))
+
     # ---- a13 / a14
     def sort_to_indices(self, cols: Sequence["Array"], descending: Sequence[bool], nulls_first: Sequence[bool], fetch: Optional[int] = None) -> "Array":
         hs, n = capi.handle_array([a.h.value for a in cols])

@@ -231,6 +231,27 @@ class InListExpr(PhysicalExpr):
         return _ExprH(out)
 
 
+class CaseExpr(PhysicalExpr):
+    """CASE [base] WHEN w THEN t ... [ELSE e] END (expressions/case.rs).  when_then: (when, then) pairs; a `then` that is None, or a
+    Literal of pyarrow's null type, is the untyped NULL literal."""
+
+    def __init__(self, base: Optional[PhysicalExpr], when_then: Sequence[Tuple[PhysicalExpr, Optional[PhysicalExpr]]], else_expr: Optional[PhysicalExpr] = None):
+        self.base, self.when_then, self.else_expr = base, list(when_then), else_expr
+        self.children = [e for pair in self.when_then for e in pair if isinstance(e, PhysicalExpr)]      # what collect_columns walks
+
+    @staticmethod
+    def _untyped_null(e) -> bool:
+        import pyarrow as pa
+        return e is None or (isinstance(e, Literal) and e.value is None and e.pa_type == pa.null())
+
+    def _build(self, ctx):
+        opt = lambda e: None if self._untyped_null(e) else e.handle(ctx).h
+        out = C.c_void_p()
+        _check(_lib().dfgpu_expr_case(opt(self.base), _ptrs([w.handle(ctx).h for w, _ in self.when_then]), _ptrs([opt(t) for _, t in self.when_then]),
+                                      len(self.when_then), opt(self.else_expr), C.byref(out)))
+        return _ExprH(out)
+
+
 # ----------------------------------------------------------------------------- ExecutionPlan builders
 class Partitioning:
     def __init__(self, kind: str, n: int, exprs: Optional[List[PhysicalExpr]] = None):

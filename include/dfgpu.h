@@ -152,6 +152,12 @@ DFGPU_API void *dfgpu_ctx_stream(dfgpu_ctx *ctx);
  * raise ArrowError conditions (overflow, divide by zero, cast range) only for selected rows; values of unselected rows are
  * unspecified and must stay behind the selection.  NULL clears it.  dfgpu_mask_count = number of true bits. */
 DFGPU_API dfgpu_status dfgpu_ctx_set_row_selection(dfgpu_ctx *ctx, const dfgpu_array *mask);
+/* PhysicalExpr::evaluate_selection (physical-expr-common physical_expr.rs, as CaseExpr uses it, case.rs:147-152, :216-224): narrow the row selection to
+ * (current selection AND mask; NULL in the mask counts as false) until the matching pop; with no selection set, to the mask.  The selections nest as a
+ * stack whose bottom is what dfgpu_ctx_set_row_selection set: set replaces the bottom and drops everything pushed (NULL clears all of it).  A NULL mask,
+ * a mask that is not Boolean or whose length differs from the current selection's, and a pop with nothing pushed are DFGPU_INVALID_ARGUMENT. */
+DFGPU_API dfgpu_status dfgpu_ctx_push_row_selection(dfgpu_ctx *ctx, const dfgpu_array *mask);
+DFGPU_API dfgpu_status dfgpu_ctx_pop_row_selection(dfgpu_ctx *ctx);
 DFGPU_API dfgpu_status dfgpu_mask_count(dfgpu_ctx *ctx, const dfgpu_array *mask, int64_t *out);
 DFGPU_API const char *dfgpu_version(void);
 /* Per-kernel device time measured with HIP events on the ctx stream (used by bench.py for the roofline
@@ -279,6 +285,19 @@ DFGPU_API dfgpu_status dfgpu_is_null(dfgpu_ctx *ctx, const dfgpu_array *a, int32
 DFGPU_API dfgpu_status dfgpu_negative(dfgpu_ctx *ctx, const dfgpu_array *a, dfgpu_array **out);            /* negative.rs:79 */
 DFGPU_API dfgpu_status dfgpu_cast(dfgpu_ctx *ctx, const dfgpu_array *a, int32_t to_type, int32_t precision, int32_t scale, dfgpu_array **out); /* cast.rs:121 */
 DFGPU_API dfgpu_status dfgpu_in_list(dfgpu_ctx *ctx, const dfgpu_array *a, const dfgpu_array *list, int32_t negated, dfgpu_array **out);      /* in_list.rs:349 */
+/* The row-wise part of CaseExpr::evaluate: what case_when_no_expr (case.rs:197-259) and case_when_with_expr (:125-188) build with one `zip` per branch, in
+ * one pass.  Row i takes thens[k][i] of the first k whose whens[k][i] is valid and true, else else_value[i], else NULL; its validity is that of the value
+ * it took.  For the form with a base expression the caller passes whens[k] = (base = when_k), which is NULL -- no match -- for a NULL base.
+ * whens[k]: BOOL arrays of one length n (NULL = false).  thens[k]: array of length n, or length 1 with then_is_scalar[k] (then_is_scalar may be NULL: all
+ * columns), or a NULL pointer = the untyped NULL literal.  else_value may be NULL (no ELSE).  n_branches >= 1.
+ * Result type = data_type() (case.rs:268-286): the type of the first THEN that is not the untyped NULL, else the ELSE's; every THEN must have it (Decimal128:
+ * with the same precision and scale), and an ELSE of another type is cast to it with dfgpu_cast (the try_cast of case.rs:177 / :250).  Anything else --
+ * also a CASE whose every THEN and ELSE is the untyped NULL, a WHEN that is not Boolean or of another length -- is DFGPU_INVALID_ARGUMENT before anything
+ * is launched.  Utf8, list and dictionary results are gathered from the concatenation of the operands: what dfgpu_concat or dfgpu_take decline
+ * (dictionaries that do not share their parent) comes back as DFGPU_NOT_IMPLEMENTED.  The operands are evaluated by the caller; short-circuit evaluation
+ * of branches that can raise is the plan layer's part (dfgpu_expr_case, over dfgpu_ctx_push_row_selection). */
+DFGPU_API dfgpu_status dfgpu_case(dfgpu_ctx *ctx, const dfgpu_array *const *whens, const dfgpu_array *const *thens, const int32_t *then_is_scalar,
+                                  int32_t n_branches, const dfgpu_array *else_value, int32_t else_is_scalar, dfgpu_array **out);
 
 /* ------------------------------------------------------------------ a2-a6: HashJoinExec */
 enum { DFGPU_JOIN_INNER = 0, DFGPU_JOIN_LEFT = 1, DFGPU_JOIN_RIGHT = 2, DFGPU_JOIN_FULL = 3,

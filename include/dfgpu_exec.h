@@ -50,6 +50,11 @@ DFGPU_API dfgpu_status dfgpu_expr_is_null(const dfgpu_expr *e, int32_t negated, 
 DFGPU_API dfgpu_status dfgpu_expr_negative(const dfgpu_expr *e, dfgpu_expr **out);
 DFGPU_API dfgpu_status dfgpu_expr_cast(const dfgpu_expr *e, int32_t to_type, int32_t precision, int32_t scale, dfgpu_expr **out);
 DFGPU_API dfgpu_status dfgpu_expr_in_list(const dfgpu_expr *e, const dfgpu_array *list, int32_t negated, dfgpu_expr **out);
+/* CaseExpr (case.rs:64-120): base may be NULL (CASE WHEN cond ...; with a base, WHEN k matches where base = when_k); else_expr may be NULL; n >= 1
+ * ("There must be at least one WHEN clause").  thens[k] may be NULL: the untyped NULL literal.  Branches are evaluated as the reference evaluates them
+ * (evaluate_selection): WHEN k can raise only on rows no earlier branch took, THEN k only on the rows of branch k, the ELSE only on the rest. */
+DFGPU_API dfgpu_status dfgpu_expr_case(const dfgpu_expr *base, const dfgpu_expr *const *whens, const dfgpu_expr *const *thens, int32_t n,
+                                       const dfgpu_expr *else_expr, dfgpu_expr **out);
 DFGPU_API void dfgpu_expr_free(dfgpu_expr *e);
 
 /* ---- ExecutionPlan nodes */
