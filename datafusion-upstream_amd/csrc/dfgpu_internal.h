@@ -243,6 +243,9 @@ inline const uint64_t* row_selection_words(dfgpu_ctx* ctx, int64_t n) { return c
 void launch_iota_u32(dfgpu_ctx* ctx, uint32_t* out, int64_t n, uint32_t start);
 void launch_set_bits_prefix(dfgpu_ctx* ctx, uint64_t* bits, int64_t m);   // bits[0..m) = 1
 
+// expr.hip: a Boolean result per dictionary entry (`dres`) mapped through the codes of the dictionary column `dcol`
+dfgpu_array* dict_predicate_map(dfgpu_ctx* ctx, const dfgpu_array* dcol, const dfgpu_array* dres);
+
 // hash.hip
 void hash_keys_device(dfgpu_ctx* ctx, const dfgpu_array* const* cols, int32_t k, uint64_t seed, uint64_t* out);
 

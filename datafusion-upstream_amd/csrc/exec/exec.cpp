@@ -368,6 +368,18 @@ struct CaseExpr : Expr {          // expressions/case.rs:64-120; evaluate :289-3
   }
 };
 
+struct LikeExpr : Expr {          // expressions/like.rs:103; evaluate -> arrow-string like / ilike / nlike / nilike
+  ExprPtr e, pattern; bool negated = false, case_insensitive = false;
+  Value eval(const TaskContext& tc, Batch& b) const override {
+    Value x = e->eval(tc, b), p = pattern->eval(tc, b);
+    if (x.scalar && !p.scalar) x = Value{into_array(tc, x, b.base_rows), false};
+    dfgpu_array* o = nullptr; tc.check(dfgpu_like(tc.ctx, x.arr.a, p.arr.a, p.scalar ? 1 : 0, negated ? 1 : 0, case_insensitive ? 1 : 0, &o));
+    return Value{ArrayRef::adopt(o), x.scalar && p.scalar};
+  }
+  bool safe() const override { return e->safe() && pattern->safe(); }      // nothing raises per row
+  void columns(std::set<int>& out) const override { e->columns(out); pattern->columns(out); }
+};
+
 // ------------------------------------------------------------------ ExecutionPlan
 struct Stream { virtual ~Stream() = default; virtual bool next(Batch& out) = 0; };     // poll_next: false = end of stream
 struct Plan;
@@ -2250,6 +2262,14 @@ dfgpu_status dfgpu_expr_case(const dfgpu_expr* base, const dfgpu_expr* const* wh
     if (else_expr) c->else_expr = else_expr->e;
     for (int k = 0; k < n; k++) { c->whens.push_back(ex(whens[k])); c->thens.push_back(thens[k] ? thens[k]->e : ExprPtr()); }
     *out = new dfgpu_expr{c};
+  });
+}
+dfgpu_status dfgpu_expr_like(const dfgpu_expr* expr, const dfgpu_expr* pattern, int32_t negated, int32_t case_insensitive, dfgpu_expr** out) {
+  return guard([&] {
+    if (!out) fail(DFGPU_INVALID_ARGUMENT, "expr_like: null argument");
+    auto l = std::make_shared<LikeExpr>();
+    l->e = ex(expr); l->pattern = ex(pattern); l->negated = negated != 0; l->case_insensitive = case_insensitive != 0;
+    *out = new dfgpu_expr{l};
   });
 }
 void dfgpu_expr_free(dfgpu_expr* e) { delete e; }

@@ -470,6 +470,30 @@ __global__ void __launch_bounds__(BLOCK) k_case_index(CaseArgs a, int64_t n, uin
   if (out_ok && lane == 0) out_ok[g] = ok;
 }
 
+// A predicate evaluated once per dictionary entry (`dres`: Boolean, one row per entry of dcol's dictionary) mapped through dcol's codes: row i is
+// dres[code[i]], NULL where the code or the entry's result is.  Shared by dfgpu_binary (column vs scalar) and dfgpu_like (scalar pattern).
+dfgpu_array* dict_predicate_map(dfgpu_ctx* ctx, const dfgpu_array* dcol, const dfgpu_array* dres) {
+  const int64_t n = dcol->length;
+  bool nv = dcol->validity || dres->validity;
+  ArrayHolder hd(new_fixed(ctx, DFGPU_BOOL, n, 0, 0, nv));
+  KernelTimer kt_(ctx, "k_dict_predicate");
+  const size_t dp_lds = (size_t)((dres->length + 63) / 64) * 8;
+  const int32_t kt = dcol->key_type;
+  if (!nv && (kt == DFGPU_INT32 || kt == DFGPU_INT16 || kt == DFGPU_INT8 || kt == DFGPU_UINT8 || kt == DFGPU_UINT16) && dp_lds <= 144 * 1024 && n >= (1 << 16)) {
+    const int per_cu = dp_lds <= 32 * 1024 ? 2 : 1;       // a large bitmap leaves room for one workgroup of 16 waves per CU
+#define DP_LAUNCH(KT) do { HIP_CHECK(hipFuncSetAttribute((const void*)k_dict_predicate_i32<KT>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024)); \
+    hipLaunchKernelGGL((k_dict_predicate_i32<KT>), dim3(grid_for(n, 1024 * 8, ctx->num_cus * per_cu)), dim3(1024), dp_lds, ctx->stream, (const KT*)dcol->values->ptr, n, (const uint64_t*)dres->values->ptr, dres->length, (uint64_t*)hd.get()->values->ptr); } while (0)
+    switch (kt) { case DFGPU_INT8: DP_LAUNCH(int8_t); break; case DFGPU_INT16: DP_LAUNCH(int16_t); break; case DFGPU_UINT8: DP_LAUNCH(uint8_t); break; case DFGPU_UINT16: DP_LAUNCH(uint16_t); break; default: DP_LAUNCH(int32_t); break; }
+#undef DP_LAUNCH
+    KERNEL_CHECK(); return hd.release();
+  }
+  hipLaunchKernelGGL(k_dict_predicate, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, dcol->values->ptr, dcol->key_type, dcol->validity ? (const uint64_t*)dcol->validity->ptr : nullptr, n,
+                     (const uint64_t*)dres->values->ptr, dres->validity ? (const uint64_t*)dres->validity->ptr : nullptr, dres->length,
+                     (uint64_t*)hd.get()->values->ptr, nv ? (uint64_t*)hd.get()->validity->ptr : nullptr);
+  KERNEL_CHECK(); if (nv) hd.get()->null_count = -1;
+  return hd.release();
+}
+
 static bool may_have_nulls(const dfgpu_array* a) { return a->validity != nullptr || (a->dictionary && a->dictionary->validity != nullptr); }
 static Operand make_operand(const dfgpu_array* a, int scalar) {
   if (scalar && a->length != 1) fail(DFGPU_INVALID_ARGUMENT, "scalar operand must have length 1");
@@ -581,24 +605,7 @@ dfgpu_status dfgpu_binary(dfgpu_ctx* ctx, int32_t op, const dfgpu_array* l, int3
           dfgpu_status st = dcol == l ? dfgpu_binary(ctx, op, dcol->dictionary, 0, r, 1, &dres) : dfgpu_binary(ctx, op, l, 1, dcol->dictionary, 0, &dres);
           if (st != DFGPU_OK) fail(st, "%s", ctx->err.c_str());
           ArrayHolder dh(dres);
-          bool nv = dcol->validity || dres->validity;
-          ArrayHolder hd(new_fixed(ctx, DFGPU_BOOL, n, 0, 0, nv));
-          KernelTimer kt_(ctx, "k_dict_predicate");
-          const size_t dp_lds = (size_t)((dres->length + 63) / 64) * 8;
-          const int32_t kt = dcol->key_type;
-          if (!nv && (kt == DFGPU_INT32 || kt == DFGPU_INT16 || kt == DFGPU_INT8 || kt == DFGPU_UINT8 || kt == DFGPU_UINT16) && dp_lds <= 144 * 1024 && n >= (1 << 16)) {
-            const int per_cu = dp_lds <= 32 * 1024 ? 2 : 1;       // a large bitmap leaves room for one workgroup of 16 waves per CU
-#define DP_LAUNCH(KT) do { HIP_CHECK(hipFuncSetAttribute((const void*)k_dict_predicate_i32<KT>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024)); \
-            hipLaunchKernelGGL((k_dict_predicate_i32<KT>), dim3(grid_for(n, 1024 * 8, ctx->num_cus * per_cu)), dim3(1024), dp_lds, ctx->stream, (const KT*)dcol->values->ptr, n, (const uint64_t*)dres->values->ptr, dres->length, (uint64_t*)hd.get()->values->ptr); } while (0)
-            switch (kt) { case DFGPU_INT8: DP_LAUNCH(int8_t); break; case DFGPU_INT16: DP_LAUNCH(int16_t); break; case DFGPU_UINT8: DP_LAUNCH(uint8_t); break; case DFGPU_UINT16: DP_LAUNCH(uint16_t); break; default: DP_LAUNCH(int32_t); break; }
-#undef DP_LAUNCH
-            KERNEL_CHECK(); *out = hd.release(); return;
-          }
-          hipLaunchKernelGGL(k_dict_predicate, grid, block, 0, ctx->stream, dcol->values->ptr, dcol->key_type, dcol->validity ? (const uint64_t*)dcol->validity->ptr : nullptr, n,
-                             (const uint64_t*)dres->values->ptr, dres->validity ? (const uint64_t*)dres->validity->ptr : nullptr, dres->length,
-                             (uint64_t*)hd.get()->values->ptr, nv ? (uint64_t*)hd.get()->validity->ptr : nullptr);
-          KERNEL_CHECK(); if (nv) hd.get()->null_count = -1;
-          *out = hd.release(); return;
+          *out = dict_predicate_map(ctx, dcol, dres); return;
         }
       }
       {   // fast path: non-null fixed-width integer column vs non-null scalar

@@ -242,6 +242,12 @@ class Context:
         self.check(self.lib.dfgpu_case(self.h, wh, th, ts, n, else_.h if else_ is not None else None, int(else_scalar), C.byref(out)))
         return self._wrap(out)
 
+    def like(self, values: "Array", pattern: "Array", pattern_is_scalar: bool = True, negated: bool = False, case_insensitive: bool = False) -> "Array":
+        """dfgpu_like: values [NOT] LIKE / ILIKE pattern -> Boolean.  pattern: a length-1 Utf8 array (pattern_is_scalar), or one pattern per row."""
+        out = C.c_void_p()
+        self.check(self.lib.dfgpu_like(self.h, values.h, pattern.h, int(pattern_is_scalar), int(negated), int(case_insensitive), C.byref(out)))
+        return self._wrap(out)
+
     def push_row_selection(self, mask: "Array"):
         """dfgpu_ctx_push_row_selection: narrow the row selection to (current AND mask) until pop_row_selection"""
         self.check(self.lib.dfgpu_ctx_push_row_selection(self.h, mask.h if mask is not None else None))

@@ -252,6 +252,19 @@ class CaseExpr(PhysicalExpr):
         return _ExprH(out)
 
 
+class LikeExpr(PhysicalExpr):
+    """expr [NOT] LIKE / ILIKE pattern (expressions/like.rs).  A Literal pattern takes the compiled scalar path, any other expression one pattern per row."""
+
+    def __init__(self, expr: PhysicalExpr, pattern: PhysicalExpr, negated: bool = False, case_insensitive: bool = False):
+        self.expr, self.pattern, self.negated, self.case_insensitive = expr, pattern, negated, case_insensitive
+        self.children = [expr, pattern]
+
+    def _build(self, ctx):
+        out = C.c_void_p()
+        _check(_lib().dfgpu_expr_like(self.expr.handle(ctx).h, self.pattern.handle(ctx).h, int(self.negated), int(self.case_insensitive), C.byref(out)))
+        return _ExprH(out)
+
+
 # ----------------------------------------------------------------------------- ExecutionPlan builders
 class Partitioning:
     def __init__(self, kind: str, n: int, exprs: Optional[List[PhysicalExpr]] = None):

@@ -298,6 +298,17 @@ DFGPU_API dfgpu_status dfgpu_in_list(dfgpu_ctx *ctx, const dfgpu_array *a, const
  * of branches that can raise is the plan layer's part (dfgpu_expr_case, over dfgpu_ctx_push_row_selection). */
 DFGPU_API dfgpu_status dfgpu_case(dfgpu_ctx *ctx, const dfgpu_array *const *whens, const dfgpu_array *const *thens, const int32_t *then_is_scalar,
                                   int32_t n_branches, const dfgpu_array *else_value, int32_t else_is_scalar, dfgpu_array **out);
+/* LikeExpr (like.rs:103): values LIKE / NOT LIKE / ILIKE / NOT ILIKE pattern, the semantics of arrow-string 50.0.0 like / nlike / ilike / nilike.
+ * `%` matches any run of characters (also the empty one), `_` exactly one Unicode scalar (not one byte; a line feed too), a backslash in front of `%` or `_`
+ * makes that character literal, a backslash in front of anything else or ending the pattern is a literal backslash, everything else matches itself byte for
+ * byte; the match is anchored at both ends, so the empty pattern matches the empty string only.  case_insensitive: ASCII letters fold, and the pattern letters
+ * k and s also match U+212A (Kelvin sign) and U+017F (long s); a pattern with a non-ASCII byte is DFGPU_NOT_IMPLEMENTED then (plain LIKE takes any pattern).
+ * values: Utf8 of length n, or Dictionary(intN, Utf8) when the pattern is a scalar.  pattern: Utf8, of length 1 with pattern_is_scalar, else of length n (one
+ * pattern per row).  Every other type and unequal lengths are DFGPU_INVALID_ARGUMENT (the planner coerces first).  The result is Boolean; row i is NULL exactly
+ * where values[i] or its pattern is NULL (a NULL scalar pattern: every row), and `negated` flips the value bits and keeps the validity.  Nothing raises per
+ * row, so a row selection changes nothing. */
+DFGPU_API dfgpu_status dfgpu_like(dfgpu_ctx *ctx, const dfgpu_array *values, const dfgpu_array *pattern, int32_t pattern_is_scalar, int32_t negated,
+                                  int32_t case_insensitive, dfgpu_array **out);
 
 /* ------------------------------------------------------------------ a2-a6: HashJoinExec */
 enum { DFGPU_JOIN_INNER = 0, DFGPU_JOIN_LEFT = 1, DFGPU_JOIN_RIGHT = 2, DFGPU_JOIN_FULL = 3,

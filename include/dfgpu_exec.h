@@ -55,6 +55,9 @@ DFGPU_API dfgpu_status dfgpu_expr_in_list(const dfgpu_expr *e, const dfgpu_array
  * (evaluate_selection): WHEN k can raise only on rows no earlier branch took, THEN k only on the rows of branch k, the ELSE only on the rest. */
 DFGPU_API dfgpu_status dfgpu_expr_case(const dfgpu_expr *base, const dfgpu_expr *const *whens, const dfgpu_expr *const *thens, int32_t n,
                                        const dfgpu_expr *else_expr, dfgpu_expr **out);
+/* LikeExpr (like.rs:103): expr [NOT] LIKE / ILIKE pattern.  A pattern that is a literal is compiled once per batch (the scalar form of dfgpu_like); any
+ * other pattern expression is evaluated to a column and parsed per row. */
+DFGPU_API dfgpu_status dfgpu_expr_like(const dfgpu_expr *expr, const dfgpu_expr *pattern, int32_t negated, int32_t case_insensitive, dfgpu_expr **out);
 DFGPU_API void dfgpu_expr_free(dfgpu_expr *e);
 
 /* ---- ExecutionPlan nodes */
