@@ -129,6 +129,7 @@ PROTOTYPES = {
     "dfgpu_in_list": (C.c_int32, [_P, _P, _P, C.c_int32, _PP]),
     "dfgpu_case": (C.c_int32, [_P, _PP, _PP, C.POINTER(C.c_int32), C.c_int32, _P, C.c_int32, _PP]),
     "dfgpu_like": (C.c_int32, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _PP]),
+    "dfgpu_scalar_function": (C.c_int32, [_P, C.c_int32, _PP, C.POINTER(C.c_int32), C.c_int32, _PP]),
     "dfgpu_join_build": (C.c_int32, [_P, _PP, C.c_int32, _P, C.c_int32, _PP]),
     "dfgpu_join_table_free": (None, [_P]),
     "dfgpu_join_table_num_rows": (C.c_int64, [_P]),
@@ -216,6 +217,7 @@ PROTOTYPES.update({
     "dfgpu_expr_in_list": (C.c_int32, [_P, _P, C.c_int32, _PP]),
     "dfgpu_expr_case": (C.c_int32, [_P, _PP, _PP, C.c_int32, _P, _PP]),
     "dfgpu_expr_like": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _PP]),
+    "dfgpu_expr_scalar_function": (C.c_int32, [C.c_int32, _PP, C.c_int32, _PP]),
     "dfgpu_expr_free": (None, [_P]),
     "dfgpu_plan_memory": (C.c_int32, [_PP, _I32P, C.c_int32, _PP]),
     "dfgpu_plan_memory_replace": (C.c_int32, [_P, _PP, _I32P, C.c_int32]),

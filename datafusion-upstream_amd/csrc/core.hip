@@ -109,6 +109,7 @@ void check_flags(dfgpu_ctx* ctx, const char* what) {
   if (f & DFGPU_FLAG_OVERFLOW) fail(DFGPU_EXECUTION, "Arrow error: Arithmetic overflow (%s)", what);
   if (f & DFGPU_FLAG_CAST) fail(DFGPU_EXECUTION, "Arrow error: Cast error: value out of range (%s)", what);
   if (f & DFGPU_FLAG_OOB) fail(DFGPU_EXECUTION, "Arrow error: index out of bounds (%s)", what);
+  if (f & DFGPU_FLAG_SUBSTR_LENGTH) fail(DFGPU_EXECUTION, "negative substring length not allowed: substr(<str>, <start>, <count>) with a count below zero (%s)", what);
   if (f & DFGPU_FLAG_STALLED) fail(DFGPU_INTERNAL, "a workgroup gave up waiting for the tile counts of the workgroups in front of it; the result of that sort is not valid (%s; option sort_onesweep_rows=0 selects the three-launch passes)", what);
   fail(DFGPU_INTERNAL, "kernel raised flag %u (%s)", f, what);
 }
@@ -421,6 +422,7 @@ static const CtxOption kCtxOptions[] = {
   { "sort_estimate_ranges", OPT_BOOL(sort_estimate_ranges) },
   { "sort_topk_words_min_rows", OPT_MIN(sort_topk_words_min_rows, 2) },
   { "sort_one_block_max_rows", OPT_MIN(sort_one_block_max_rows, 0) },
+  { "string_wave_row_bytes", OPT_MIN(string_wave_row_bytes, 1) },
   { "sort_onesweep_min_rows", OPT_MIN(sort_onesweep_min_rows, 2) },
   { "sort_onesweep_rows", OPT_GET(sort_onesweep_rows), [](dfgpu_ctx* c, int64_t v) { c->sort_onesweep_rows = v == 16 ? 16 : v > 0 ? 8 : 0; } },      // 16, 8 or 0
   { "sort_onesweep_fused_finish", OPT_BOOL(sort_onesweep_fused_finish) },

@@ -31,9 +31,13 @@ struct Error : std::exception {
 }  // namespace dfgpu
 
 // Device error flags raised by kernels (checked by the op that launched them).
-enum : uint32_t { DFGPU_FLAG_DIV_ZERO = 1, DFGPU_FLAG_OVERFLOW = 2, DFGPU_FLAG_CAST = 4, DFGPU_FLAG_OOB = 8, DFGPU_FLAG_TABLE_FULL = 16, DFGPU_FLAG_STALLED = 32 };      // STALLED: a workgroup gave up waiting for a word another workgroup publishes (one-sweep sort passes)
+enum : uint32_t { DFGPU_FLAG_DIV_ZERO = 1, DFGPU_FLAG_OVERFLOW = 2, DFGPU_FLAG_CAST = 4, DFGPU_FLAG_OOB = 8, DFGPU_FLAG_TABLE_FULL = 16, DFGPU_FLAG_STALLED = 32, DFGPU_FLAG_SUBSTR_LENGTH = 64 };      // STALLED: a workgroup gave up waiting for a word another workgroup publishes (one-sweep sort passes)
 
 namespace dfgpu { struct Buffer; }
+// scalar_fn.hip: a Utf8 column whose rows average at least this many bytes gives every row a wave (16 B per lane, 1 KiB per step) instead of a lane (8 B per step);
+// both kernels are exact at every length.  Measured (profiles/scalar_fn_microbench.json, `crossing`: character_length over 256 MB of equal-length rows, ms lane / wave):
+// 64 B 0.10 / 1.00, 96 B 0.22 / 0.64, 128 B 0.54 / 0.48, 256 B 0.44 / 0.24, 1024 B 0.22 / 0.07; left(s, -1) crosses at 128 B too (1.54 / 1.51).
+namespace dfgpu { constexpr int64_t STR_WAVE_ROW_BYTES = 128; }
 struct dfgpu_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -97,6 +101,7 @@ struct dfgpu_ctx {
   int sort_onesweep_rows = 16;                                  // word-mode sorts of 2^20 .. 2^30 rows: one launch per pass (look-back over published tile counts, sort.hip); rows per lane of a tile (8 or 16), 0 = the three-launch passes
   bool sort_fused_small_passes = true;                         // inputs below 2^20 rows: the per-pass scan is folded into the scatter (two launches per varying key byte instead of three)
   bool sort_estimate_ranges = true;                            // packed-key sort of >= 2^22 rows: value ranges from a sample, checked while encoding
+  int64_t string_wave_row_bytes = dfgpu::STR_WAVE_ROW_BYTES;  // scalar_fn.hip: Utf8 columns averaging at least this many bytes a row take the wave-per-row kernels
   int64_t spm_merge_rows = (int64_t)1 << 25;                   // SortPreservingMergeExec: rows loaded over all inputs per merge step
   int64_t sort_spill_bytes = 0, sort_spill_ranges = 16;        // SortExec: bytes of input batches kept on the device before they are sorted and spilled to host memory as a run (0 = never); key ranges a run is cut into
   int64_t agg_spill_state_bytes = 0, agg_spill_ranges = 16;    // AggregateExec: state size (group table + accumulators) above which the state is spilled to host memory (0 = never); key ranges a spill is cut into

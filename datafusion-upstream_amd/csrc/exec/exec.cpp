@@ -380,6 +380,35 @@ struct LikeExpr : Expr {          // expressions/like.rs:103; evaluate -> arrow-
   void columns(std::set<int>& out) const override { e->columns(out); pattern->columns(out); }
 };
 
+struct ScalarFunctionExpr : Expr { // scalar_function.rs:ScalarFunctionExpr::evaluate over the built-in functions of dfgpu_scalar_function
+  int32_t fn = 0; std::vector<ExprPtr> args;
+  // a three-argument SUBSTR whose count is a literal: 1 = the literal is NULL or >= 0 (no row can raise), 0 = anything else, -1 = not read yet.  The value is read
+  // through the public ABI at the first evaluation (building an expression has no context to read with); until then safe() answers for the worst case
+  mutable std::atomic<int> count_cannot_raise{-1};
+  void learn_count(const TaskContext& tc) const {
+    if (fn != DFGPU_FN_SUBSTR || args.size() != 3 || count_cannot_raise.load() >= 0) return;
+    auto* lit = dynamic_cast<const LiteralExpr*>(args[2].get());
+    dfgpu_array_desc d{}; if (lit) dfgpu_array_describe(lit->scalar.a, &d);
+    if (!lit || d.type != DFGPU_INT64 || d.length != 1) { count_cannot_raise.store(0); return; }
+    int64_t v = 0; uint8_t valid = 1;
+    tc.check(dfgpu_array_export_host(tc.ctx, lit->scalar.a, &v, &valid, nullptr));
+    count_cannot_raise.store(((d.validity && !(valid & 1)) || v >= 0) ? 1 : 0);
+  }
+  Value eval(const TaskContext& tc, Batch& b) const override {
+    learn_count(tc);
+    std::vector<Value> v; std::vector<const dfgpu_array*> a; std::vector<int32_t> sc; bool all_scalar = true;
+    for (auto& e : args) { v.push_back(e->eval(tc, b)); a.push_back(v.back().arr.a); sc.push_back(v.back().scalar ? 1 : 0); all_scalar = all_scalar && v.back().scalar; }
+    dfgpu_array* o = nullptr; tc.check(dfgpu_scalar_function(tc.ctx, fn, a.data(), sc.data(), (int32_t)a.size(), &o));
+    return Value{ArrayRef::adopt(o), all_scalar};
+  }
+  // only a three-argument SUBSTR raises per row (a negative count), and not when its count is a NULL or non-negative literal
+  bool safe() const override {
+    for (auto& e : args) if (!e->safe()) return false;
+    return fn != DFGPU_FN_SUBSTR || args.size() != 3 || count_cannot_raise.load() == 1;
+  }
+  void columns(std::set<int>& out) const override { for (auto& e : args) e->columns(out); }
+};
+
 // ------------------------------------------------------------------ ExecutionPlan
 struct Stream { virtual ~Stream() = default; virtual bool next(Batch& out) = 0; };     // poll_next: false = end of stream
 struct Plan;
@@ -2270,6 +2299,18 @@ dfgpu_status dfgpu_expr_like(const dfgpu_expr* expr, const dfgpu_expr* pattern, 
     auto l = std::make_shared<LikeExpr>();
     l->e = ex(expr); l->pattern = ex(pattern); l->negated = negated != 0; l->case_insensitive = case_insensitive != 0;
     *out = new dfgpu_expr{l};
+  });
+}
+dfgpu_status dfgpu_expr_scalar_function(int32_t fn, const dfgpu_expr* const* args, int32_t nargs, dfgpu_expr** out) {
+  return guard([&] {
+    if (!out || !args) fail(DFGPU_INVALID_ARGUMENT, "expr_scalar_function: null argument");
+    // the table of dfgpu_scalar_function: what no evaluation could take is refused when the plan is built
+    static const int32_t lo[7] = {0, 2, 1, 2, 2, 2, 2}, hi[7] = {0, 2, 1, 3, 2, 2, 2};
+    if (fn < DFGPU_FN_DATE_PART || fn > DFGPU_FN_STARTS_WITH) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: scalar function %d on the device", fn);
+    if (nargs < lo[fn] || nargs > hi[fn]) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: scalar function %d with %d arguments on the device", fn, nargs);
+    auto f = std::make_shared<ScalarFunctionExpr>();
+    f->fn = fn; for (int32_t k = 0; k < nargs; k++) f->args.push_back(ex(args[k]));
+    *out = new dfgpu_expr{f};
   });
 }
 void dfgpu_expr_free(dfgpu_expr* e) { delete e; }

@@ -248,6 +248,16 @@ class Context:
         self.check(self.lib.dfgpu_like(self.h, values.h, pattern.h, int(pattern_is_scalar), int(negated), int(case_insensitive), C.byref(out)))
         return self._wrap(out)
 
+    def scalar_function(self, fn: int, args, scalars=None) -> "Array":
+        """dfgpu_scalar_function: fn = FN_DATE_PART .. FN_STARTS_WITH over 1 to 3 arrays; scalars[k]: args[k] is a length-1 array that stands for every row"""
+        n = len(args)
+        scalars = [False] * n if scalars is None else list(scalars)
+        ah = (C.c_void_p * n)(*[a.h for a in args])
+        sc = (C.c_int32 * n)(*[int(bool(x)) for x in scalars])
+        out = C.c_void_p()
+        self.check(self.lib.dfgpu_scalar_function(self.h, int(fn), ah, sc, n, C.byref(out)))
+        return self._wrap(out)
+
     def push_row_selection(self, mask: "Array"):
         """dfgpu_ctx_push_row_selection: narrow the row selection to (current AND mask) until pop_row_selection"""
         self.check(self.lib.dfgpu_ctx_push_row_selection(self.h, mask.h if mask is not None else None))

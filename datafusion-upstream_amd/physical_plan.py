@@ -265,6 +265,49 @@ class LikeExpr(PhysicalExpr):
         return _ExprH(out)
 
 
+FN_DATE_PART, FN_CHARACTER_LENGTH, FN_SUBSTR, FN_LEFT, FN_RIGHT, FN_STARTS_WITH = 1, 2, 3, 4, 5, 6          # DFGPU_FN_* (include/dfgpu.h)
+
+
+class ScalarFunctionExpr(PhysicalExpr):
+    """A built-in scalar function over 1 to 3 argument expressions (scalar_function.rs).  Literal arguments stay scalars."""
+
+    def __init__(self, fn: int, args: List[PhysicalExpr]):
+        self.fn, self.args = fn, list(args)
+        self.children = self.args
+
+    def _build(self, ctx):
+        out = C.c_void_p()
+        hs = [a.handle(ctx) for a in self.args]
+        arr = (C.c_void_p * len(hs))(*[h.h for h in hs])
+        _check(_lib().dfgpu_expr_scalar_function(int(self.fn), arr, len(hs), C.byref(out)))
+        return _ExprH(out)
+
+
+def date_part(part: PhysicalExpr, date: PhysicalExpr) -> ScalarFunctionExpr:
+    """date_part(part, Date32) -> Float64; `part` is a Utf8 literal: year, quarter, month, week, day, doy, dow, hour, epoch"""
+    return ScalarFunctionExpr(FN_DATE_PART, [part, date])
+
+
+def character_length(s: PhysicalExpr) -> ScalarFunctionExpr:
+    return ScalarFunctionExpr(FN_CHARACTER_LENGTH, [s])
+
+
+def substr(s: PhysicalExpr, start: PhysicalExpr, count: Optional[PhysicalExpr] = None) -> ScalarFunctionExpr:
+    return ScalarFunctionExpr(FN_SUBSTR, [s, start] + ([count] if count is not None else []))
+
+
+def left(s: PhysicalExpr, n: PhysicalExpr) -> ScalarFunctionExpr:
+    return ScalarFunctionExpr(FN_LEFT, [s, n])
+
+
+def right(s: PhysicalExpr, n: PhysicalExpr) -> ScalarFunctionExpr:
+    return ScalarFunctionExpr(FN_RIGHT, [s, n])
+
+
+def starts_with(s: PhysicalExpr, prefix: PhysicalExpr) -> ScalarFunctionExpr:
+    return ScalarFunctionExpr(FN_STARTS_WITH, [s, prefix])
+
+
 # ----------------------------------------------------------------------------- ExecutionPlan builders
 class Partitioning:
     def __init__(self, kind: str, n: int, exprs: Optional[List[PhysicalExpr]] = None):

@@ -130,6 +130,8 @@ DFGPU_API dfgpu_status dfgpu_ctx_synchronize(dfgpu_ctx *ctx);
  * "sort_topk_words_min_rows" (default 2^23) == a sort with fetch <= n / 16 over at least this many rows whose keys pack selects on the packed keys (radix select, then the
  * few candidates sorted) instead of on byte planes (identical indices); "sort_one_block_max_rows" (default 8192, 0 = off) == byte-plane sorts of at most this many rows run
  * every pass inside one launch of one workgroup (identical indices);
+ * "string_wave_row_bytes" (default 128, at least 1) == dfgpu_scalar_function over a Utf8 column whose rows average at least this many bytes gives every row a wave
+ * instead of a lane (identical results);
  * "memory_limit" (bytes, 0 = none) == live device memory this ctx may hold; an allocation beyond it fails with DFGPU_RESOURCES_EXHAUSTED and the
  * message of MemoryPool::try_grow (≙ RuntimeConfig::with_memory_limit, execution/src/runtime_env.rs); "live_bytes" / "cached_bytes" (read only);
  * "trim_cache" (set only, value ignored) == wait for the ctx stream to drain, then give the freed blocks the ctx keeps for reuse back to the driver (≙ MemoryPool::shrink; cached_bytes = 0);
@@ -309,6 +311,27 @@ DFGPU_API dfgpu_status dfgpu_case(dfgpu_ctx *ctx, const dfgpu_array *const *when
  * row, so a row selection changes nothing. */
 DFGPU_API dfgpu_status dfgpu_like(dfgpu_ctx *ctx, const dfgpu_array *values, const dfgpu_array *pattern, int32_t pattern_is_scalar, int32_t negated,
                                   int32_t case_insensitive, dfgpu_array **out);
+/* ScalarFunctionExpr (scalar_function.rs, functions.rs): the built-in functions below, row-wise.  arg_is_scalar[k]: args[k] is a length-1 array that stands
+ * for every row; the result has the row count of the other arguments, or length 1 when every argument is a scalar.  A NULL in any argument of a row makes
+ * that row NULL.  A Utf8 or Date32 argument may be a dictionary.  When it is the only column, has fewer entries than rows and no row can raise, the function
+ * is evaluated once per dictionary entry: a Utf8 result is a dictionary over the same codes (entries may repeat), any other result is gathered through the
+ * codes.  Otherwise the dictionary is decoded first and the result is plain.
+ *   DATE_PART         (Utf8 scalar part, Date32) -> Float64   year, quarter, month, week (ISO-8601), day, doy (1-based), dow (days from Sunday), hour (0),
+ *                                                             epoch (days * 86400); the name matches case-insensitively.  minute, second, millisecond,
+ *                                                             microsecond, nanosecond: DFGPU_NOT_IMPLEMENTED; any other name: DFGPU_EXECUTION "Date part
+ *                                                             '<name>' not supported".  Proleptic Gregorian calendar in 64-bit arithmetic: no Int32 day count
+ *                                                             faults; outside 0001-01-01 .. 9999-12-31 the value is what that arithmetic gives.
+ *   CHARACTER_LENGTH  (Utf8) -> Int32                         code points
+ *   SUBSTR            (Utf8, Int64 start [, Int64 count]) -> Utf8   positions count code points from 1.  Two arguments: start <= 0 is the whole string.  Three:
+ *                                                             skip max(0, start - 1), take max(0, count + (start < 1 ? start - 1 : 0)); a count < 0 on a row
+ *                                                             inside the row selection whose three arguments are non-NULL is DFGPU_EXECUTION "negative
+ *                                                             substring length not allowed"
+ *   LEFT / RIGHT      (Utf8, Int64 n) -> Utf8                 the first / last n code points; n < 0: all but the last / first |n|; n = 0: ''
+ *   STARTS_WITH       (Utf8, Utf8) -> Boolean                 byte prefix
+ * Huge |start|, |count|, |n| saturate.  Any other function, argument count or argument type (the planner coerces first) is DFGPU_NOT_IMPLEMENTED. */
+enum { DFGPU_FN_DATE_PART = 1, DFGPU_FN_CHARACTER_LENGTH = 2, DFGPU_FN_SUBSTR = 3, DFGPU_FN_LEFT = 4, DFGPU_FN_RIGHT = 5, DFGPU_FN_STARTS_WITH = 6 };
+DFGPU_API dfgpu_status dfgpu_scalar_function(dfgpu_ctx *ctx, int32_t fn, const dfgpu_array *const *args, const int32_t *arg_is_scalar, int32_t nargs,
+                                             dfgpu_array **out);
 
 /* ------------------------------------------------------------------ a2-a6: HashJoinExec */
 enum { DFGPU_JOIN_INNER = 0, DFGPU_JOIN_LEFT = 1, DFGPU_JOIN_RIGHT = 2, DFGPU_JOIN_FULL = 3,

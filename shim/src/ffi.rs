@@ -42,6 +42,7 @@ extern "C" {
     pub fn dfgpu_comm_free(comm: *mut dfgpu_comm);
     pub fn dfgpu_exchange(ctx: *mut dfgpu_ctx, comm: *mut dfgpu_comm, keys: *const *const dfgpu_array, nkeys: i32, cols: *const *const dfgpu_array, ncols: i32,
                           opt_mask: *const dfgpu_array, out_cols: *mut *mut dfgpu_array, out_counts: *mut i64) -> i32;
+    pub fn dfgpu_scalar_function(ctx: *mut dfgpu_ctx, fn_: i32, args: *const *const dfgpu_array, arg_is_scalar: *const i32, nargs: i32, out: *mut *mut dfgpu_array) -> i32;
     pub fn dfgpu_parquet_open(ctx: *mut dfgpu_ctx, file_bytes: *const u8, len: i64, device_bytes: *const u8, out: *mut *mut dfgpu_parquet) -> i32;
     pub fn dfgpu_parquet_close(file: *mut dfgpu_parquet);
     pub fn dfgpu_parquet_num_row_groups(file: *const dfgpu_parquet) -> i32;
@@ -84,6 +85,8 @@ extern "C" {
     pub fn dfgpu_expr_is_null(e: *const dfgpu_expr, negated: i32, out: *mut *mut dfgpu_expr) -> i32;
     pub fn dfgpu_expr_negative(e: *const dfgpu_expr, out: *mut *mut dfgpu_expr) -> i32;
     pub fn dfgpu_expr_cast(e: *const dfgpu_expr, to_type: i32, precision: i32, scale: i32, out: *mut *mut dfgpu_expr) -> i32;
+    /// ScalarFunctionExpr: fn_ is a DFGPU_FN_* (1 date_part, 2 character_length, 3 substr, 4 left, 5 right, 6 starts_with); literal arguments stay scalars.
+    pub fn dfgpu_expr_scalar_function(fn_: i32, args: *const *const dfgpu_expr, nargs: i32, out: *mut *mut dfgpu_expr) -> i32;
     pub fn dfgpu_expr_free(e: *mut dfgpu_expr);
     pub fn dfgpu_plan_memory(batches: *const *const dfgpu_batch, partition_sizes: *const i32, npartitions: i32, out: *mut *mut dfgpu_plan) -> i32;
     pub fn dfgpu_plan_filter(predicate: *const dfgpu_expr, input: *const dfgpu_plan, out: *mut *mut dfgpu_plan) -> i32;
