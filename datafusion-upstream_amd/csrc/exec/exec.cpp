@@ -79,6 +79,14 @@ struct Composed { ArrayRef inner, outer, out; };
 struct TakeMemo { std::map<std::pair<const dfgpu_array*, const dfgpu_array*>, Composed> composed; };
 using MemoPtr = std::shared_ptr<TakeMemo>;
 static ArrayRef take(const TaskContext& tc, const ArrayRef& v, const ArrayRef& idx) { dfgpu_array* o = nullptr; tc.check(dfgpu_take(tc.ctx, v.a, idx.a, &o)); return ArrayRef::adopt(o); }
+// n host values as a device array: a literal (n == 1), a row list, or the empty array (n == 0, `v` is not read: the descriptor wants a non-null `values` even then
+// and points at itself)
+static ArrayRef host_array(const TaskContext& tc, int32_t type, const void* v, int64_t n) {
+  dfgpu_array_desc d{}; d.type = type; d.length = n; d.values = n ? v : &d;
+  dfgpu_array* a = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &d, &a)); return ArrayRef::adopt(a);
+}
+static ArrayRef host_u32(const TaskContext& tc, const uint32_t* v, int64_t n) { return host_array(tc, DFGPU_UINT32, v, n); }
+static ArrayRef host_u64(const TaskContext& tc, const uint64_t* v, int64_t n) { return host_array(tc, DFGPU_UINT64, v, n); }
 // The innermost stage of a pending gather can be a join's build-row lookup that has not run yet (dfgpu_join_probe_deferred): the chain then indexes the join's matched
 // pairs, and the build rows are computed when a build-side column is finally read -- for the pairs still wanted by then.  TPC-H Q18 joins 600 M lineitems to their orders
 // and keeps a few thousand of them in the next (semi) join: the lookup runs for those, not for 600 M.  Columns of one join output share the object, so a lookup runs once
@@ -567,6 +575,13 @@ static ArrayRef known_mask(const TaskContext& tc, const ArrayRef& m) {     // NU
   tc.check(dfgpu_is_null(tc.ctx, m.a, 1, &nn)); ArrayRef n1 = ArrayRef::adopt(nn);
   tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_AND, m.a, 0, n1.a, 0, &o)); return ArrayRef::adopt(o);
 }
+// `filter` AND `mask`, or whichever of the two exists.  A filter may hold NULLs: they drop the row (NULL -> false) before the AND; a mask never holds any.  A filter
+// that meets no mask is returned as it is -- whoever reads it drops its NULL rows itself.
+static ArrayRef and_masks(const TaskContext& tc, const ArrayRef& filter, const ArrayRef& mask) {
+  if (!filter || !mask) return filter ? filter : mask;
+  ArrayRef kf = known_mask(tc, filter); dfgpu_array* o = nullptr;
+  tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_AND, kf.a, 0, mask.a, 0, &o)); return ArrayRef::adopt(o);
+}
 
 struct FilterExec : Plan {        // filter.rs:56-66, batch_filter :315-327
   ExprPtr pred; PlanPtr input;
@@ -604,8 +619,7 @@ struct FilterExec : Plan {        // filter.rs:56-66, batch_filter :315-327
       ArrayRef mask = into_array(tc, v, b.base_rows);
       dfgpu_array_desc d; dfgpu_array_describe(mask.a, &d);
       if (d.type != DFGPU_BOOL) fail(DFGPU_INTERNAL, "Cannot create filter_array from non-boolean predicates");
-      if (b.filtered()) { ArrayRef km = known_mask(tc, mask); dfgpu_array* o = nullptr; tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_AND, km.a, 0, b.selection(tc).a, 0, &o)); mask = ArrayRef::adopt(o); }
-      b.set_selection(mask); out = std::move(b); return true;
+      b.set_selection(and_masks(tc, mask, b.selection(tc))); out = std::move(b); return true;
     }
   };
   std::unique_ptr<Stream> execute(int p, const TaskContext& tc) const override { return std::unique_ptr<Stream>(new S(this, input->run(p, tc), tc)); }
@@ -873,9 +887,7 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
       const int64_t m = pidx.len(); chunk_last.clear(); if (!m) return;
       std::vector<uint32_t> pos; for (int64_t e = bsz; ; e += bsz) { pos.push_back((uint32_t)((e < m ? e : m) - 1)); if (e >= m) break; }
       if (pos.size() == 1) { chunk_last.push_back((uint32_t)last_u32(pidx)); return; }
-      dfgpu_array_desc d{}; d.type = DFGPU_UINT32; d.length = (int64_t)pos.size(); d.values = pos.data();
-      dfgpu_array* a = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &d, &a)); ArrayRef at = ArrayRef::adopt(a);
-      ArrayRef ends = take(tc, pidx, at); chunk_last.resize(pos.size());
+      ArrayRef ends = take(tc, pidx, host_u32(tc, pos.data(), (int64_t)pos.size())); chunk_last.resize(pos.size());
       tc.check(dfgpu_array_export_host(tc.ctx, ends.a, chunk_last.data(), nullptr, nullptr));
     }
     ArrayRef slice_of(const ArrayRef& a, int64_t off, int64_t len) { dfgpu_array* s1 = nullptr; tc.check(dfgpu_array_slice(tc.ctx, a.a, off, len, &s1)); return ArrayRef::adopt(s1); }
@@ -980,7 +992,7 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
         PendingPredicate pend; ArrayRef mask;
         if (pb.has_pending() && !bs->empty) mask = pb.take_filter(&pend); else { mask = pb.selection(tc); pb.set_selection(ArrayRef()); }
         ArrayRef bidx, pidx;
-        if (bs->empty) { dfgpu_array *a = nullptr, *b = nullptr; dfgpu_array_desc d{}; d.type = DFGPU_UINT64; d.values = &d; tc.check(dfgpu_array_import_host(tc.ctx, &d, &a)); d.type = DFGPU_UINT32; tc.check(dfgpu_array_import_host(tc.ctx, &d, &b)); bidx = ArrayRef::adopt(a); pidx = ArrayRef::adopt(b); }
+        if (bs->empty) { bidx = host_u64(tc, nullptr, 0); pidx = host_u32(tc, nullptr, 0); }
         else {
           std::vector<ArrayRef> keys; std::vector<const dfgpu_array*> kp;
           for (auto& e : op->on_r) { keys.push_back(into_array(tc, e->eval(tc, pb), pb.base_rows)); kp.push_back(keys.back().a); }
@@ -1071,8 +1083,7 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
       ArrayRef lidx;
       if (!have_right) {
         if (!anti) return o;
-        dfgpu_array *e0 = nullptr, *e1 = nullptr; dfgpu_array_desc d{}; d.type = DFGPU_UINT64; d.values = &d; tc.check(dfgpu_array_import_host(tc.ctx, &d, &e0)); ArrayRef b0 = ArrayRef::adopt(e0);
-        d.type = DFGPU_UINT32; tc.check(dfgpu_array_import_host(tc.ctx, &d, &e1)); ArrayRef p0 = ArrayRef::adopt(e1);
+        ArrayRef b0 = host_u64(tc, nullptr, 0), p0 = host_u32(tc, nullptr, 0);
         dfgpu_array *b2 = nullptr, *p2 = nullptr; tc.check(dfgpu_join_adjust_indices(tc.ctx, b0.a, p0.a, 0, lb.base_rows, DFGPU_JOIN_RIGHT_ANTI, &b2, &p2)); ArrayRef drop = ArrayRef::adopt(b2); lidx = ArrayRef::adopt(p2);
       } else {
         std::vector<ArrayRef> rk, lk; std::vector<const dfgpu_array*> rp, lp;
@@ -1107,7 +1118,7 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
       if (bs->segments.size() <= 1 || fidx.len() == 0) return fidx;
       std::vector<int64_t> bounds{0}; for (auto s : bs->segments) bounds.push_back(bounds.back() + s);
       if (bs->segments.size() <= 64) {          // on the device: the ascending index list is cut at the batch boundaries and the pieces are put back last batch first
-        auto scalar = [&](uint64_t v) { dfgpu_array_desc d{}; d.type = DFGPU_UINT64; d.length = 1; d.values = &v; dfgpu_array* a = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &d, &a)); return ArrayRef::adopt(a); };
+        auto scalar = [&](uint64_t v) { return host_u64(tc, &v, 1); };
         std::vector<ArrayRef> pieces;
         for (size_t sg = bs->segments.size(); sg-- > 0;) {
           ArrayRef lo = scalar((uint64_t)bounds[sg]), hi = scalar((uint64_t)bounds[sg + 1]); dfgpu_array *ge = nullptr, *lt = nullptr, *both = nullptr, *part = nullptr;
@@ -1126,8 +1137,7 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
       for (size_t sg = 1; sg < bounds.size(); sg++) cut.push_back((size_t)(std::lower_bound(h.begin(), h.end(), (uint64_t)bounds[sg]) - h.begin()));
       std::vector<uint64_t> o; o.reserve((size_t)n);
       for (size_t sg = bs->segments.size(); sg-- > 0;) o.insert(o.end(), h.begin() + (std::ptrdiff_t)cut[sg], h.begin() + (std::ptrdiff_t)cut[sg + 1]);
-      dfgpu_array_desc d{}; d.type = DFGPU_UINT64; d.length = n; d.values = o.data();
-      dfgpu_array* a = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &d, &a)); return ArrayRef::adopt(a);
+      return host_u64(tc, o.data(), n);
     }
   };
   std::unique_ptr<Stream> execute(int p, const TaskContext& tc) const override { return std::unique_ptr<Stream>(new S(this, p, tc)); }
@@ -1377,7 +1387,7 @@ static const char* agg_fun_name(int k) { switch (k) { case DFGPU_AGG_SUM: return
 // every group's first row.  The state of Partial is the value itself (min_max.rs state() = [evaluate()]), so every mode works.
 struct StringMinMax {
   bool is_max = false; ArrayRef gids, vals;
-  static ArrayRef true1(const TaskContext& tc) { uint64_t one = 1; dfgpu_array_desc d{}; d.type = DFGPU_BOOL; d.length = 1; d.values = &one; dfgpu_array* a = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &d, &a)); return ArrayRef::adopt(a); }
+  static ArrayRef true1(const TaskContext& tc) { const uint64_t one = 1; return host_array(tc, DFGPU_BOOL, &one, 1); }
   static ArrayRef slice(const TaskContext& tc, const ArrayRef& a, int64_t off, int64_t len) { dfgpu_array* o = nullptr; tc.check(dfgpu_array_slice(tc.ctx, a.a, off, len, &o)); return ArrayRef::adopt(o); }
   void reduce(const TaskContext& tc, ArrayRef g, ArrayRef v) {
     const int64_t n = g.len();
@@ -1394,8 +1404,7 @@ struct StringMinMax {
   void update(const TaskContext& tc, const ArrayRef& g_in, ArrayRef v_in, const ArrayRef& filter) {
     dfgpu_array_desc d; dfgpu_array_describe(v_in.a, &d);
     if (d.type == DFGPU_DICTIONARY) { dfgpu_array* c = nullptr; tc.check(dfgpu_cast(tc.ctx, v_in.a, DFGPU_UTF8, 0, 0, &c)); v_in = ArrayRef::adopt(c); }
-    dfgpu_array* nn = nullptr; tc.check(dfgpu_is_null(tc.ctx, v_in.a, 1, &nn)); ArrayRef mask = ArrayRef::adopt(nn);
-    if (filter) { ArrayRef kf = known_mask(tc, filter); dfgpu_array* o = nullptr; tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_AND, mask.a, 0, kf.a, 0, &o)); mask = ArrayRef::adopt(o); }
+    dfgpu_array* nn = nullptr; tc.check(dfgpu_is_null(tc.ctx, v_in.a, 1, &nn)); ArrayRef mask = and_masks(tc, filter, ArrayRef::adopt(nn));
     dfgpu_array *fg = nullptr, *fv = nullptr; tc.check(dfgpu_filter(tc.ctx, g_in.a, mask.a, &fg)); ArrayRef g = ArrayRef::adopt(fg); tc.check(dfgpu_filter(tc.ctx, v_in.a, mask.a, &fv)); ArrayRef v = ArrayRef::adopt(fv);
     if (gids && gids.len()) { std::vector<ArrayRef> gp{gids, g}, vp{vals, v}; g = concat_arrays(tc, gp); v = concat_arrays(tc, vp); }
     reduce(tc, g, v);
@@ -1411,12 +1420,15 @@ struct StringMinMax {
 // COUNT(DISTINCT x) (physical-expr/src/aggregate/count_distinct/: a set of values per group): the (group id, value) pairs are interned in a GroupValues of their own;
 // every NEW pair adds one to its group's count.  Partial emits the reference's state -- one List of distinct values per group -- in the Utf8 layout (state()), Final /
 // FinalPartitioned merge such lists (merge()); fixed-width arguments as packed values, Utf8 arguments as (length, bytes) strings (count_distinct/bytes.rs:47-75).
+static void grow_to(const TaskContext& tc, dfgpu_acc* acc, int64_t total) {       // zero-row update: grow the state to `total` groups
+  ArrayRef empty_ids = host_u32(tc, nullptr, 0);
+  tc.check(dfgpu_acc_update_batch(tc.ctx, acc, nullptr, empty_ids.a, nullptr, total));
+}
 struct CountDistinct {
   GroupsRef pairs; AccRef cnt;
   void init(const TaskContext& tc) { tc.check(dfgpu_groups_new(tc.ctx, 2, &pairs.g)); tc.check(dfgpu_acc_new(tc.ctx, DFGPU_AGG_COUNT, DFGPU_INT64, 0, 0, &cnt.a)); }
   void update(const TaskContext& tc, const ArrayRef& g_in, const ArrayRef& v_in, const ArrayRef& filter, int64_t total) {
-    dfgpu_array* nn = nullptr; tc.check(dfgpu_is_null(tc.ctx, v_in.a, 1, &nn)); ArrayRef mask = ArrayRef::adopt(nn);
-    if (filter) { ArrayRef kf = known_mask(tc, filter); dfgpu_array* o = nullptr; tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_AND, mask.a, 0, kf.a, 0, &o)); mask = ArrayRef::adopt(o); }
+    dfgpu_array* nn = nullptr; tc.check(dfgpu_is_null(tc.ctx, v_in.a, 1, &nn)); ArrayRef mask = and_masks(tc, filter, ArrayRef::adopt(nn));
     const int64_t before = dfgpu_groups_len(pairs.g);
     const dfgpu_array* kp[2] = { g_in.a, v_in.a }; dfgpu_array* ids = nullptr; tc.check(dfgpu_groups_intern(tc.ctx, pairs.g, kp, 2, mask.a, &ids)); ArrayRef drop = ArrayRef::adopt(ids);
     const int64_t fresh = dfgpu_groups_len(pairs.g) - before;
@@ -1427,8 +1439,7 @@ struct CountDistinct {
     }
   }
   ArrayRef emit(const TaskContext& tc, int64_t total) {
-    dfgpu_array_desc ed{}; ed.type = DFGPU_UINT32; ed.values = &ed; dfgpu_array* e = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &ed, &e)); ArrayRef empty_ids = ArrayRef::adopt(e);
-    tc.check(dfgpu_acc_update_batch(tc.ctx, cnt.a, nullptr, empty_ids.a, nullptr, total));
+    grow_to(tc, cnt.a, total);
     dfgpu_array* v = nullptr; tc.check(dfgpu_acc_evaluate(tc.ctx, cnt.a, &v)); return ArrayRef::adopt(v);
   }
   // state() (count_distinct/native.rs:97-110: one List of the group's distinct values): the interned (group, value) pairs ordered by group -- stable, so a group's values
@@ -1460,6 +1471,46 @@ struct HostColumn { ArrowArray a{}; ArrowSchema s{}; bool live = false;
   ~HostColumn() { if (live) { if (a.release) a.release(&a); if (s.release) s.release(&s); } } };
 struct SpillPiece { std::vector<HostColumn> cols; int64_t rows = 0; };
 struct SpillRun { std::vector<SpillPiece> pieces; };
+// bounds[r] = first row of range r in a batch sorted on its first desc.size() columns (`cols`; number of splitters + 2 entries).  The first call fixes the splitters: K - 1
+// of its rows at equal distances.  Splitter keys and rows are concatenated (splitters first) and ordered by the stable sort: a splitter lands in front of the rows
+// equal to it, so position of splitter j in the order minus j = rows strictly below it.
+static std::vector<int64_t> range_bounds(const TaskContext& tc, const char* who, std::vector<ArrayRef>& splitters, const std::vector<ArrayRef>& cols, const std::vector<uint8_t>& desc, const std::vector<uint8_t>& nulls_first, int64_t K) {
+  const int64_t rows = cols[0].len(); const size_t nk = desc.size();
+  if (splitters.empty()) {
+    std::vector<uint32_t> at; for (int64_t j = 1; j < K; j++) at.push_back((uint32_t)(rows * j / K));
+    if (at.empty()) at.push_back(0);               // one range: a splitter in front of everything keeps the code below uniform (range 0 is empty, range 1 is the run)
+    ArrayRef ix = host_u32(tc, at.data(), (int64_t)at.size());
+    for (size_t k = 0; k < nk; k++) splitters.push_back(take(tc, cols[k], ix));
+  }
+  const int64_t ns = splitters[0].len();
+  std::vector<ArrayRef> both; std::vector<const dfgpu_array*> bp;
+  for (size_t k = 0; k < nk; k++) { const dfgpu_array* two[2] = { splitters[k].a, cols[k].a }; dfgpu_array* c = nullptr; tc.check(dfgpu_concat(tc.ctx, two, 2, &c)); both.push_back(ArrayRef::adopt(c)); bp.push_back(both.back().a); }
+  dfgpu_array* idx = nullptr; tc.check(dfgpu_sort_to_indices(tc.ctx, bp.data(), desc.data(), nulls_first.data(), (int32_t)nk, -1, &idx)); ArrayRef order = ArrayRef::adopt(idx);
+  const uint32_t nsv = (uint32_t)ns; ArrayRef lit = host_u32(tc, &nsv, 1);
+  dfgpu_array* m = nullptr; tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_LT, order.a, 0, lit.a, 1, &m)); ArrayRef is_split = ArrayRef::adopt(m);
+  ArrayRef pos = mask_indices(tc, is_split);
+  if (pos.len() != ns) fail(DFGPU_INTERNAL, "%s spill: %lld splitter positions for %lld splitters", who, (long long)pos.len(), (long long)ns);
+  std::vector<uint32_t> hp((size_t)ns); tc.check(dfgpu_array_export_host(tc.ctx, pos.a, hp.data(), nullptr, nullptr));
+  std::vector<int64_t> bounds; bounds.push_back(0);
+  for (int64_t j = 0; j < ns; j++) bounds.push_back((int64_t)hp[(size_t)j] - j);      // splitters keep their own order (they are rows of a sorted run and the sort is stable)
+  bounds.push_back(rows);
+  return bounds;
+}
+// the sorted columns cut at `bounds` and copied to host memory, one piece per range (an empty range keeps no columns)
+static SpillRun spill_ranges(const TaskContext& tc, const std::vector<ArrayRef>& cols, const std::vector<int64_t>& bounds) {
+  SpillRun run; run.pieces.resize(bounds.size() - 1);
+  for (size_t r = 0; r + 1 < bounds.size(); r++) {
+    const int64_t lo = bounds[r], len = bounds[r + 1] - bounds[r]; run.pieces[r].rows = len; if (len <= 0) continue;
+    for (auto& c : cols) { dfgpu_array* sl = nullptr; tc.check(dfgpu_array_slice(tc.ctx, c.a, lo, len, &sl)); ArrayRef piece = ArrayRef::adopt(sl);
+      run.pieces[r].cols.emplace_back(); HostColumn& h = run.pieces[r].cols.back(); tc.check(dfgpu_array_export_arrow(tc.ctx, piece.a, &h.a, &h.s)); h.live = true; }
+  }
+  return run;
+}
+// one piece back on the device; its host copy goes
+static std::vector<ArrayRef> unspill(const TaskContext& tc, SpillPiece& pc) {
+  std::vector<ArrayRef> cols; for (auto& h : pc.cols) { dfgpu_array* a = nullptr; tc.check(dfgpu_array_import_arrow(tc.ctx, &h.a, &h.s, &a)); cols.push_back(ArrayRef::adopt(a)); }
+  pc.cols.clear(); return cols;
+}
 
 struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggregateStream row_hash.rs:423-662
   int mode; std::vector<ExprPtr> gexprs; std::vector<std::string> gnames; std::vector<AggExpr> aggs; PlanPtr input; mutable SchemaPtr sch; mutable std::mutex mu;
@@ -1477,6 +1528,14 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
   bool is_string_minmax(size_t i) const { return (aggs[i].kind == DFGPU_AGG_MIN || aggs[i].kind == DFGPU_AGG_MAX) && aggs[i].type == DFGPU_UTF8; }
   bool special(size_t i) const { return aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT || is_string_minmax(i); }
   bool any_special() const { for (size_t i = 0; i < aggs.size(); i++) if (special(i)) return true; return false; }
+  struct AggState;
+  // One input batch as the update paths see it: `b` is the batch above the input ProjectionExec when that was looked through (`raw` is the batch below it); its columns
+  // marked in `deferred` have not been evaluated yet.
+  struct InBatch {
+    const TaskContext& tc; const ProjectionExec* pj; Batch raw; Batch& b; std::vector<bool> deferred;
+    void ensure(int ci) { if (ci >= 0 && ci < (int)deferred.size() && deferred[(size_t)ci]) { pj->evaluate_deferred(tc, raw, b, (size_t)ci); deferred[(size_t)ci] = false; } }
+    void ensure_all() { for (size_t ci = 0; ci < deferred.size(); ci++) ensure((int)ci); }
+  };
   // The accumulator arguments as ONE expression DAG over plain columns (common subexpressions shared; references to deferred projection
   // columns expand into the projection's expression over ITS input) handed to dfgpu_acc_update_batch_fused.  false = shape not taken,
   // nothing was accumulated: the caller evaluates the arguments node by node.
@@ -1509,27 +1568,29 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
       return -1;
     }
   };
-  bool try_fused(const TaskContext& tc, const ProjectionExec* pj, Batch& raw, Batch& b, const std::vector<bool>& deferred, std::vector<AccRef>& accs,
-                 const ArrayRef& gids, const ArrayRef& filt, int64_t total) const {
+  bool try_fused(AggState& S, InBatch& in, const ArrayRef& gids, const ArrayRef& filt, int64_t total) const {
+    const TaskContext& tc = S.tc; const std::vector<bool>& deferred = in.deferred;
     bool computed = false;          // worth it only when some argument is an expression, not a stored column
     for (auto& a : aggs) { if (a.filter || (a.kind != DFGPU_AGG_SUM && a.kind != DFGPU_AGG_AVG && a.kind != DFGPU_AGG_COUNT)) return false;
       if (a.arg) { int ci = a.arg->column_index(); computed |= ci < 0 || (ci < (int)deferred.size() && deferred[(size_t)ci]); } }
     if (!computed) return false;
-    DagBuilder d{tc, pj, raw, b, deferred};
+    DagBuilder d{tc, in.pj, in.raw, in.b, deferred};
     std::vector<int32_t> acc_nodes; std::vector<dfgpu_acc*> ap;
     for (size_t i = 0; i < aggs.size(); i++) {
       int nd = -1;
       if (aggs[i].arg && aggs[i].kind != DFGPU_AGG_COUNT) { nd = d.build(aggs[i].arg.get(), false); if (nd < 0) return false; }
       else if (aggs[i].arg) return false;      // COUNT(expr) counts non-NULL values: leave it to the ordinary path
-      acc_nodes.push_back(nd); ap.push_back(accs[i].a);
+      acc_nodes.push_back(nd); ap.push_back(S.accs[i].a);
     }
     dfgpu_status st = dfgpu_acc_update_batch_fused(tc.ctx, ap.data(), acc_nodes.data(), (int32_t)ap.size(), d.nodes.data(), (int32_t)d.nodes.size(), d.cols.data(), (int32_t)d.cols.size(), gids.a, filt.a, total);
     if (st == DFGPU_NOT_IMPLEMENTED) return false;
     tc.check(st); return true;
   }
   // dfgpu_agg_preaggregate over one batch, then intern + merge_batch of its partial rows.  false = shape not taken, nothing accumulated.
-  template <typename Ensure>
-  bool preaggregate(const TaskContext& tc, const ProjectionExec* pj, Batch& raw, Batch& b, const std::vector<bool>& deferred, Ensure&& ensure, const std::vector<const dfgpu_array*>& keyv, const ArrayRef& mask, GroupsRef& groups, std::vector<AccRef>& accs, ArrayRef* pending) const {
+  bool preaggregate(AggState& S, InBatch& in, const std::vector<ArrayRef>& keys, const ArrayRef& mask) const {
+    const TaskContext& tc = S.tc; const ProjectionExec* pj = in.pj; Batch& raw = in.raw; Batch& b = in.b; const std::vector<bool>& deferred = in.deferred;
+    ArrayRef* pending = S.spill ? nullptr : &S.pending;
+    std::vector<const dfgpu_array*> keyv; for (auto& k : keys) keyv.push_back(k.a);
     const int32_t nk = (int32_t)keyv.size();
     std::vector<ArrayRef> vals(aggs.size()); std::vector<const dfgpu_array*> vp; std::vector<int32_t> kinds;
     for (auto& a : aggs) if (a.filter) return false;
@@ -1546,6 +1607,10 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
       if (*src == &b && ci < (int)deferred.size() && deferred[(size_t)ci]) return -1;
       return ci;
     };
+    auto evaluated = [&](size_t i) {            // the argument as an array, its deferred columns evaluated first
+      std::set<int> need; aggs[i].arg->columns(need); for (int ci : need) in.ensure(ci);
+      return into_array(tc, aggs[i].arg->eval(tc, b), b.base_rows);
+    };
     std::vector<int32_t> casts(aggs.size(), 0); bool any_cast = false;
     for (size_t i = 0; i < aggs.size(); i++) {
       if (aggs[i].arg) {
@@ -1559,10 +1624,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
           const bool is_int = d.type == DFGPU_INT32 || d.type == DFGPU_INT64;
           if (is_int && (aggs[i].kind == DFGPU_AGG_SUM || aggs[i].kind == DFGPU_AGG_AVG || aggs[i].kind == DFGPU_AGG_MIN || aggs[i].kind == DFGPU_AGG_MAX || aggs[i].kind == DFGPU_AGG_COUNT)) { vals[i] = col; casts[i] = DFGPU_FLOAT64; any_cast = true; }
         }
-        if (!casts[i]) {
-          std::set<int> need; aggs[i].arg->columns(need); for (int ci2 : need) ensure(ci2);
-          vals[i] = into_array(tc, aggs[i].arg->eval(tc, b), b.base_rows);
-        }
+        if (!casts[i]) vals[i] = evaluated(i);
       }
       vp.push_back(vals[i].a); kinds.push_back(aggs[i].kind);
     }
@@ -1570,7 +1632,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
     dfgpu_status rc = dfgpu_agg_preaggregate_flags(tc.ctx, keyv.data(), nk, kinds.data(), vp.data(), any_cast ? casts.data() : nullptr, (int32_t)aggs.size(), mask.a, any_group_order ? DFGPU_PREAGG_ANY_ORDER : 0, pk, st.data());
     if (rc == DFGPU_NOT_IMPLEMENTED && any_cast) {          // declined with the casts (a shape limit): the arguments as arrays, as before
       vp.clear();
-      for (size_t i = 0; i < aggs.size(); i++) { if (casts[i]) { std::set<int> need; aggs[i].arg->columns(need); for (int ci2 : need) ensure(ci2); vals[i] = into_array(tc, aggs[i].arg->eval(tc, b), b.base_rows); } vp.push_back(vals[i].a); }
+      for (size_t i = 0; i < aggs.size(); i++) { if (casts[i]) vals[i] = evaluated(i); vp.push_back(vals[i].a); }
       rc = dfgpu_agg_preaggregate_flags(tc.ctx, keyv.data(), nk, kinds.data(), vp.data(), nullptr, (int32_t)aggs.size(), mask.a, any_group_order ? DFGPU_PREAGG_ANY_ORDER : 0, pk, st.data());
     }
     if (rc == DFGPU_NOT_IMPLEMENTED) return false;
@@ -1580,20 +1642,31 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
     // A FIRST batch whose partial rows hold every key once (in first-seen order) needs no hash table to number its groups: ids are 0, 1, ..; the keys wait
     // in `pending` and are interned only if another batch follows (merge_partial with pending == nullptr), else they are emitted as they are.
     int64_t distinct = 0, fs = 1; dfgpu_ctx_get_option(tc.ctx, "agg_preaggregate_distinct", &distinct); dfgpu_ctx_get_option(tc.ctx, "first_seen_group_order", &fs); distinct = distinct && (fs || any_group_order);
-    if (nk == 1 && pending && distinct && dfgpu_groups_len(groups.g) == 0 && !*pending) { *pending = pkeys; merge_partial(tc, {}, states, pkeys.len(), groups, accs); return true; }
-    merge_partial(tc, pkeyv, states, 0, groups, accs);
+    if (nk == 1 && pending && distinct && dfgpu_groups_len(S.groups.g) == 0 && !*pending) { *pending = pkeys; merge_partial(S, {}, states, pkeys.len()); return true; }
+    merge_partial(S, pkeyv, states, 0);
     return true;
   }
-  // intern the partial rows' keys (or take ids 0 .. n-1 when `keys` is empty) and merge their states
-  void merge_partial(const TaskContext& tc, const std::vector<ArrayRef>& keys, const std::vector<ArrayRef>& states, int64_t n_ids, GroupsRef& groups, std::vector<AccRef>& accs) const {
-    dfgpu_array* ids = nullptr; int64_t total;
-    if (!keys.empty()) { std::vector<const dfgpu_array*> kp; for (auto& k : keys) kp.push_back(k.a); tc.check(dfgpu_groups_intern(tc.ctx, groups.g, kp.data(), (int32_t)kp.size(), nullptr, &ids)); total = dfgpu_groups_len(groups.g); }
+  int nstates(size_t i) const { return aggs[i].kind == DFGPU_AGG_AVG ? 2 : 1; }
+  // merge_batch of every aggregate's state columns into its accumulator.  `states` starts at the first state column: one per aggregate, two (count, sum) for AVG, in
+  // the order of the aggregates.  An aggregate without a kernel accumulator is passed over with its column: its owner merges that one.
+  void merge_states(const TaskContext& tc, std::vector<AccRef>& accs, const dfgpu_array* const* states, const ArrayRef& gids, const ArrayRef& row_mask, int64_t total) const {
+    for (size_t i = 0; i < aggs.size(); states += nstates(i), i++)
+      if (accs[i].a) tc.check(dfgpu_acc_merge_batch(tc.ctx, accs[i].a, states, nstates(i), gids.a, row_mask.a, total));
+  }
+  // the state columns of a batch that a Partial stage emitted: they follow the keys
+  std::vector<const dfgpu_array*> state_columns(const TaskContext& tc, Batch& b) const {
+    std::vector<const dfgpu_array*> st; int col = (int)gexprs.size();
+    for (size_t i = 0; i < aggs.size(); i++) for (int k = 0; k < nstates(i); k++) st.push_back(b.column(tc, col++).a);
+    return st;
+  }
+  // intern the partial rows' keys (or take ids 0 .. n-1 when `keys` is empty) and merge their states (dfgpu_agg_preaggregate's layout: two slots per aggregate)
+  void merge_partial(AggState& S, const std::vector<ArrayRef>& keys, const std::vector<ArrayRef>& states, int64_t n_ids) const {
+    const TaskContext& tc = S.tc; dfgpu_array* ids = nullptr; int64_t total;
+    if (!keys.empty()) { std::vector<const dfgpu_array*> kp; for (auto& k : keys) kp.push_back(k.a); tc.check(dfgpu_groups_intern(tc.ctx, S.groups.g, kp.data(), (int32_t)kp.size(), nullptr, &ids)); total = dfgpu_groups_len(S.groups.g); }
     else { tc.check(dfgpu_array_iota(tc.ctx, n_ids, &ids)); total = n_ids; }
     ArrayRef gids = ArrayRef::adopt(ids);
-    for (size_t i = 0; i < aggs.size(); i++) {
-      const dfgpu_array* sp[2] = { states[2 * i].a, states[2 * i + 1].a };
-      tc.check(dfgpu_acc_merge_batch(tc.ctx, accs[i].a, sp, aggs[i].kind == DFGPU_AGG_AVG ? 2 : 1, gids.a, nullptr, total));
-    }
+    std::vector<const dfgpu_array*> sp; for (size_t i = 0; i < aggs.size(); i++) for (int k = 0; k < nstates(i); k++) sp.push_back(states[2 * i + (size_t)k].a);
+    merge_states(tc, S.accs, sp.data(), gids, ArrayRef(), total);
   }
   // evaluate_group_by + the per-set loop of group_aggregate_batch (aggregates/mod.rs:1161-1200, row_hash.rs:540-600): keys and accumulator
   // arguments are evaluated once per batch; every grouping set interns its own key tuples (masked keys come from null_exprs) into the
@@ -1602,27 +1675,20 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
     std::vector<ArrayRef> keys, nulls, vals(aggs.size()), filts(aggs.size());
     for (auto& e : gexprs) keys.push_back(into_array(tc, e->eval(tc, b), b.base_rows));
     for (auto& e : null_exprs) nulls.push_back(into_array(tc, e->eval(tc, b), b.base_rows));
-    for (size_t i = 0; i < aggs.size(); i++) {
-      if (merging()) continue;
+    std::vector<dfgpu_acc*> ap; std::vector<const dfgpu_array*> vp, fp, states;
+    if (merging()) states = state_columns(tc, b);
+    else for (size_t i = 0; i < aggs.size(); i++) {
       if (aggs[i].arg) vals[i] = into_array(tc, aggs[i].arg->eval(tc, b), b.base_rows);
       if (aggs[i].filter) filts[i] = into_array(tc, aggs[i].filter->eval(tc, b), b.base_rows);
+      ap.push_back(accs[i].a); vp.push_back(vals[i].a); fp.push_back(filts[i].a);
     }
     for (auto& set : sets) {
       std::vector<const dfgpu_array*> gp;
       for (size_t i = 0; i < keys.size(); i++) gp.push_back(set[i] ? nulls[i].a : keys[i].a);
       dfgpu_array* ids = nullptr; tc.check(dfgpu_groups_intern(tc.ctx, groups.g, gp.data(), (int32_t)gp.size(), mask.a, &ids)); ArrayRef gids = ArrayRef::adopt(ids);
       int64_t total = dfgpu_groups_len(groups.g);
-      size_t col = gexprs.size();
-      std::vector<dfgpu_acc*> ap; std::vector<const dfgpu_array*> vp, fp;
-      for (size_t i = 0; i < aggs.size(); i++) {
-        if (merging()) {
-          int nst = aggs[i].kind == DFGPU_AGG_AVG ? 2 : 1; const dfgpu_array* st[2];
-          for (int k = 0; k < nst; k++) st[k] = b.column(tc, (int)(col + (size_t)k)).a;
-          col += (size_t)nst;
-          tc.check(dfgpu_acc_merge_batch(tc.ctx, accs[i].a, st, nst, gids.a, nullptr, total));
-        } else { ap.push_back(accs[i].a); vp.push_back(vals[i].a); fp.push_back(filts[i].a); }
-      }
-      if (!ap.empty()) tc.check(dfgpu_acc_update_batch_multi(tc.ctx, ap.data(), vp.data(), fp.data(), (int32_t)ap.size(), gids.a, total));
+      if (merging()) merge_states(tc, accs, states.data(), gids, ArrayRef(), total);
+      else if (!ap.empty()) tc.check(dfgpu_acc_update_batch_multi(tc.ctx, ap.data(), vp.data(), fp.data(), (int32_t)ap.size(), gids.a, total));
     }
   }
   std::vector<std::string> out_names() const { return out_names(mode == 0); }
@@ -1647,144 +1713,144 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
     auto SP = std::make_shared<AggState>(tc); AggState& S = *SP;
     // An input ProjectionExec is looked through: its computed columns that only feed accumulator arguments are evaluated inside the
     // accumulate pass (dfgpu_acc_update_batch_fused) instead of being written out as columns first.
-    int64_t fuse_min_rows = 1 << 20; dfgpu_ctx_get_option(tc.ctx, "fused_aggregate_min_rows", &fuse_min_rows);
-    int64_t preagg_min_rows = 1 << 22, preagg_on = 1; dfgpu_ctx_get_option(tc.ctx, "agg_partitioned_min_rows", &preagg_min_rows); dfgpu_ctx_get_option(tc.ctx, "agg_partitioned", &preagg_on);
-    if (!preagg_on) preagg_min_rows = INT64_MAX;
-    const ProjectionExec* pj = (!merging() && !aggs.empty() && fuse_min_rows >= 0) ? dynamic_cast<const ProjectionExec*>(input.get()) : nullptr;
-    const PlanPtr& src = pj ? pj->input : input;
-    if (mode == 1 || mode == 3) { for (int p = 0; p < src->partitions(); p++) S.parts.push_back(p); } else S.parts.push_back(partition);
-    const bool grouped = !gexprs.empty();      // false: AggregateStream (aggregates/no_grouping.rs): one implicit group
-    GroupsRef& groups = S.groups; if (grouped) tc.check(dfgpu_groups_new(tc.ctx, (int32_t)gexprs.size(), &groups.g));
-    S.accs = std::vector<AccRef>(aggs.size()); S.smm = std::vector<StringMinMax>(aggs.size()); S.cds = std::vector<CountDistinct>(aggs.size());
-    std::vector<AccRef>& accs = S.accs; std::vector<StringMinMax>& smm = S.smm; std::vector<CountDistinct>& cds = S.cds;
-    const bool specials = any_special();
+    dfgpu_ctx_get_option(tc.ctx, "fused_aggregate_min_rows", &S.fuse_min_rows);
+    int64_t preagg_on = 1; dfgpu_ctx_get_option(tc.ctx, "agg_partitioned_min_rows", &S.preagg_min_rows); dfgpu_ctx_get_option(tc.ctx, "agg_partitioned", &preagg_on);
+    if (!preagg_on || order_mode != 0) S.preagg_min_rows = INT64_MAX;        // ordered input is clustered on its keys: run numbering, and the group table has to hold every id for EmitTo::First
+    S.pj = (!merging() && !aggs.empty() && S.fuse_min_rows >= 0) ? dynamic_cast<const ProjectionExec*>(input.get()) : nullptr;
+    S.src = S.pj ? S.pj->input : input;
+    if (mode == 1 || mode == 3) { for (int p = 0; p < S.src->partitions(); p++) S.parts.push_back(p); } else S.parts.push_back(partition);
+    S.grouped = !gexprs.empty();      // false: AggregateStream (aggregates/no_grouping.rs): one implicit group
+    if (S.grouped) tc.check(dfgpu_groups_new(tc.ctx, (int32_t)gexprs.size(), &S.groups.g));
+    S.specials = any_special();
+    new_accs(S); S.smm = std::vector<StringMinMax>(aggs.size()); S.cds = std::vector<CountDistinct>(aggs.size());
     for (size_t i = 0; i < aggs.size(); i++) {
-      if (is_string_minmax(i)) { smm[i].is_max = aggs[i].kind == DFGPU_AGG_MAX; continue; }
-      if (aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT) { cds[i].init(tc); continue; }
-      int32_t t = aggs[i].kind == DFGPU_AGG_COUNT ? DFGPU_INT64 : aggs[i].type;
-      tc.check(dfgpu_acc_new(tc.ctx, aggs[i].kind, t, aggs[i].precision, aggs[i].scale, &accs[i].a));
+      if (is_string_minmax(i)) S.smm[i].is_max = aggs[i].kind == DFGPU_AGG_MAX;
+      else if (aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT) S.cds[i].init(tc);
     }
-    { int64_t lim = 0, ranges = 16; dfgpu_ctx_get_option(tc.ctx, "agg_spill_state_bytes", &lim); dfgpu_ctx_get_option(tc.ctx, "agg_spill_ranges", &ranges);
-      if (lim > 0 && grouped && !specials && sets.empty()) { S.spill = std::make_shared<SpillState>(); S.spill->limit = lim; S.spill->ranges = ranges; } }
-    if (order_mode != 0) preagg_min_rows = INT64_MAX;        // ordered input is clustered on its keys: run numbering, and the group table has to hold every id for EmitTo::First
-    S.pj = pj; S.src = src; S.grouped = grouped; S.specials = specials; S.fuse_min_rows = fuse_min_rows; S.preagg_min_rows = preagg_min_rows;
+    int64_t lim = 0, ranges = 16; dfgpu_ctx_get_option(tc.ctx, "agg_spill_state_bytes", &lim); dfgpu_ctx_get_option(tc.ctx, "agg_spill_ranges", &ranges);
+    if (lim > 0 && S.grouped && !S.specials && sets.empty()) { S.spill = std::make_shared<SpillState>(); S.spill->limit = lim; S.spill->ranges = ranges; }
     return SP;
   }
-  void consume(AggState& S, Batch& b_in) const {           // group_aggregate_batch (row_hash.rs:524-613)
-    const TaskContext& tc = S.tc; const ProjectionExec* pj = S.pj; const bool grouped = S.grouped, specials = S.specials; const int64_t fuse_min_rows = S.fuse_min_rows, preagg_min_rows = S.preagg_min_rows;
-    GroupsRef& groups = S.groups; std::vector<AccRef>& accs = S.accs; std::vector<StringMinMax>& smm = S.smm; std::vector<CountDistinct>& cds = S.cds; ArrayRef& pending = S.pending;
-    auto settle_pending = [&]() {  // another batch follows: the keys go into the table after all; first-seen interning of distinct keys numbers them 0 .. n-1 again
-      if (!pending) return;
-      const dfgpu_array* kp = pending.a; dfgpu_array* ids = nullptr; tc.check(dfgpu_groups_intern(tc.ctx, groups.g, &kp, 1, nullptr, &ids)); ArrayRef drop = ArrayRef::adopt(ids);
-      if (dfgpu_groups_len(groups.g) != pending.len()) fail(DFGPU_INTERNAL, "AggregateExec: pre-aggregated keys were not distinct");
-      pending = ArrayRef();
-    };
-    {
-      if (b_in.base_rows == 0) return;
-      // spill_previous_if_necessary (row_hash.rs:667-683): not in Partial mode, not with an ordered input
-      if (S.spill && order_mode == 0 && mode != 0 && !pending && dfgpu_groups_len(groups.g) > 0 && state_bytes(S) > S.spill->limit) spill(S, *S.spill);
-      settle_pending();
-      Batch raw; std::vector<bool> deferred;
-      if (pj) { raw = b_in; b_in = pj->project(tc, raw, &deferred); }
-      Batch& b = b_in;
-      bool any_deferred = false; for (bool d : deferred) any_deferred |= d;
-      auto ensure = [&](int ci) { if (ci >= 0 && ci < (int)deferred.size() && deferred[(size_t)ci]) { pj->evaluate_deferred(tc, raw, b, (size_t)ci); deferred[(size_t)ci] = false; } };
-      if (any_deferred) {         // group keys and accumulator filters read their columns the ordinary way
-        std::set<int> need; for (auto& e : gexprs) e->columns(need); for (auto& a : aggs) if (a.filter) a.filter->columns(need);
-        for (int ci : need) ensure(ci);
-      }
-      if (b.base_rows == 0) return;
-      ArrayRef mask = b.selection(tc); b.set_selection(ArrayRef());
-      if (!sets.empty()) { if (specials) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: COUNT(DISTINCT) / string MIN-MAX under grouping sets on the device"); for (size_t ci = 0; ci < deferred.size(); ci++) ensure((int)ci); group_aggregate_sets(tc, b, mask, groups, accs); return; }
-      ArrayRef gids; int64_t total = 1;
-      if (grouped) {
-        std::vector<ArrayRef> gc; std::vector<const dfgpu_array*> gp;
-        for (auto& e : gexprs) {
-          // A group key that is still a pending gather take(source, indices) from a small source (a dimension attribute carried through
-          // joins: GROUP BY n_name) IS a dictionary array: intern its codes instead of materialising and hashing the values per row.
-          int ci = e->column_index();
-          if (ci >= 0 && ci < (int)b.cols.size() && !b.cols[(size_t)ci].arr && b.cols[(size_t)ci].source && b.cols[(size_t)ci].source.len() * 4 <= b.base_rows) {
-            Col& c = b.cols[(size_t)ci]; dfgpu_array_desc sd; dfgpu_array_describe(c.source.a, &sd);
-            if (sd.type != DFGPU_DICTIONARY) {
-              dfgpu_array* d = nullptr; tc.check(dfgpu_array_make_dictionary(tc.ctx, col_indices(tc, c).a, c.source.a, &d));
-              gc.push_back(ArrayRef::adopt(d)); gp.push_back(gc.back().a); continue;
-            }
-          }
-          gc.push_back(into_array(tc, e->eval(tc, b), b.base_rows)); gp.push_back(gc.back().a);
-        }
-        // A large batch of high-cardinality keys is first reduced to one row per group partition by partition out of LDS (the Partial stage
-        // of a two-phase plan, applied inside the operator): its partial rows are then interned and MERGED like the Final stage does.
-        if (!specials && !merging() && gp.size() >= 1 && gp.size() <= 4 && b.base_rows >= preagg_min_rows && preaggregate(tc, pj, raw, b, deferred, ensure, gp, mask, groups, accs, S.spill ? nullptr : &pending)) return;
-        dfgpu_array* ids = nullptr; tc.check(specials || order_mode == 1 ? dfgpu_groups_intern(tc.ctx, groups.g, gp.data(), (int32_t)gp.size(), mask.a, &ids) : dfgpu_groups_intern_deferred(tc.ctx, groups.g, gp.data(), (int32_t)gp.size(), mask.a, &ids)); gids = ArrayRef::adopt(ids);      // deferred ids: only the accumulators read them
-        total = dfgpu_groups_len(groups.g);
-        if (order_mode == 1 && !specials) note_sort_prefix(S, gp, gids, mask);
-      } else { dfgpu_array* z = nullptr; tc.check(dfgpu_array_new_zeros(tc.ctx, DFGPU_UINT32, 0, 0, b.base_rows, &z)); gids = ArrayRef::adopt(z); }
-      if (!specials && !merging() && total <= 8 && fuse_min_rows >= 0 && b.base_rows >= fuse_min_rows && try_fused(tc, pj, raw, b, deferred, accs, gids, grouped ? ArrayRef() : mask, total)) return;
-      for (size_t ci = 0; ci < deferred.size(); ci++) ensure((int)ci);
-      size_t col = gexprs.size();
-      std::vector<ArrayRef> uvals(aggs.size()), ufilt(aggs.size());       // update mode: all accumulators of the batch go down together
-      for (size_t i = 0; i < aggs.size(); i++) {
-        if (merging() && is_string_minmax(i)) {           // the state column is the value (min_max.rs state())
-          ArrayRef stv = b.column(tc, (int)col); col += 1;
-          smm[i].update(tc, gids, stv, mask);              // rows a fused selection dropped carry no state
-        } else if (merging() && aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT) {      // the state column is the list of the group's distinct values
-          ArrayRef stv = b.column(tc, (int)col); col += 1;
-          cds[i].merge(tc, gids, stv, mask, total, aggs[i].type, aggs[i].precision, aggs[i].scale);
-        } else if (merging()) {
-          int nst = aggs[i].kind == DFGPU_AGG_AVG ? 2 : 1; const dfgpu_array* st[2];
-          for (int k = 0; k < nst; k++) st[k] = b.column(tc, (int)(col + (size_t)k)).a;
-          col += (size_t)nst;
-          tc.check(dfgpu_acc_merge_batch(tc.ctx, accs[i].a, st, nst, gids.a, grouped ? nullptr : mask.a, total));
-        } else {
-          ArrayRef vals, filt;
-          if (aggs[i].arg) vals = into_array(tc, aggs[i].arg->eval(tc, b), b.base_rows);
-          if (aggs[i].filter) filt = into_array(tc, aggs[i].filter->eval(tc, b), b.base_rows);
-          if (!grouped && mask) {         // rows dropped by a fused FilterExec must not reach the single group
-            if (filt) { ArrayRef kf = known_mask(tc, filt); dfgpu_array* o = nullptr; tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_AND, kf.a, 0, mask.a, 0, &o)); filt = ArrayRef::adopt(o); } else filt = mask;
-          }
-          uvals[i] = vals; ufilt[i] = filt;
-        }
-      }
-      if (!merging() && !aggs.empty()) {
-        std::vector<dfgpu_acc*> ap; std::vector<const dfgpu_array*> vp, fp;
-        for (size_t i = 0; i < aggs.size(); i++) {
-          if (special(i)) {
-            ArrayRef f = ufilt[i]; if (grouped && mask) { if (f) { ArrayRef kf = known_mask(tc, f); dfgpu_array* o = nullptr; tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_AND, kf.a, 0, mask.a, 0, &o)); f = ArrayRef::adopt(o); } else f = mask; }
-            if (is_string_minmax(i)) smm[i].update(tc, gids, uvals[i], f); else cds[i].update(tc, gids, uvals[i], f, total);
-            continue;
-          }
-          ap.push_back(accs[i].a); vp.push_back(uvals[i].a); fp.push_back(ufilt[i].a);
-        }
-        if (!ap.empty()) tc.check(dfgpu_acc_update_batch_multi(tc.ctx, ap.data(), vp.data(), fp.data(), (int32_t)ap.size(), gids.a, total));
-      }
+  // another batch follows a first one whose pre-aggregated keys waited in `pending`: the keys go into the table after all; first-seen interning of distinct keys
+  // numbers them 0 .. n-1 again
+  void settle_pending(AggState& S) const {
+    if (!S.pending) return;
+    const dfgpu_array* kp = S.pending.a; dfgpu_array* ids = nullptr; S.tc.check(dfgpu_groups_intern(S.tc.ctx, S.groups.g, &kp, 1, nullptr, &ids)); ArrayRef drop = ArrayRef::adopt(ids);
+    if (dfgpu_groups_len(S.groups.g) != S.pending.len()) fail(DFGPU_INTERNAL, "AggregateExec: pre-aggregated keys were not distinct");
+    S.pending = ArrayRef();
+  }
+  void consume(AggState& S, Batch& b) const {           // group_aggregate_batch (row_hash.rs:524-613)
+    const TaskContext& tc = S.tc;
+    if (b.base_rows == 0) return;
+    // spill_previous_if_necessary (row_hash.rs:667-683): not in Partial mode, not with an ordered input
+    if (S.spill && order_mode == 0 && mode != 0 && !S.pending && dfgpu_groups_len(S.groups.g) > 0 && state_bytes(S) > S.spill->limit) spill(S, *S.spill);
+    settle_pending(S);
+    InBatch in{tc, S.pj, Batch(), b, {}};
+    if (S.pj) { in.raw = b; b = S.pj->project(tc, in.raw, &in.deferred); }
+    if (!in.deferred.empty()) {         // group keys and accumulator filters read their columns the ordinary way
+      std::set<int> need; for (auto& e : gexprs) e->columns(need); for (auto& a : aggs) if (a.filter) a.filter->columns(need);
+      for (int ci : need) in.ensure(ci);
     }
+    if (b.base_rows == 0) return;
+    ArrayRef mask = b.selection(tc); b.set_selection(ArrayRef());
+    if (!sets.empty()) consume_sets(S, in, mask);
+    else if (merging()) consume_merge(S, b, mask);
+    else consume_update(S, in, mask);
+  }
+  void consume_sets(AggState& S, InBatch& in, const ArrayRef& mask) const {
+    if (S.specials) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: COUNT(DISTINCT) / string MIN-MAX under grouping sets on the device");
+    in.ensure_all(); group_aggregate_sets(S.tc, in.b, mask, S.groups, S.accs);
+  }
+  // the group keys of the batch, evaluated (evaluate_group_by for the single set of all keys)
+  std::vector<ArrayRef> group_keys(const TaskContext& tc, Batch& b) const {
+    std::vector<ArrayRef> keys;
+    for (auto& e : gexprs) {
+      // A group key that is still a pending gather take(source, indices) from a small source (a dimension attribute carried through
+      // joins: GROUP BY n_name) IS a dictionary array: intern its codes instead of materialising and hashing the values per row.
+      int ci = e->column_index();
+      if (ci >= 0 && ci < (int)b.cols.size() && !b.cols[(size_t)ci].arr && b.cols[(size_t)ci].source && b.cols[(size_t)ci].source.len() * 4 <= b.base_rows) {
+        Col& c = b.cols[(size_t)ci]; dfgpu_array_desc sd; dfgpu_array_describe(c.source.a, &sd);
+        if (sd.type != DFGPU_DICTIONARY) {
+          dfgpu_array* d = nullptr; tc.check(dfgpu_array_make_dictionary(tc.ctx, col_indices(tc, c).a, c.source.a, &d));
+          keys.push_back(ArrayRef::adopt(d)); continue;
+        }
+      }
+      keys.push_back(into_array(tc, e->eval(tc, b), b.base_rows));
+    }
+    return keys;
+  }
+  // the group id of every one of the batch's `rows` rows -- the evaluated keys interned; all zeros without GROUP BY -- and the number of groups there are now
+  ArrayRef group_ids(AggState& S, const std::vector<ArrayRef>& keys, int64_t rows, const ArrayRef& mask, int64_t* total) const {
+    const TaskContext& tc = S.tc; dfgpu_array* ids = nullptr;
+    if (!S.grouped) { tc.check(dfgpu_array_new_zeros(tc.ctx, DFGPU_UINT32, 0, 0, rows, &ids)); *total = 1; return ArrayRef::adopt(ids); }
+    std::vector<const dfgpu_array*> gp; for (auto& k : keys) gp.push_back(k.a);
+    tc.check(S.specials || order_mode == 1 ? dfgpu_groups_intern(tc.ctx, S.groups.g, gp.data(), (int32_t)gp.size(), mask.a, &ids) : dfgpu_groups_intern_deferred(tc.ctx, S.groups.g, gp.data(), (int32_t)gp.size(), mask.a, &ids));      // deferred ids: only the accumulators read them
+    ArrayRef gids = ArrayRef::adopt(ids); *total = dfgpu_groups_len(S.groups.g);
+    if (order_mode == 1 && !S.specials) note_sort_prefix(S, gp, gids, mask);
+    return gids;
+  }
+  // Final / FinalPartitioned: the batch is a Partial stage's output, its state columns are merged
+  void consume_merge(AggState& S, Batch& b, const ArrayRef& mask) const {
+    const TaskContext& tc = S.tc; int64_t total = 1;
+    ArrayRef gids = group_ids(S, group_keys(tc, b), b.base_rows, mask, &total);
+    std::vector<const dfgpu_array*> st = state_columns(tc, b);
+    for (size_t i = 0, col = 0; i < aggs.size(); col += (size_t)nstates(i), i++) {
+      if (is_string_minmax(i)) S.smm[i].update(tc, gids, ArrayRef::share(st[col]), mask);           // the state column is the value (min_max.rs state()); rows a fused selection dropped carry no state
+      else if (aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT) S.cds[i].merge(tc, gids, ArrayRef::share(st[col]), mask, total, aggs[i].type, aggs[i].precision, aggs[i].scale);      // the state column is the list of the group's distinct values
+    }
+    merge_states(tc, S.accs, st.data(), gids, S.grouped ? ArrayRef() : mask, total);
+  }
+  // Partial / Single / SinglePartitioned: the batch's rows update the accumulators -- pre-aggregated, fused with the evaluation of the arguments, or argument by argument
+  void consume_update(AggState& S, InBatch& in, const ArrayRef& mask) const {
+    const TaskContext& tc = S.tc; Batch& b = in.b;
+    std::vector<ArrayRef> keys = group_keys(tc, b);
+    // A large batch of high-cardinality keys is first reduced to one row per group partition by partition out of LDS (the Partial stage
+    // of a two-phase plan, applied inside the operator): its partial rows are then interned and MERGED like the Final stage does.
+    if (!S.specials && keys.size() >= 1 && keys.size() <= 4 && b.base_rows >= S.preagg_min_rows && preaggregate(S, in, keys, mask)) return;
+    int64_t total = 1; ArrayRef gids = group_ids(S, keys, b.base_rows, mask, &total);
+    if (!S.specials && total <= 8 && S.fuse_min_rows >= 0 && b.base_rows >= S.fuse_min_rows && try_fused(S, in, gids, S.grouped ? ArrayRef() : mask, total)) return;
+    in.ensure_all();
+    std::vector<ArrayRef> vals(aggs.size()), filt(aggs.size()); std::vector<dfgpu_acc*> ap; std::vector<const dfgpu_array*> vp, fp;       // all kernel accumulators of the batch go down together
+    for (size_t i = 0; i < aggs.size(); i++) {
+      if (aggs[i].arg) vals[i] = into_array(tc, aggs[i].arg->eval(tc, b), b.base_rows);
+      if (aggs[i].filter) filt[i] = into_array(tc, aggs[i].filter->eval(tc, b), b.base_rows);
+      // rows dropped by a fused FilterExec must not reach the single group; under GROUP BY their group id makes the kernel accumulators skip them, the others read the mask
+      if (!S.grouped || special(i)) filt[i] = and_masks(tc, filt[i], mask);
+      if (is_string_minmax(i)) S.smm[i].update(tc, gids, vals[i], filt[i]);
+      else if (aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT) S.cds[i].update(tc, gids, vals[i], filt[i], total);
+      else { ap.push_back(S.accs[i].a); vp.push_back(vals[i].a); fp.push_back(filt[i].a); }
+    }
+    if (!ap.empty()) tc.check(dfgpu_acc_update_batch_multi(tc.ctx, ap.data(), vp.data(), fp.data(), (int32_t)ap.size(), gids.a, total));
+  }
+  // the emitted batch's schema: the output names with the types of the columns that leave.  `keep`: it is the operator's schema from now on
+  void stamp_schema(Batch& o, bool as_state, bool keep) const {
+    auto s = std::make_shared<Schema>(); auto names = out_names(as_state);
+    for (size_t i = 0; i < o.cols.size(); i++) s->f.push_back(field_of(names[i], o.cols[i].arr.a));
+    o.schema = s; if (keep) { std::lock_guard<std::mutex> l(mu); sch = s; }
   }
   // emit(EmitTo::All, spilling) (row_hash.rs:626-662): every group as one batch -- state columns when as_state (Partial output, and what a spill holds), else final values
   bool emit_all(AggState& S, bool as_state, Batch* out) const {
-    const TaskContext& tc = S.tc; const bool grouped = S.grouped; GroupsRef& groups = S.groups; std::vector<AccRef>& accs = S.accs; std::vector<StringMinMax>& smm = S.smm; std::vector<CountDistinct>& cds = S.cds; ArrayRef& pending = S.pending;
-    int64_t total = grouped ? (pending ? pending.len() : dfgpu_groups_len(groups.g)) : 1;     // no GROUP BY: always one row, even on empty input
+    const TaskContext& tc = S.tc;
+    int64_t total = S.grouped ? (S.pending ? S.pending.len() : dfgpu_groups_len(S.groups.g)) : 1;     // no GROUP BY: always one row, even on empty input
     if (total > 0) {              // emit(EmitTo::All) (row_hash.rs:626-662)
       Batch o; o.base_rows = total; std::vector<dfgpu_array*> keys(gexprs.size(), nullptr);
-      if (grouped && pending) o.cols.push_back(col_of(pending));          // one key column, already in first-seen order
-      else if (grouped) {
+      if (S.grouped && S.pending) o.cols.push_back(col_of(S.pending));          // one key column, already in first-seen order
+      else if (S.grouped) {
         // keys still "column c at the first row of the run" (one clustered batch): they leave as pending gathers, so that a HAVING above reads the keys of the groups it keeps only
         std::vector<dfgpu_array*> src(gexprs.size(), nullptr); dfgpu_array* rows = nullptr;
-        dfgpu_status st = dfgpu_groups_emit_deferred(tc.ctx, groups.g, src.data(), &rows);
+        dfgpu_status st = dfgpu_groups_emit_deferred(tc.ctx, S.groups.g, src.data(), &rows);
         if (st == DFGPU_OK) { ArrayRef r = ArrayRef::adopt(rows); MemoPtr memo = std::make_shared<TakeMemo>();
           for (auto sp : src) { Col c; c.source = ArrayRef::adopt(sp); c.chain.push_back(r); c.memo = memo; o.cols.push_back(std::move(c)); } }
-        else { if (st != DFGPU_NOT_IMPLEMENTED) tc.check(st); tc.check(dfgpu_groups_emit(tc.ctx, groups.g, keys.data())); for (auto k : keys) o.cols.push_back(col_of(ArrayRef::adopt(k))); }
+        else { if (st != DFGPU_NOT_IMPLEMENTED) tc.check(st); tc.check(dfgpu_groups_emit(tc.ctx, S.groups.g, keys.data())); for (auto k : keys) o.cols.push_back(col_of(ArrayRef::adopt(k))); }
       }
-      dfgpu_array_desc ed{}; ed.type = DFGPU_UINT32; ed.values = &ed; dfgpu_array* e = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &ed, &e)); ArrayRef empty_ids = ArrayRef::adopt(e);
       for (size_t i = 0; i < aggs.size(); i++) {
-        if (is_string_minmax(i)) { o.cols.push_back(col_of(smm[i].emit(tc, total))); continue; }          // state and final value are the same column
-        if (aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT) { o.cols.push_back(col_of(as_state ? cds[i].state(tc, total, aggs[i].type) : cds[i].emit(tc, total))); continue; }
-        tc.check(dfgpu_acc_update_batch(tc.ctx, accs[i].a, nullptr, empty_ids.a, nullptr, total));      // zero-row update: grow the state to `total` groups
-        if (as_state) { dfgpu_array* st[2] = {nullptr, nullptr}; int32_t n = 0; tc.check(dfgpu_acc_state(tc.ctx, accs[i].a, st, &n)); for (int k = 0; k < n; k++) o.cols.push_back(col_of(ArrayRef::adopt(st[k]))); }
-        else { dfgpu_array* v = nullptr; tc.check(dfgpu_acc_evaluate(tc.ctx, accs[i].a, &v)); o.cols.push_back(col_of(ArrayRef::adopt(v))); }
+        if (is_string_minmax(i)) { o.cols.push_back(col_of(S.smm[i].emit(tc, total))); continue; }          // state and final value are the same column
+        if (aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT) { o.cols.push_back(col_of(as_state ? S.cds[i].state(tc, total, aggs[i].type) : S.cds[i].emit(tc, total))); continue; }
+        grow_to(tc, S.accs[i].a, total);
+        if (as_state) { dfgpu_array* st[2] = {nullptr, nullptr}; int32_t n = 0; tc.check(dfgpu_acc_state(tc.ctx, S.accs[i].a, st, &n)); for (int k = 0; k < n; k++) o.cols.push_back(col_of(ArrayRef::adopt(st[k]))); }
+        else { dfgpu_array* v = nullptr; tc.check(dfgpu_acc_evaluate(tc.ctx, S.accs[i].a, &v)); o.cols.push_back(col_of(ArrayRef::adopt(v))); }
       }
-      auto s = std::make_shared<Schema>(); auto names = out_names(as_state);
-      for (size_t i = 0; i < o.cols.size(); i++) s->f.push_back(field_of(names[i], o.cols[i].arr.a));
-      o.schema = s; if (as_state == (mode == 0)) { std::lock_guard<std::mutex> l(mu); sch = s; }
+      stamp_schema(o, as_state, as_state == (mode == 0));
       *out = std::move(o); return true;
     }
     return false;
@@ -1813,65 +1879,31 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
     cols->clear(); for (auto& c : b.cols) cols->push_back(take(S.tc, c.arr, ix));
     return true;
   }
-  // boundaries[r] = first row of range r in a key-sorted state batch (ranges + 1 entries).  Splitter keys and rows are concatenated (splitters first) and ordered by the
-  // stable sort: a splitter lands in front of the rows equal to it, so position of splitter j in the order minus j = rows strictly below it.
-  std::vector<int64_t> range_bounds(AggState& S, SpillState& P, const std::vector<ArrayRef>& cols) const {
-    const TaskContext& tc = S.tc; const int64_t rows = cols[0].len(), K = P.ranges; const size_t nk = gexprs.size();
-    if (P.splitters.empty()) {                   // first spill: K - 1 of its rows at equal distances
-      std::vector<uint32_t> at; for (int64_t j = 1; j < K; j++) at.push_back((uint32_t)(rows * j / K));
-      dfgpu_array_desc d{}; d.type = DFGPU_UINT32; d.length = (int64_t)at.size(); d.values = at.data(); dfgpu_array* ia = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &d, &ia)); ArrayRef ix = ArrayRef::adopt(ia);
-      for (size_t k = 0; k < nk; k++) P.splitters.push_back(take(tc, cols[k], ix));
-    }
-    const int64_t ns = P.splitters[0].len();
-    std::vector<ArrayRef> both; std::vector<const dfgpu_array*> bp;
-    for (size_t k = 0; k < nk; k++) { const dfgpu_array* two[2] = { P.splitters[k].a, cols[k].a }; dfgpu_array* c = nullptr; tc.check(dfgpu_concat(tc.ctx, two, 2, &c)); both.push_back(ArrayRef::adopt(c)); bp.push_back(both.back().a); }
-    std::vector<uint8_t> desc(nk, 0), nf(nk, 1);
-    dfgpu_array* idx = nullptr; tc.check(dfgpu_sort_to_indices(tc.ctx, bp.data(), desc.data(), nf.data(), (int32_t)nk, -1, &idx)); ArrayRef order = ArrayRef::adopt(idx);
-    uint32_t nsv = (uint32_t)ns; dfgpu_array_desc ld{}; ld.type = DFGPU_UINT32; ld.length = 1; ld.values = &nsv; dfgpu_array* la = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &ld, &la)); ArrayRef lit = ArrayRef::adopt(la);
-    dfgpu_array* m = nullptr; tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_LT, order.a, 0, lit.a, 1, &m)); ArrayRef is_split = ArrayRef::adopt(m);
-    ArrayRef pos = mask_indices(tc, is_split);
-    if (pos.len() != ns) fail(DFGPU_INTERNAL, "AggregateExec spill: %lld splitter positions for %lld splitters", (long long)pos.len(), (long long)ns);
-    std::vector<uint32_t> hp((size_t)ns); tc.check(dfgpu_array_export_host(tc.ctx, pos.a, hp.data(), nullptr, nullptr));
-    std::vector<int64_t> bounds; bounds.push_back(0);
-    for (int64_t j = 0; j < ns; j++) bounds.push_back((int64_t)hp[(size_t)j] - j);      // splitters keep their own order (they are sorted and the sort is stable)
-    bounds.push_back(rows);
-    return bounds;
-  }
   void spill(AggState& S, SpillState& P) const {           // spill (row_hash.rs:685-705)
     std::vector<ArrayRef> cols; if (!sorted_state(S, &cols)) return;
-    std::vector<int64_t> bounds = range_bounds(S, P, cols);
-    SpillRun run; run.pieces.resize(bounds.size() - 1);
-    for (size_t r = 0; r + 1 < bounds.size(); r++) {
-      const int64_t lo = bounds[r], len = bounds[r + 1] - bounds[r]; run.pieces[r].rows = len; if (len <= 0) continue;
-      for (auto& c : cols) { dfgpu_array* sl = nullptr; S.tc.check(dfgpu_array_slice(S.tc.ctx, c.a, lo, len, &sl)); ArrayRef piece = ArrayRef::adopt(sl);
-        run.pieces[r].cols.emplace_back(); HostColumn& h = run.pieces[r].cols.back(); S.tc.check(dfgpu_array_export_arrow(S.tc.ctx, piece.a, &h.a, &h.s)); h.live = true; }
-    }
-    P.spilled_rows += cols[0].len(); P.runs.push_back(std::move(run));
+    const std::vector<uint8_t> asc(gexprs.size(), 0), nf(gexprs.size(), 1);
+    P.runs.push_back(spill_ranges(S.tc, cols, range_bounds(S.tc, name(), P.splitters, cols, asc, nf, P.ranges)));
+    P.spilled_rows += cols[0].len();
     cols.clear(); reset_state(S);
   }
   // update_merged_stream + the re-aggregation of the merged stream (row_hash.rs:736-771, :545-600 with is_stream_merging): range by range
   void merge_spills(AggState& S, SpillState& P) const {
-    const TaskContext& tc = S.tc; const size_t nk = gexprs.size();
+    const TaskContext& tc = S.tc; const size_t nk = gexprs.size(); const std::vector<uint8_t> asc(nk, 0), nf(nk, 1);
     std::vector<ArrayRef> rest; std::vector<int64_t> rb;
-    if (dfgpu_groups_len(S.groups.g) > 0 && sorted_state(S, &rest)) rb = range_bounds(S, P, rest);
+    if (dfgpu_groups_len(S.groups.g) > 0 && sorted_state(S, &rest)) rb = range_bounds(tc, name(), P.splitters, rest, asc, nf, P.ranges);
     reset_state(S);
     const size_t R = P.runs[0].pieces.size();
     for (size_t r = 0; r < R; r++) {
-      auto merge_in = [&](const std::vector<ArrayRef>& cols) {
-        std::vector<const dfgpu_array*> kp; for (size_t k = 0; k < nk; k++) kp.push_back(cols[k].a);
-        dfgpu_array* ids = nullptr; tc.check(dfgpu_groups_intern(tc.ctx, S.groups.g, kp.data(), (int32_t)nk, nullptr, &ids)); ArrayRef gids = ArrayRef::adopt(ids);
-        const int64_t total = dfgpu_groups_len(S.groups.g); size_t col = nk;
-        for (size_t i = 0; i < aggs.size(); i++) { const int nst = aggs[i].kind == DFGPU_AGG_AVG ? 2 : 1; const dfgpu_array* st[2]; for (int k = 0; k < nst; k++) st[k] = cols[col + (size_t)k].a; col += (size_t)nst;
-          tc.check(dfgpu_acc_merge_batch(tc.ctx, S.accs[i].a, st, nst, gids.a, nullptr, total)); }
+      auto merge_in = [&](const std::vector<ArrayRef>& cols) {          // keys, then states: what sorted_state() wrote
+        std::vector<const dfgpu_array*> cp; for (auto& c : cols) cp.push_back(c.a);
+        dfgpu_array* ids = nullptr; tc.check(dfgpu_groups_intern(tc.ctx, S.groups.g, cp.data(), (int32_t)nk, nullptr, &ids)); ArrayRef gids = ArrayRef::adopt(ids);
+        merge_states(tc, S.accs, cp.data() + nk, gids, ArrayRef(), dfgpu_groups_len(S.groups.g));
       };
-      for (auto& run : P.runs) { SpillPiece& pc = run.pieces[r]; if (pc.rows <= 0) continue;
-        std::vector<ArrayRef> cols; for (auto& h : pc.cols) { dfgpu_array* a = nullptr; tc.check(dfgpu_array_import_arrow(tc.ctx, &h.a, &h.s, &a)); cols.push_back(ArrayRef::adopt(a)); }
-        merge_in(cols); pc.cols.clear(); }
+      for (auto& run : P.runs) { SpillPiece& pc = run.pieces[r]; if (pc.rows > 0) merge_in(unspill(tc, pc)); }
       if (!rest.empty() && rb[r + 1] > rb[r]) { std::vector<ArrayRef> cols; for (auto& c : rest) { dfgpu_array* sl = nullptr; tc.check(dfgpu_array_slice(tc.ctx, c.a, rb[r], rb[r + 1] - rb[r], &sl)); cols.push_back(ArrayRef::adopt(sl)); } merge_in(cols); }
       Batch o; if (!emit_all(S, mode == 0, &o)) { reset_state(S); continue; }
       std::vector<const dfgpu_array*> kp; for (size_t k = 0; k < nk; k++) kp.push_back(o.cols[k].arr.a);
-      std::vector<uint8_t> desc(nk, 0), nf(nk, 1);
-      dfgpu_array* idx = nullptr; tc.check(dfgpu_sort_to_indices(tc.ctx, kp.data(), desc.data(), nf.data(), (int32_t)nk, -1, &idx)); ArrayRef ix = ArrayRef::adopt(idx);
+      dfgpu_array* idx = nullptr; tc.check(dfgpu_sort_to_indices(tc.ctx, kp.data(), asc.data(), nf.data(), (int32_t)nk, -1, &idx)); ArrayRef ix = ArrayRef::adopt(idx);
       for (auto& c : o.cols) c = col_of(take(tc, c.arr, ix));
       S.ready.push_back(std::move(o)); reset_state(S);
     }
@@ -1887,15 +1919,12 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
     if (n <= 0 || n > total) return;
     Batch o; o.base_rows = n; std::vector<dfgpu_array*> keys(gexprs.size(), nullptr);
     tc.check(dfgpu_groups_emit_first(tc.ctx, S.groups.g, n, keys.data())); for (auto k : keys) o.cols.push_back(col_of(ArrayRef::adopt(k)));
-    dfgpu_array_desc ed{}; ed.type = DFGPU_UINT32; ed.values = &ed; dfgpu_array* e = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &ed, &e)); ArrayRef empty_ids = ArrayRef::adopt(e);
     for (size_t i = 0; i < aggs.size(); i++) {
-      tc.check(dfgpu_acc_update_batch(tc.ctx, S.accs[i].a, nullptr, empty_ids.a, nullptr, total));      // zero-row update: grow the state to `total` groups
+      grow_to(tc, S.accs[i].a, total);
       dfgpu_array* st[2] = {nullptr, nullptr}; int32_t ns = 0; tc.check(dfgpu_acc_emit_first(tc.ctx, S.accs[i].a, n, mode == 0 ? 1 : 0, st, &ns));
       for (int k = 0; k < ns; k++) o.cols.push_back(col_of(ArrayRef::adopt(st[k])));
     }
-    auto sc = std::make_shared<Schema>(); auto names = out_names();
-    for (size_t i = 0; i < o.cols.size(); i++) sc->f.push_back(field_of(names[i], o.cols[i].arr.a));
-    o.schema = sc; { std::lock_guard<std::mutex> l(mu); sch = sc; }
+    stamp_schema(o, mode == 0, true);
     S.ready.push_back(std::move(o)); S.emitted_any = true; S.current_sort = S.current_sort > n ? S.current_sort - n : 0;
   }
   // GroupOrderingPartial::new_groups (aggregates/order/partial.rs:196-240): current_sort = group index of the first row that carries the latest sort-key prefix.
@@ -1909,11 +1938,9 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
     dfgpu_array* si = nullptr; tc.check(dfgpu_groups_intern(tc.ctx, S.sort_groups.g, sk.data(), (int32_t)sk.size(), mask.a, &si)); ArrayRef sids = ArrayRef::adopt(si);
     const int64_t after = dfgpu_groups_len(S.sort_groups.g);
     if (after == before) return;                         // the batch stayed inside the prefix already current
-    uint32_t latest = (uint32_t)(after - 1); dfgpu_array_desc ld{}; ld.type = DFGPU_UINT32; ld.length = 1; ld.values = &latest;
-    dfgpu_array* la = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &ld, &la)); ArrayRef lit = ArrayRef::adopt(la);
+    const uint32_t latest = (uint32_t)(after - 1); ArrayRef lit = host_u32(tc, &latest, 1);
     dfgpu_array* m = nullptr; tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_EQ, sids.a, 0, lit.a, 1, &m)); ArrayRef eq = ArrayRef::adopt(m);
-    if (mask) { dfgpu_array* o = nullptr; tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_AND, eq.a, 0, mask.a, 0, &o)); eq = ArrayRef::adopt(o); }
-    ArrayRef rows = mask_indices(tc, eq);
+    ArrayRef rows = mask_indices(tc, and_masks(tc, eq, mask));      // eq holds no NULLs: ids compared with a literal
     if (rows.len() == 0) fail(DFGPU_INTERNAL, "AggregateExec: no row carries the latest sort prefix");
     dfgpu_array* r0 = nullptr; tc.check(dfgpu_array_slice(tc.ctx, rows.a, 0, 1, &r0)); ArrayRef first_row = ArrayRef::adopt(r0);
     ArrayRef g0 = take(tc, gids, first_row);
@@ -1999,8 +2026,8 @@ struct SortExec : Plan {          // sorts/sort.rs:719-733; sort_batch :584-609
         std::vector<Batch> parts;
         for (auto& run : runs) { SpillPiece& pc = run.pieces[r]; if (pc.rows <= 0) continue;
           Batch b; b.schema = op->schema(); b.base_rows = pc.rows;
-          for (auto& h : pc.cols) { dfgpu_array* a = nullptr; tc.check(dfgpu_array_import_arrow(tc.ctx, &h.a, &h.s, &a)); b.cols.push_back(col_of(ArrayRef::adopt(a))); }
-          pc.cols.clear(); parts.push_back(std::move(b)); }
+          for (auto& a : unspill(tc, pc)) b.cols.push_back(col_of(a));
+          parts.push_back(std::move(b)); }
         Batch all; if (parts.empty() || !concat_batches(tc, parts, &all) || all.base_rows <= 0) continue;
         parts.clear();
         std::vector<ArrayRef> keys; std::vector<const dfgpu_array*> kp;
@@ -2010,30 +2037,6 @@ struct SortExec : Plan {          // sorts/sort.rs:719-733; sort_batch :584-609
       return false;
     }
   };
-  // first row of every range in a batch sorted on `keys` (ranges + 1 entries): splitters and rows are concatenated, splitters first, and ranked by the stable sort -- a splitter
-  // lands in front of the rows equal to it, so (its rank - its own number) rows are strictly before it
-  std::vector<int64_t> range_bounds(const TaskContext& tc, std::vector<ArrayRef>& splitters, const std::vector<ArrayRef>& keys, int64_t K) const {
-    const int64_t rows = keys[0].len(); const size_t nk = keys.size();
-    if (splitters.empty()) {
-      std::vector<uint32_t> at; for (int64_t j = 1; j < K; j++) at.push_back((uint32_t)(rows * j / K));
-      if (at.empty()) at.push_back(0);               // one range: a splitter in front of everything keeps the code below uniform (range 0 is empty, range 1 is the run)
-      dfgpu_array_desc d{}; d.type = DFGPU_UINT32; d.length = (int64_t)at.size(); d.values = at.data(); dfgpu_array* ia = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &d, &ia)); ArrayRef ix = ArrayRef::adopt(ia);
-      for (size_t k = 0; k < nk; k++) splitters.push_back(take(tc, keys[k], ix));
-    }
-    const int64_t ns = splitters[0].len();
-    std::vector<ArrayRef> both; std::vector<const dfgpu_array*> bp;
-    for (size_t k = 0; k < nk; k++) { const dfgpu_array* two[2] = { splitters[k].a, keys[k].a }; dfgpu_array* c = nullptr; tc.check(dfgpu_concat(tc.ctx, two, 2, &c)); both.push_back(ArrayRef::adopt(c)); bp.push_back(both.back().a); }
-    dfgpu_array* idx = nullptr; tc.check(dfgpu_sort_to_indices(tc.ctx, bp.data(), desc.data(), nulls_first.data(), (int32_t)nk, -1, &idx)); ArrayRef order = ArrayRef::adopt(idx);
-    uint32_t nsv = (uint32_t)ns; dfgpu_array_desc ld{}; ld.type = DFGPU_UINT32; ld.length = 1; ld.values = &nsv; dfgpu_array* la = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &ld, &la)); ArrayRef lit = ArrayRef::adopt(la);
-    dfgpu_array* m = nullptr; tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_LT, order.a, 0, lit.a, 1, &m)); ArrayRef is_split = ArrayRef::adopt(m);
-    ArrayRef pos = mask_indices(tc, is_split);
-    if (pos.len() != ns) fail(DFGPU_INTERNAL, "SortExec spill: %lld splitter positions for %lld splitters", (long long)pos.len(), (long long)ns);
-    std::vector<uint32_t> hp((size_t)ns); tc.check(dfgpu_array_export_host(tc.ctx, pos.a, hp.data(), nullptr, nullptr));
-    std::vector<int64_t> bounds; bounds.push_back(0);
-    for (int64_t j = 0; j < ns; j++) bounds.push_back((int64_t)hp[(size_t)j] - j);      // the splitters are sorted among themselves (rows of a sorted run) and the sort is stable
-    bounds.push_back(rows);
-    return bounds;
-  }
   static int64_t batch_bytes(const Batch& b) {
     int64_t t = 0;
     for (auto& c : b.cols) { dfgpu_array_desc d; if (!c.arr.a) continue; dfgpu_array_describe(c.arr.a, &d);
@@ -2051,16 +2054,9 @@ struct SortExec : Plan {          // sorts/sort.rs:719-733; sort_batch :584-609
     std::vector<ArrayRef> cols; for (auto& c : sorted.cols) cols.push_back(col_get(tc, c));
     Batch view; view.schema = sorted.schema; view.base_rows = sorted.base_rows; for (auto& c : cols) view.cols.push_back(col_of(c));
     std::vector<ArrayRef> skeys; for (auto& e : exprs) skeys.push_back(into_array(tc, e->eval(tc, view), view.base_rows));
-    std::vector<int64_t> bounds = range_bounds(tc, splitters, skeys, K);
-    SpillRun run; run.pieces.resize(bounds.size() - 1); int64_t bytes = 0;
-    for (size_t r = 0; r + 1 < bounds.size(); r++) {
-      const int64_t lo = bounds[r], len = bounds[r + 1] - bounds[r]; run.pieces[r].rows = len; if (len <= 0) continue;
-      for (auto& c : cols) { dfgpu_array* sl = nullptr; tc.check(dfgpu_array_slice(tc.ctx, c.a, lo, len, &sl)); ArrayRef piece = ArrayRef::adopt(sl);
-        run.pieces[r].cols.emplace_back(); HostColumn& h = run.pieces[r].cols.back(); tc.check(dfgpu_array_export_arrow(tc.ctx, piece.a, &h.a, &h.s)); h.live = true; }
-    }
-    bytes = batch_bytes(view);
+    runs.push_back(spill_ranges(tc, cols, range_bounds(tc, name(), splitters, skeys, desc, nulls_first, K)));
+    const int64_t bytes = batch_bytes(view);
     { std::lock_guard<std::mutex> l(met->mu); met->spill_count++; met->spilled_rows += view.base_rows; met->spilled_bytes += bytes; }
-    runs.push_back(std::move(run));
   }
   std::unique_ptr<Stream> execute(int partition, const TaskContext& tc) const override {
     int64_t budget = 0, K = 16; dfgpu_ctx_get_option(tc.ctx, "sort_spill_bytes", &budget); dfgpu_ctx_get_option(tc.ctx, "sort_spill_ranges", &K);
@@ -2169,7 +2165,7 @@ struct SortPreservingMergeExec : Plan {
         Batch all; concat_batches(tc, seq, &all); seq.clear();
         ArrayRef ix = order_of(all, -1);
         // where the copy landed = how many rows may leave
-        uint32_t sv = (uint32_t)sentinel; dfgpu_array_desc ld{}; ld.type = DFGPU_UINT32; ld.length = 1; ld.values = &sv; dfgpu_array* la = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &ld, &la)); ArrayRef lit = ArrayRef::adopt(la);
+        const uint32_t sv = (uint32_t)sentinel; ArrayRef lit = host_u32(tc, &sv, 1);
         dfgpu_array* m = nullptr; tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_EQ, ix.a, 0, lit.a, 1, &m)); ArrayRef is_s = ArrayRef::adopt(m);
         ArrayRef where = mask_indices(tc, is_s); if (where.len() != 1) fail(DFGPU_INTERNAL, "SortPreservingMergeExec: the bound row was ranked %lld times", (long long)where.len());
         uint32_t cut = 0; tc.check(dfgpu_array_export_host(tc.ctx, where.a, &cut, nullptr, nullptr));
@@ -2177,7 +2173,7 @@ struct SortPreservingMergeExec : Plan {
         // rows leaving per input: an input's emitted rows are a prefix of it (it is sorted); the prefix length is the number of its rows ranked before the cut
         std::vector<int64_t> gone(act.size(), 0);
         { const dfgpu_array* pk = ix.a; uint8_t no = 0; dfgpu_array* rk = nullptr; tc.check(dfgpu_sort_to_indices(tc.ctx, &pk, &no, &no, 1, -1, &rk)); ArrayRef rank = ArrayRef::adopt(rk);      // argsort of a permutation = its inverse: rank[i] = position of row i
-          uint32_t cv = cut; dfgpu_array_desc cd{}; cd.type = DFGPU_UINT32; cd.length = 1; cd.values = &cv; dfgpu_array* ca = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &cd, &ca)); ArrayRef clit = ArrayRef::adopt(ca);
+          ArrayRef clit = host_u32(tc, &cut, 1);
           dfgpu_array* bm = nullptr; tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_LT, rank.a, 0, clit.a, 1, &bm)); ArrayRef before = ArrayRef::adopt(bm);
           for (size_t k = 0; k < act.size(); k++) { dfgpu_array* sl = nullptr; tc.check(dfgpu_array_slice(tc.ctx, before.a, start[k], parts[k].base_rows, &sl)); ArrayRef part = ArrayRef::adopt(sl); tc.check(dfgpu_mask_count(tc.ctx, part.a, &gone[k])); } }
         Batch o = gather(all, head);

@@ -245,3 +245,66 @@ def test_count_distinct_partial_states_through_repartition_into_final(ctx, parts
     assert out.equals(single)
     ref = t.group_by("k", use_threads=False).aggregate([("v", "count_distinct"), ("v", "sum"), ("d", "count_distinct")]).sort_by([("k", "ascending")])
     assert out["cv"].to_pylist() == ref["v_count_distinct"].to_pylist() and out["cd"].to_pylist() == ref["d_count_distinct"].to_pylist() and out["sv"].to_pylist() == ref["v_sum"].to_pylist()
+
+
+# ------------------------------------------------------------------ FILTER (WHERE f) above a FilterExec
+N_FILTERED = 130                     # the FilterExec's selection bitmap: two full 64-bit words and a ragged tail of two rows
+
+
+def filter_clause_table():
+    """p: the FilterExec keeps p = 1 (no NULLs: a selection without validity); f: the aggregates' FILTER column -- true, false and NULL under both values of p, but in
+    group k = 2 it is true only on rows the FilterExec drops; x: Int64 with NULLs; s: Utf8 with NULLs"""
+    i = np.arange(N_FILTERED)
+    p = (i % 4 != 0).astype(np.int64)
+    k = (i % 3).astype(np.int64)
+    f = [[True, False, None][(j % 5) % 3] for j in i]
+    f = [(True if p[j] == 0 else (False if j % 2 else None)) if k[j] == 2 else f[j] for j in i]
+    x = [None if j % 5 == 0 else int(j) * 3 - 100 for j in i]
+    s = [None if j % 6 == 1 else f"s{j % 11:02d}" for j in i]
+    t = pa.table({"p": pa.array(p), "k": pa.array(k), "f": pa.array(f, type=pa.bool_()), "x": pa.array(x, type=pa.int64()), "s": pa.array(s, type=pa.utf8())})
+    assert any(fv is None and pv == 1 for fv, pv in zip(f, p)) and any(fv is True and pv == 0 for fv, pv in zip(f, p)) and any(fv is False for fv in f)
+    assert any(xv is None and fv is True and pv == 1 for xv, fv, pv in zip(x, f, p))
+    return t
+
+
+def aggregate_over_filter(ctx, t, keys, aggs):
+    """AggregateExec(Single) directly above FilterExec(p = 1), every aggregate with FILTER (WHERE f): the filter's selection reaches the aggregate as a bitmap"""
+    from dfgpu import physical_plan as ops
+    C, F = ops.Column, ops.Field
+    names = t.column_names
+    b = ops.batch_from_arrow(ctx, t)
+    src = ops.FilterExec(ops.BinaryExpr(C("p", names.index("p")), "=", ops.Literal(1, pa.int64())), ops.MemoryExec([[b]], b.schema))
+    ae = [ops.AggregateFunctionExpr(fun, C(col, names.index(col)), f"{fun}({col})", filter=C("f", names.index("f")), input_field=F(col, typ)) for fun, col, typ in aggs]
+    plan = ops.AggregateExec("Single", [(C(key, names.index(key)), key) for key in keys], ae, src)
+    return pa.concat_tables([o.to_arrow() for o in plan.execute(0, ops.TaskContext(ctx, 8192))])
+
+
+@pytest.mark.gpu
+def test_ungrouped_filter_clause_above_filter_exec(ctx):
+    """SUM(x) FILTER (WHERE f), COUNT(x) FILTER (WHERE f) without GROUP BY: a row counts only if the FilterExec keeps it AND f is true -- a NULL f drops the row
+    although the FilterExec keeps it, a true f does not bring back a row the FilterExec dropped"""
+    from dfgpu import capi
+    t = filter_clause_table()
+    out = aggregate_over_filter(ctx, t, [], [("SUM", "x", capi.INT64), ("COUNT", "x", capi.INT64)])
+    counted = [xv for pv, fv, xv in zip(t["p"].to_pylist(), t["f"].to_pylist(), t["x"].to_pylist()) if pv == 1 and fv is True and xv is not None]
+    assert 0 < len(counted) < N_FILTERED
+    assert out.num_rows == 1 and (out.column(0)[0].as_py(), out.column(1)[0].as_py()) == (sum(counted), len(counted))
+
+
+@pytest.mark.gpu
+def test_grouped_special_aggregates_filter_clause_above_filter_exec(ctx):
+    """COUNT(DISTINCT s) FILTER (WHERE f), MIN(s) FILTER (WHERE f) by k over Utf8 s: the same rule for the aggregates that are served outside the kernel accumulators;
+    group 2 keeps rows under the FilterExec but none of them has a true f: it counts 0 distinct values and its MIN is NULL"""
+    from dfgpu import capi
+    t = filter_clause_table()
+    out = aggregate_over_filter(ctx, t, ["k"], [("COUNT DISTINCT", "s", capi.UTF8), ("MIN", "s", capi.UTF8)])
+    want = {}
+    for kv, pv, fv, sv in zip(t["k"].to_pylist(), t["p"].to_pylist(), t["f"].to_pylist(), t["s"].to_pylist()):
+        if pv != 1:
+            continue
+        vals = want.setdefault(kv, set())
+        if fv is True and sv is not None:
+            vals.add(sv)
+    assert sorted(want) == [0, 1, 2] and want[2] == set() and len(want[0]) > 1 and len(want[1]) > 1
+    got = {r["k"]: (r["COUNT DISTINCT(s)"], r["MIN(s)"]) for r in out.to_pylist()}
+    assert got == {kv: (len(v), min(v) if v else None) for kv, v in want.items()}
