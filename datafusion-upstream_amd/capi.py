@@ -14,6 +14,8 @@ LIB_PATH = os.path.join(_HERE, "libdfgpu.so")
 # dfgpu_type
 BOOL, INT8, INT16, INT32, INT64, UINT8, UINT16, UINT32, UINT64 = 1, 2, 3, 4, 5, 6, 7, 8, 9
 FLOAT32, FLOAT64, DATE32, DECIMAL128, UTF8, DICTIONARY = 10, 11, 12, 13, 14, 15
+TIMESTAMP_SECOND, TIMESTAMP_MILLISECOND, TIMESTAMP_MICROSECOND, TIMESTAMP_NANOSECOND = 16, 17, 18, 19      # Int64 counts since the Unix epoch, no time zone
+FN_DATE_TRUNC = 7                                                                                          # DFGPU_FN_DATE_TRUNC
 # ops
 OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_REM = 0, 1, 2, 3, 4
 OP_EQ, OP_NEQ, OP_LT, OP_LTEQ, OP_GT, OP_GTEQ, OP_DISTINCT, OP_NOT_DISTINCT = 10, 11, 12, 13, 14, 15, 16, 17

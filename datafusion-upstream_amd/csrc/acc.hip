@@ -552,7 +552,7 @@ static void check_batch_args(const dfgpu_array* gids, const dfgpu_array* values,
 }
 // stored exactly as the element type the kernels instantiate for the class, no validity, no dictionary (SUM / AVG of a narrower integer widens per row)
 static bool stored_as_state(const dfgpu_array* values, int cls) {
-  return values && !values->validity && values->type == (cls == CLS_F64 ? DFGPU_FLOAT64 : cls == CLS_I128 ? DFGPU_DECIMAL128 : cls == CLS_U64 ? DFGPU_UINT64 : DFGPU_INT64);
+  return values && !values->validity && storage_type(values->type) == (cls == CLS_F64 ? DFGPU_FLOAT64 : cls == CLS_I128 ? DFGPU_DECIMAL128 : cls == CLS_U64 ? DFGPU_UINT64 : DFGPU_INT64);
 }
 // "plain": every row goes from memory into the state unconditionally.  COUNT reads no values: COUNT(*), or a column that cannot be NULL
 static bool plain_batch(int kind, int cls, const dfgpu_array* values, const dfgpu_array* filt) {

@@ -15,6 +15,8 @@ static int32_t parse_format(const char* f, int32_t* p, int32_t* s) {
   if (x == "I") return DFGPU_UINT32; if (x == "l") return DFGPU_INT64; if (x == "L") return DFGPU_UINT64;
   if (x == "f") return DFGPU_FLOAT32; if (x == "g") return DFGPU_FLOAT64; if (x == "tdD") return DFGPU_DATE32;
   if (x == "u") return DFGPU_UTF8;
+  // Timestamp without a time zone only: "tsu:UTC" and the like stay unsupported formats
+  if (x == "tss:") return DFGPU_TIMESTAMP_SECOND; if (x == "tsm:") return DFGPU_TIMESTAMP_MILLISECOND; if (x == "tsu:") return DFGPU_TIMESTAMP_MICROSECOND; if (x == "tsn:") return DFGPU_TIMESTAMP_NANOSECOND;
   if (x.rfind("d:", 0) == 0) {
     int pp = 0, ss = 0, bw = 128;
     int k = sscanf(f, "d:%d,%d,%d", &pp, &ss, &bw);
@@ -27,6 +29,7 @@ static std::string format_of(int32_t t, int32_t p, int32_t s) {
     case DFGPU_BOOL: return "b"; case DFGPU_INT8: return "c"; case DFGPU_UINT8: return "C"; case DFGPU_INT16: return "s"; case DFGPU_UINT16: return "S";
     case DFGPU_INT32: return "i"; case DFGPU_UINT32: return "I"; case DFGPU_INT64: return "l"; case DFGPU_UINT64: return "L";
     case DFGPU_FLOAT32: return "f"; case DFGPU_FLOAT64: return "g"; case DFGPU_DATE32: return "tdD"; case DFGPU_UTF8: return "u";
+    case DFGPU_TIMESTAMP_SECOND: return "tss:"; case DFGPU_TIMESTAMP_MILLISECOND: return "tsm:"; case DFGPU_TIMESTAMP_MICROSECOND: return "tsu:"; case DFGPU_TIMESTAMP_NANOSECOND: return "tsn:";
     case DFGPU_DECIMAL128: return "d:" + std::to_string(p) + "," + std::to_string(s);
     default: return "";
   }

@@ -110,6 +110,10 @@ void check_flags(dfgpu_ctx* ctx, const char* what) {
   if (f & DFGPU_FLAG_CAST) fail(DFGPU_EXECUTION, "Arrow error: Cast error: value out of range (%s)", what);
   if (f & DFGPU_FLAG_OOB) fail(DFGPU_EXECUTION, "Arrow error: index out of bounds (%s)", what);
   if (f & DFGPU_FLAG_SUBSTR_LENGTH) fail(DFGPU_EXECUTION, "negative substring length not allowed: substr(<str>, <start>, <count>) with a count below zero (%s)", what);
+  if (f & DFGPU_FLAG_TS_RANGE) {          // the reference names the instant: "Timestamp {value} out of range"
+    const long long v = (long long)read_scratch(ctx, TS_BAD_SLOT);
+    fail(DFGPU_EXECUTION, "Timestamp %lld out of range: date_trunc of an instant that, or whose truncation, does not fit an Int64 of nanoseconds (%s)", v, what);
+  }
   if (f & DFGPU_FLAG_STALLED) fail(DFGPU_INTERNAL, "a workgroup gave up waiting for the tile counts of the workgroups in front of it; the result of that sort is not valid (%s; option sort_onesweep_rows=0 selects the three-launch passes)", what);
   fail(DFGPU_INTERNAL, "kernel raised flag %u (%s)", f, what);
 }
@@ -176,7 +180,7 @@ ColView make_view(const dfgpu_array* a) {
     d = a->dictionary;
     v.keys = a->values->ptr; v.key_validity = a->validity ? (const uint64_t*)a->validity->ptr : nullptr; v.key_type = a->key_type;
   }
-  v.type = d->type; v.width = type_width(d->type);
+  v.type = storage_type(d->type); v.width = type_width(d->type);      // kernels see Date32 as Int32 and a Timestamp as Int64: same bytes, order and hash
   v.values = d->values ? d->values->ptr : nullptr;
   v.validity = d->validity ? (const uint64_t*)d->validity->ptr : nullptr;
   v.offsets = d->offsets ? (const int32_t*)d->offsets->ptr : nullptr;
@@ -275,7 +279,7 @@ int64_t count_set_bits(dfgpu_ctx* ctx, const uint64_t* bits, int64_t n) {
   return (int64_t)read_scratch(ctx, 62);
 }
 
-static void validate_type(int32_t t) { if (t < DFGPU_BOOL || t > DFGPU_DICTIONARY) fail(DFGPU_INVALID_ARGUMENT, "unknown type id %d", t); }
+static void validate_type(int32_t t) { if (t < DFGPU_BOOL || t > DFGPU_TIMESTAMP_NANOSECOND) fail(DFGPU_INVALID_ARGUMENT, "unknown type id %d", t); }
 
 static dfgpu_array* import_desc(dfgpu_ctx* ctx, const dfgpu_array_desc* d, bool copy, const std::shared_ptr<void>& owner = nullptr) {
   validate_type(d->type);

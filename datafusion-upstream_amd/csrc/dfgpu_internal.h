@@ -31,9 +31,9 @@ struct Error : std::exception {
 }  // namespace dfgpu
 
 // Device error flags raised by kernels (checked by the op that launched them).
-enum : uint32_t { DFGPU_FLAG_DIV_ZERO = 1, DFGPU_FLAG_OVERFLOW = 2, DFGPU_FLAG_CAST = 4, DFGPU_FLAG_OOB = 8, DFGPU_FLAG_TABLE_FULL = 16, DFGPU_FLAG_STALLED = 32, DFGPU_FLAG_SUBSTR_LENGTH = 64 };      // STALLED: a workgroup gave up waiting for a word another workgroup publishes (one-sweep sort passes)
+enum : uint32_t { DFGPU_FLAG_DIV_ZERO = 1, DFGPU_FLAG_OVERFLOW = 2, DFGPU_FLAG_CAST = 4, DFGPU_FLAG_OOB = 8, DFGPU_FLAG_TABLE_FULL = 16, DFGPU_FLAG_STALLED = 32, DFGPU_FLAG_SUBSTR_LENGTH = 64, DFGPU_FLAG_TS_RANGE = 128 };      // STALLED: a workgroup gave up waiting for a word another workgroup publishes (one-sweep sort passes)
 
-namespace dfgpu { struct Buffer; }
+namespace dfgpu { struct Buffer; constexpr int TS_BAD_SLOT = 50; }      // slot of ctx->d_scratch64 where k_ts_trunc leaves an instant that raised DFGPU_FLAG_TS_RANGE
 // scalar_fn.hip: a Utf8 column whose rows average at least this many bytes gives every row a wave (16 B per lane, 1 KiB per step) instead of a lane (8 B per step);
 // both kernels are exact at every length.  Measured (profiles/scalar_fn_microbench.json, `crossing`: character_length over 256 MB of equal-length rows, ms lane / wave):
 // 64 B 0.10 / 1.00, 96 B 0.22 / 0.64, 128 B 0.54 / 0.48, 256 B 0.44 / 0.24, 1024 B 0.22 / 0.07; left(s, -1) crosses at 128 B too (1.54 / 1.51).
@@ -170,10 +170,15 @@ inline int type_width(int32_t t) {
     case DFGPU_INT16: case DFGPU_UINT16: return 2;
     case DFGPU_INT32: case DFGPU_UINT32: case DFGPU_FLOAT32: case DFGPU_DATE32: return 4;
     case DFGPU_INT64: case DFGPU_UINT64: case DFGPU_FLOAT64: return 8;
+    case DFGPU_TIMESTAMP_SECOND: case DFGPU_TIMESTAMP_MILLISECOND: case DFGPU_TIMESTAMP_MICROSECOND: case DFGPU_TIMESTAMP_NANOSECOND: return 8;
     case DFGPU_DECIMAL128: return 16;
     default: return 0;
   }
 }
+inline bool is_timestamp(int32_t t) { return t >= DFGPU_TIMESTAMP_SECOND && t <= DFGPU_TIMESTAMP_NANOSECOND; }
+// the type whose bytes, order and hash a logical type shares: the dispatch points that move, compare, hash or order values switch on this (Date32 is an Int32
+// day count, a Timestamp of any unit an Int64 count since the epoch; create_hashes hashes them as such); output columns keep the logical type
+inline int32_t storage_type(int32_t t) { return t == DFGPU_DATE32 ? DFGPU_INT32 : is_timestamp(t) ? DFGPU_INT64 : t; }
 inline bool is_signed_int(int32_t t) { return t == DFGPU_INT8 || t == DFGPU_INT16 || t == DFGPU_INT32 || t == DFGPU_INT64; }
 inline bool is_unsigned_int(int32_t t) { return t == DFGPU_UINT8 || t == DFGPU_UINT16 || t == DFGPU_UINT32 || t == DFGPU_UINT64; }
 inline bool is_float(int32_t t) { return t == DFGPU_FLOAT32 || t == DFGPU_FLOAT64; }

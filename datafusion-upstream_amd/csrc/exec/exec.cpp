@@ -409,9 +409,11 @@ struct ScalarFunctionExpr : Expr { // scalar_function.rs:ScalarFunctionExpr::eva
     dfgpu_array* o = nullptr; tc.check(dfgpu_scalar_function(tc.ctx, fn, a.data(), sc.data(), (int32_t)a.size(), &o));
     return Value{ArrayRef::adopt(o), all_scalar};
   }
-  // only a three-argument SUBSTR raises per row (a negative count), and not when its count is a NULL or non-negative literal
+  // a three-argument SUBSTR raises per row (a negative count) unless its count is a NULL or non-negative literal; DATE_TRUNC raises for a row outside the
+  // nanosecond window
   bool safe() const override {
     for (auto& e : args) if (!e->safe()) return false;
+    if (fn == DFGPU_FN_DATE_TRUNC) return false;
     return fn != DFGPU_FN_SUBSTR || args.size() != 3 || count_cannot_raise.load() == 1;
   }
   void columns(std::set<int>& out) const override { for (auto& e : args) e->columns(out); }
@@ -599,7 +601,8 @@ struct FilterExec : Plan {        // filter.rs:56-66, batch_filter :315-327
     if (!lit || ci < 0 || ci >= (int)b.cols.size() || !b.cols[(size_t)ci].arr) return false;
     int64_t v = 1; if (dfgpu_ctx_get_option(tc.ctx, "join_probe_fused_filter", &v) == DFGPU_OK && v == 0) return false;
     dfgpu_array_desc cd, sd; dfgpu_array_describe(b.cols[(size_t)ci].arr.a, &cd); dfgpu_array_describe(lit->scalar.a, &sd);
-    if ((cd.type != DFGPU_INT32 && cd.type != DFGPU_DATE32 && cd.type != DFGPU_INT64) || cd.validity || cd.length != b.base_rows || sd.type != cd.type || sd.length != 1 || sd.validity || sd.null_count != 0) return false;
+    const bool timestamp = cd.type >= DFGPU_TIMESTAMP_SECOND && cd.type <= DFGPU_TIMESTAMP_NANOSECOND;
+    if ((cd.type != DFGPU_INT32 && cd.type != DFGPU_DATE32 && cd.type != DFGPU_INT64 && !timestamp) || cd.validity || cd.length != b.base_rows || sd.type != cd.type || sd.length != 1 || sd.validity || sd.null_count != 0) return false;
     static const int swapped[6] = { DFGPU_OP_EQ, DFGPU_OP_NEQ, DFGPU_OP_GT, DFGPU_OP_GTEQ, DFGPU_OP_LT, DFGPU_OP_LTEQ };      // literal <op> column == column <swapped op> literal
     *column = b.cols[(size_t)ci].arr; *scalar = lit->scalar; *op = col_left ? be->op : swapped[be->op - DFGPU_OP_EQ];
     return true;
@@ -931,7 +934,7 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
           const Col& bc = build->cols[(size_t)bi]; const Col& pc = probe_b.cols[(size_t)pi];
           const dfgpu_array* ba = bc.arr ? bc.arr.a : bc.source.a; const dfgpu_array* pa = pc.arr ? pc.arr.a : pc.source.a; if (!ba || !pa) continue;
           dfgpu_array_desc bd, pd; dfgpu_array_describe(ba, &bd); dfgpu_array_describe(pa, &pd);
-          const bool exact = (bd.type >= DFGPU_INT8 && bd.type <= DFGPU_UINT64) || bd.type == DFGPU_DATE32 || bd.type == DFGPU_DECIMAL128;
+          const bool exact = (bd.type >= DFGPU_INT8 && bd.type <= DFGPU_UINT64) || bd.type == DFGPU_DATE32 || bd.type == DFGPU_DECIMAL128 || (bd.type >= DFGPU_TIMESTAMP_SECOND && bd.type <= DFGPU_TIMESTAMP_NANOSECOND);
           if (exact && bd.type == pd.type && bd.precision == pd.precision && bd.scale == pd.scale) alias[(size_t)bi] = pi;
         }
       return alias;
@@ -2301,8 +2304,8 @@ dfgpu_status dfgpu_expr_scalar_function(int32_t fn, const dfgpu_expr* const* arg
   return guard([&] {
     if (!out || !args) fail(DFGPU_INVALID_ARGUMENT, "expr_scalar_function: null argument");
     // the table of dfgpu_scalar_function: what no evaluation could take is refused when the plan is built
-    static const int32_t lo[7] = {0, 2, 1, 2, 2, 2, 2}, hi[7] = {0, 2, 1, 3, 2, 2, 2};
-    if (fn < DFGPU_FN_DATE_PART || fn > DFGPU_FN_STARTS_WITH) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: scalar function %d on the device", fn);
+    static const int32_t lo[8] = {0, 2, 1, 2, 2, 2, 2, 2}, hi[8] = {0, 2, 1, 3, 2, 2, 2, 2};
+    if (fn < DFGPU_FN_DATE_PART || fn > DFGPU_FN_DATE_TRUNC) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: scalar function %d on the device", fn);
     if (nargs < lo[fn] || nargs > hi[fn]) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: scalar function %d with %d arguments on the device", fn, nargs);
     auto f = std::make_shared<ScalarFunctionExpr>();
     f->fn = fn; for (int32_t k = 0; k < nargs; k++) f->args.push_back(ex(args[k]));

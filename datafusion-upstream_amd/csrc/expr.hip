@@ -335,6 +335,20 @@ __global__ void __launch_bounds__(BLOCK) k_cast(ColView c, int64_t n, int32_t to
   if (to == DFGPU_BOOL) { uint64_t m = ballot64(bit); if (lane_id() == 0 && (i >> 6) < ((n + 63) >> 6)) ((uint64_t*)out)[i >> 6] = m; }
 }
 
+// Casts that involve a Timestamp (arrow-cast 50, safe = false): out = in * mul (checked: DFGPU_FLAG_OVERFLOW on a valid, selected row) or in / div (the crate's
+// `/`: toward zero).  The source is Int64, Date32 or a Timestamp (plain or behind dictionary codes); `to` Date32 narrows the quotient with `as i32`.
+__global__ void __launch_bounds__(BLOCK) k_ts_cast(ColView c, int64_t n, int64_t mul, int64_t div, int32_t to, void* out, uint32_t* flags, const uint64_t* emask) {
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  int64_t r, v = 0;
+  if (cell_resolve(c, i, &r)) {
+    v = (int64_t)cell_int(c, r);
+    if (mul != 1) { int64_t w; if (__builtin_mul_overflow(v, mul, &w)) { if (emask == nullptr || bit_get(emask, i)) atomicOr(flags, DFGPU_FLAG_OVERFLOW); w = 0; } v = w; }
+    else if (div != 1) v = v / div;
+  }
+  if (to == DFGPU_DATE32) ((int32_t*)out)[i] = (int32_t)(uint32_t)(uint64_t)v; else ((int64_t*)out)[i] = v;
+}
+
 __global__ void __launch_bounds__(BLOCK) k_in_list(ColView c, ColView list, int64_t list_len, int64_t n, int negated, uint64_t* out_bits, uint64_t* out_valid) {
   int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   bool v = false, ok = false;
@@ -578,6 +592,7 @@ dfgpu_status dfgpu_binary(dfgpu_ctx* ctx, int32_t op, const dfgpu_array* l, int3
     int64_t n = ls ? (rs ? 1 : r->length) : l->length;
     if (!ls && !rs && l->length != r->length) fail(DFGPU_INVALID_ARGUMENT, "binary: operand lengths differ (%lld vs %lld)", (long long)l->length, (long long)r->length);
     int32_t lt = logical_type(l), rt = logical_type(r);
+    if (lt != rt && is_timestamp(lt) && is_timestamp(rt)) fail(DFGPU_NOT_IMPLEMENTED, "binary: Timestamp operands of two units (%d vs %d); the planner coerces first", lt, rt);
     if (lt != rt) fail(DFGPU_INVALID_ARGUMENT, "binary: operand types differ (%d vs %d); the planner coerces first", lt, rt);
     Operand lo = make_operand(l, ls), ro = make_operand(r, rs);
     bool nulls = may_have_nulls(l) || may_have_nulls(r);
@@ -612,9 +627,9 @@ dfgpu_status dfgpu_binary(dfgpu_ctx* ctx, int32_t op, const dfgpu_array* l, int3
         const dfgpu_array* col = rs && !ls ? l : (ls && !rs ? r : nullptr); const dfgpu_array* sc = col == l ? r : l;
         int fop = col == l ? op : swap_cmp(op);
         if (col && n && !nulls && op <= DFGPU_OP_GTEQ && col->type != DFGPU_DICTIONARY && sc->type != DFGPU_DICTIONARY && sc->has_host_scalar && sc->host_scalar_valid &&
-            (lt == DFGPU_INT32 || lt == DFGPU_DATE32 || lt == DFGPU_INT64)) {
+            (storage_type(lt) == DFGPU_INT32 || storage_type(lt) == DFGPU_INT64)) {
           KernelTimer kt_(ctx, "k_compare_scalar_fast");
-          if (lt == DFGPU_INT64) { int64_t sv; memcpy(&sv, sc->host_scalar, 8); launch_compare_scalar_fast<int64_t>(ctx, fop, (const int64_t*)col->values->ptr, sv, n, (uint64_t*)h.get()->values->ptr); }
+          if (storage_type(lt) == DFGPU_INT64) { int64_t sv; memcpy(&sv, sc->host_scalar, 8); launch_compare_scalar_fast<int64_t>(ctx, fop, (const int64_t*)col->values->ptr, sv, n, (uint64_t*)h.get()->values->ptr); }
           else { int32_t sv; memcpy(&sv, sc->host_scalar, 4); launch_compare_scalar_fast<int32_t>(ctx, fop, (const int32_t*)col->values->ptr, sv, n, (uint64_t*)h.get()->values->ptr); }
           KERNEL_CHECK();
           *out = h.release(); return;
@@ -740,6 +755,32 @@ dfgpu_status dfgpu_cast(dfgpu_ctx* ctx, const dfgpu_array* a, int32_t to, int32_
     if (!a || !out) fail(DFGPU_INVALID_ARGUMENT, "cast: null argument");
     int32_t from = logical_type(a);
     if (from == to && from != DFGPU_DECIMAL128 && a->type != DFGPU_DICTIONARY) { dfgpu_array_retain(const_cast<dfgpu_array*>(a)); *out = const_cast<dfgpu_array*>(a); return; }
+    if (is_timestamp(from) || is_timestamp(to)) {
+      // Int64 <-> Timestamp: the values unchanged; Timestamp -> finer Timestamp and Date32 -> Timestamp: a checked multiply; Timestamp -> coarser Timestamp and
+      // Timestamp -> Date32: the crate's `/`, toward zero.  Everything else (Utf8, other integer widths, floats, decimals) is the planner's to route through Int64
+      static const int64_t per_sec[4] = {1ll, 1000ll, 1000000ll, 1000000000ll};
+      const int64_t uf = is_timestamp(from) ? per_sec[from - DFGPU_TIMESTAMP_SECOND] : 0, ut = is_timestamp(to) ? per_sec[to - DFGPU_TIMESTAMP_SECOND] : 0;
+      int64_t mul = 1, div = 1;
+      if (uf && ut) { if (ut > uf) mul = ut / uf; else div = uf / ut; }
+      else if (from == DFGPU_DATE32 && ut) mul = 86400ll * ut;
+      else if (uf && to == DFGPU_DATE32) div = 86400ll * uf;
+      else if (!((from == DFGPU_INT64 && ut) || (uf && to == DFGPU_INT64))) fail(DFGPU_NOT_IMPLEMENTED, "cast %d -> %d", from, to);
+      if (mul == 1 && div == 1 && a->type != DFGPU_DICTIONARY) {          // the same bytes under another logical type: share the buffers
+        ArrayHolder h(new_array(ctx, to, a->length));
+        h.get()->values = a->values; h.get()->validity = a->validity; h.get()->null_count = a->validity ? a->null_count : 0;
+        if (a->has_host_scalar) { h.get()->has_host_scalar = true; h.get()->host_scalar_valid = a->host_scalar_valid; memcpy(h.get()->host_scalar, a->host_scalar, sizeof a->host_scalar); }
+        *out = h.release(); return;
+      }
+      ColView v = make_view(a);
+      ArrayHolder h(new_fixed(ctx, to, a->length));
+      { KernelTimer kt_(ctx, "k_ts_cast");
+        if (a->length) hipLaunchKernelGGL(k_ts_cast, dim3(grid_for(a->length, BLOCK)), dim3(BLOCK), 0, ctx->stream, v, a->length, mul, div, to, h.get()->values->ptr, ctx->d_flags, row_selection_words(ctx, a->length));
+        KERNEL_CHECK(); }
+      if (a->type != DFGPU_DICTIONARY) { h.get()->validity = a->validity; h.get()->null_count = a->null_count; }
+      else if (may_have_nulls(a)) { h.get()->validity = alloc_buffer(ctx, bitmap_bytes(a->length), true); hipLaunchKernelGGL(k_is_null, dim3(grid_for(a->length, BLOCK)), dim3(BLOCK), 0, ctx->stream, v, a->length, 1, (uint64_t*)h.get()->validity->ptr); h.get()->null_count = -1; }
+      if (mul != 1) check_flags(ctx, "cast");
+      *out = h.release(); return;
+    }
     bool okf = from == DFGPU_BOOL || from == DFGPU_DATE32 || (from >= DFGPU_INT8 && from <= DFGPU_FLOAT64) || from == DFGPU_DECIMAL128;
     bool okt = to == DFGPU_BOOL || to == DFGPU_DATE32 || (to >= DFGPU_INT8 && to <= DFGPU_FLOAT64) || to == DFGPU_DECIMAL128;
     if (!okf || !okt || (to == DFGPU_BOOL && !(from == DFGPU_BOOL || (from >= DFGPU_INT8 && from <= DFGPU_UINT64)))) fail(DFGPU_NOT_IMPLEMENTED, "cast %d -> %d", from, to);

@@ -567,7 +567,7 @@ static void groups_hash_stored(dfgpu_ctx* ctx, dfgpu_groups* g) {
 }
 static bool run_key_type(const dfgpu_array* a) {
   if (a->type == DFGPU_DICTIONARY || a->validity) return false;
-  switch (a->type) { case DFGPU_INT8: case DFGPU_INT16: case DFGPU_INT32: case DFGPU_INT64: case DFGPU_DATE32: case DFGPU_UINT8: case DFGPU_UINT16: case DFGPU_UINT32: case DFGPU_UINT64: return true; default: return false; }
+  switch (storage_type(a->type)) { case DFGPU_INT8: case DFGPU_INT16: case DFGPU_INT32: case DFGPU_INT64: case DFGPU_UINT8: case DFGPU_UINT16: case DFGPU_UINT32: case DFGPU_UINT64: return true; default: return false; }
 }
 // RUNS: clustered keys (the shape of GROUP BY over a fact table stored in key order) -> ids by run number, no hash table.  Declines
 // (nothing changed) when the batch does not qualify or is not clustered.
@@ -583,8 +583,8 @@ static bool groups_intern_runs(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_arra
   dim3 grid(grid_for(n, BLOCK)), block(BLOCK);
 #define RUNS(T) do { if (nkeys == 1) hipLaunchKernelGGL((k_run_heads1<T>), dim3(grid_for(n, BLOCK * 4)), block, 0, ctx->stream, (const T*)k0->values->ptr, n, (const T*)prev, (uint64_t*)heads->ptr, (unsigned long long*)(ctx->d_scratch64 + 2)); \
                      else hipLaunchKernelGGL((k_run_heads<T>), grid, block, 0, ctx->stream, bk, n, (const T*)prev, (uint64_t*)heads->ptr, (unsigned long long*)(ctx->d_scratch64 + 2)); } while (0)
-  switch (k0->type) {
-    case DFGPU_INT8: RUNS(int8_t); break; case DFGPU_INT16: RUNS(int16_t); break; case DFGPU_INT32: case DFGPU_DATE32: RUNS(int32_t); break; case DFGPU_INT64: RUNS(int64_t); break;
+  switch (storage_type(k0->type)) {
+    case DFGPU_INT8: RUNS(int8_t); break; case DFGPU_INT16: RUNS(int16_t); break; case DFGPU_INT32: RUNS(int32_t); break; case DFGPU_INT64: RUNS(int64_t); break;
     case DFGPU_UINT8: RUNS(uint8_t); break; case DFGPU_UINT16: RUNS(uint16_t); break; case DFGPU_UINT32: RUNS(uint32_t); break; default: RUNS(uint64_t); break; }
 #undef RUNS
   KERNEL_CHECK();
@@ -608,7 +608,7 @@ static bool groups_intern_runs(dfgpu_ctx* ctx, dfgpu_groups* g, const dfgpu_arra
   g->n_groups += n_new; g->rep = GroupRep::RUNS;
   return true;
 }
-static bool prim_key_type(const dfgpu_array* a) { return a && (a->type == DFGPU_INT64 || a->type == DFGPU_UINT64 || a->type == DFGPU_INT32 || a->type == DFGPU_UINT32 || a->type == DFGPU_DATE32) && !a->validity; }
+static bool prim_key_type(const dfgpu_array* a) { if (!a || a->validity) return false; const int32_t t = storage_type(a->type); return t == DFGPU_INT64 || t == DFGPU_UINT64 || t == DFGPU_INT32 || t == DFGPU_UINT32; }
 // a primitive table of cap slots holding the numbered groups
 static void prim_rebuild(dfgpu_ctx* ctx, dfgpu_groups* g, uint64_t cap, bool key4) {
   g->pslots = alloc_buffer(ctx, (size_t)cap * sizeof(PSlot)); g->pcap = cap; HIP_CHECK(hipMemsetAsync(g->pslots->ptr, 0xFF, (size_t)cap * sizeof(PSlot), ctx->stream));

@@ -445,12 +445,12 @@ __global__ void __launch_bounds__(BLOCK) k_probe_lookup_rank(const T* pkeys, con
   for (int q = 0; q < LR_ROWS; q++) { int64_t i = base + (int64_t)q * BLOCK; if (i < m) out_build[i] = r[q]; }
 }
 #define DFGPU_INT_KEY_DISPATCH(TYPE, CALL)                                                                      \
-  switch (TYPE) {                                                                                               \
+  switch (storage_type(TYPE)) {            /* Date32 as Int32, a Timestamp as Int64 */                          \
     case DFGPU_INT8: { using T = int8_t; CALL; break; } case DFGPU_INT16: { using T = int16_t; CALL; break; }   \
-    case DFGPU_INT32: case DFGPU_DATE32: { using T = int32_t; CALL; break; } case DFGPU_INT64: { using T = int64_t; CALL; break; } \
+    case DFGPU_INT32: { using T = int32_t; CALL; break; } case DFGPU_INT64: { using T = int64_t; CALL; break; } \
     case DFGPU_UINT8: { using T = uint8_t; CALL; break; } case DFGPU_UINT16: { using T = uint16_t; CALL; break; } \
     case DFGPU_UINT32: { using T = uint32_t; CALL; break; } default: break; }
-static bool int_key_type(int32_t t) { return t == DFGPU_INT8 || t == DFGPU_INT16 || t == DFGPU_INT32 || t == DFGPU_INT64 || t == DFGPU_DATE32 || t == DFGPU_UINT8 || t == DFGPU_UINT16 || t == DFGPU_UINT32; }
+static bool int_key_type(int32_t t) { t = storage_type(t); return t == DFGPU_INT8 || t == DFGPU_INT16 || t == DFGPU_INT32 || t == DFGPU_INT64 || t == DFGPU_UINT8 || t == DFGPU_UINT16 || t == DFGPU_UINT32; }
 
 __global__ void k_mark_bits_u64idx(const uint64_t* idx, const uint64_t* idx_valid, int64_t n, uint64_t* bits, int64_t nbits, uint32_t* flags) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -521,7 +521,7 @@ __global__ void __launch_bounds__(BLOCK) k_pack_keys(PackCols pc, int64_t n, int
 }
 static PackCols pack_cols(const dfgpu_join_table* t, const dfgpu_array* const* cols) {
   PackCols pc{}; pc.n = t->pack_n;
-  for (int c = 0; c < t->pack_n; c++) { pc.v[c] = cols[c]->values->ptr; pc.valid[c] = cols[c]->validity ? (const uint64_t*)cols[c]->validity->ptr : nullptr; pc.type[c] = cols[c]->type;
+  for (int c = 0; c < t->pack_n; c++) { pc.v[c] = cols[c]->values->ptr; pc.valid[c] = cols[c]->validity ? (const uint64_t*)cols[c]->validity->ptr : nullptr; pc.type[c] = storage_type(cols[c]->type);
                                         pc.mn[c] = t->pack_min[c]; pc.range[c] = t->pack_range[c]; pc.stride[c] = t->pack_stride[c]; }
   return pc;
 }
@@ -817,7 +817,7 @@ static void lookup_rank(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_a
 struct ProbePred { const dfgpu_array* col = nullptr; int op = 0; int64_t scalar = 0; };
 // what the fused probe kernel is instantiated for: Int32 / Date32 / Int64 keys without validity, an Int32 / Date32 / Int64 predicate column without validity, the six comparisons
 static bool probe_pred_ok(const dfgpu_join_table* t, const dfgpu_array* pk, const ProbePred& pp) {
-  auto w48 = [](int32_t ty) { return ty == DFGPU_INT32 || ty == DFGPU_DATE32 || ty == DFGPU_INT64; };
+  auto w48 = [](int32_t ty) { ty = storage_type(ty); return ty == DFGPU_INT32 || ty == DFGPU_INT64; };
   return pp.col && pp.op >= DFGPU_OP_EQ && pp.op <= DFGPU_OP_GTEQ && w48(pp.col->type) && !pp.col->validity && pp.col->length == pk->length && w48(pk->type) && !pk->validity &&
          pk->type == t->keys[0]->type && (t->bitmap || (t->lazy_row_slot && t->range <= (uint64_t)pk->length * 16));
 }
@@ -858,7 +858,7 @@ static bool match_bits_by_bitmap(dfgpu_ctx* ctx, const dfgpu_join_table* t, cons
   const uint64_t* bm = (const uint64_t*)t->bitmap->ptr;
   if (pp.op) {
     const void* pptr = pair_aligned(ctx, pp.col, n, aligned_pred);
-    const bool k8 = pk->type == DFGPU_INT64, p8 = pp.col->type == DFGPU_INT64;
+    const bool k8 = storage_type(pk->type) == DFGPU_INT64, p8 = storage_type(pp.col->type) == DFGPU_INT64;
     if (k8 && p8) launch_probe_fused<int64_t, int64_t>(ctx, pp.op, grid, (const int64_t*)kptr, mk, (const int64_t*)pptr, pp.scalar, n, t->key_min, t->range, bm, match_bits);
     else if (k8) launch_probe_fused<int64_t, int32_t>(ctx, pp.op, grid, (const int64_t*)kptr, mk, (const int32_t*)pptr, (int32_t)pp.scalar, n, t->key_min, t->range, bm, match_bits);
     else if (p8) launch_probe_fused<int32_t, int64_t>(ctx, pp.op, grid, (const int32_t*)kptr, mk, (const int64_t*)pptr, pp.scalar, n, t->key_min, t->range, bm, match_bits);
@@ -876,7 +876,7 @@ static bool match_bits_by_bitmap(dfgpu_ctx* ctx, const dfgpu_join_table* t, cons
 static BufferPtr match_bits_by_hash(dfgpu_ctx* ctx, const dfgpu_join_table* t, const dfgpu_array* const* probe_keys, int32_t nkeys, const KeySet& pks, int64_t n, const uint64_t* mk, uint64_t* match_bits) {
   if (!t->slots) build_hash_table(ctx, t, false);
   KernelTimer kt_(ctx, "k_probe_match_hash");
-  auto plain8 = [](const dfgpu_array* a) { return (a->type == DFGPU_INT64 || a->type == DFGPU_UINT64) && !a->validity; };
+  auto plain8 = [](const dfgpu_array* a) { return (storage_type(a->type) == DFGPU_INT64 || a->type == DFGPU_UINT64) && !a->validity; };
   bool fast_hash = (nkeys == 1 || nkeys == 2) && !t->null_equals_null && !ctx->force_hash_collisions && t->n_build > 0;
   for (int c = 0; c < nkeys && fast_hash; c++) fast_hash = plain8(probe_keys[c]) && plain8(t->keys[(size_t)c]);
   BufferPtr found_slot;
@@ -1003,8 +1003,8 @@ dfgpu_status dfgpu_join_probe_fused(dfgpu_ctx* ctx, const dfgpu_join_table* t, c
   dfgpu::ProbePred pp; pp.col = pred_column; pp.op = pred_op;
   // the scalar as the compare fast path reads it (expr.hip): a host-resident non-NULL value of the column's type; anything else is not a predicate the kernel takes
   const int32_t pt = pred_column->type;
-  const bool scalar_ok = pred_scalar->type == pt && pred_scalar->length == 1 && pred_scalar->has_host_scalar && pred_scalar->host_scalar_valid && (pt == DFGPU_INT32 || pt == DFGPU_DATE32 || pt == DFGPU_INT64);
-  if (scalar_ok) { if (pt == DFGPU_INT64) memcpy(&pp.scalar, pred_scalar->host_scalar, 8); else { int32_t v; memcpy(&v, pred_scalar->host_scalar, 4); pp.scalar = v; } }
+  const bool scalar_ok = pred_scalar->type == pt && pred_scalar->length == 1 && pred_scalar->has_host_scalar && pred_scalar->host_scalar_valid && (storage_type(pt) == DFGPU_INT32 || storage_type(pt) == DFGPU_INT64);
+  if (scalar_ok) { if (storage_type(pt) == DFGPU_INT64) memcpy(&pp.scalar, pred_scalar->host_scalar, 8); else { int32_t v; memcpy(&v, pred_scalar->host_scalar, 4); pp.scalar = v; } }
   else pp.op = 0;                                   // declined below, after the ordinary argument checks
   return join_probe_impl(ctx, t, probe_keys, nkeys, opt_mask, sel ? nullptr : out_build_idx, sel ? nullptr : out_probe_idx, out_form == DFGPU_PROBE_DEFERRED, sel ? out_selection : nullptr, &pp);
 }

@@ -433,9 +433,9 @@ extern "C" dfgpu_status dfgpu_agg_preaggregate_flags(dfgpu_ctx* ctx, const dfgpu
     // Several key columns, or one with NULLs, travel as ONE packed u64 (value ranges multiplied out, NULL = digit 0 of its column): the partial rows' keys are unpacked again
     const bool packed_keys = nkeys > 1 || (!is_dict && key->validity);
     auto plain_int = [](int32_t t) { switch (t) { case DFGPU_INT8: case DFGPU_INT16: case DFGPU_INT32: case DFGPU_INT64: case DFGPU_DATE32: case DFGPU_UINT8: case DFGPU_UINT16: case DFGPU_UINT32: case DFGPU_UINT64: return true; default: return false; } };
-    if (packed_keys) { for (int c = 0; c < nkeys; c++) if (!keys[c] || !plain_int(keys[c]->type) || keys[c]->length != n) skip("integer / Date32 key columns (not dictionary-encoded) when there are several or one carries NULLs"); }
+    if (packed_keys) { for (int c = 0; c < nkeys; c++) if (!keys[c] || !plain_int(storage_type(keys[c]->type)) || keys[c]->length != n) skip("integer / Date32 key columns (not dictionary-encoded) when there are several or one carries NULLs"); }
     int32_t ktype = is_dict ? key->key_type : key->type;
-    if (!packed_keys && (!pa_key_type_ok(ktype) || key->validity)) skip("a 4- or 8-byte integer key column (or dictionary codes of that width)");
+    if (!packed_keys && (!pa_key_type_ok(storage_type(ktype)) || key->validity)) skip("a 4- or 8-byte integer key column (or dictionary codes of that width)");
     if (n < ctx->agg_partitioned_min_rows || n > 0xFFFF0000ll) skip("batch below agg_partitioned_min_rows");
     if (n_aggs > 16) skip("at most 16 aggregates");
     // accumulator plan: one 8-byte LDS cell per SUM / MIN / MAX; COUNT and AVG counts come from the row count (value columns carry no NULLs)
@@ -463,8 +463,9 @@ extern "C" dfgpu_status dfgpu_agg_preaggregate_flags(dfgpu_ctx* ctx, const dfgpu
       if (!v) skip("aggregate without an argument");
       int op = PA_NONE;
       const bool asf = cast_f64(i);
-      const bool i64 = !asf && v->type == DFGPU_INT64, u64 = !asf && v->type == DFGPU_UINT64, f64 = asf || v->type == DFGPU_FLOAT64, d128 = v->type == DFGPU_DECIMAL128;
+      const bool i64 = !asf && storage_type(v->type) == DFGPU_INT64, u64 = !asf && v->type == DFGPU_UINT64, f64 = asf || v->type == DFGPU_FLOAT64, d128 = v->type == DFGPU_DECIMAL128;
       if (!i64 && !u64 && !f64 && !d128) skip("Int64 / UInt64 / Float64 / Decimal128 aggregate arguments");
+      if (is_timestamp(v->type) && kinds[i] != DFGPU_AGG_MIN && kinds[i] != DFGPU_AGG_MAX) skip("MIN / MAX / COUNT over a Timestamp (SUM and AVG are refused, as in the reference)");
       switch (kinds[i]) {
         case DFGPU_AGG_SUM: op = d128 ? PA_SUM_I128_LO : f64 ? PA_SUM_F64 : PA_SUM_I64; break;
         case DFGPU_AGG_AVG: if (!f64 && !d128) skip("AVG over Float64 / Decimal128"); op = d128 ? PA_SUM_I128_LO : PA_SUM_F64; break;
@@ -493,7 +494,7 @@ extern "C" dfgpu_status dfgpu_agg_preaggregate_flags(dfgpu_ctx* ctx, const dfgpu
     const bool cached = ctx->pa_sample_key == ident && ctx->pa_sample_n == n && ctx->pa_sample_mask == (const void*)mk && (!packed_keys || (ctx->pa_pack && ctx->pa_pack_n == nkeys));
     BufferPtr packed; PaPackCols pc{};
     if (packed_keys) {
-      pc.n = nkeys; for (int c = 0; c < nkeys; c++) { pc.v[c] = keys[c]->values->ptr; pc.valid[c] = keys[c]->validity ? (const uint64_t*)keys[c]->validity->ptr : nullptr; pc.type[c] = keys[c]->type == DFGPU_DATE32 ? DFGPU_INT32 : keys[c]->type; pc.nullable[c] = keys[c]->validity ? 1 : 0;
+      pc.n = nkeys; for (int c = 0; c < nkeys; c++) { pc.v[c] = keys[c]->values->ptr; pc.valid[c] = keys[c]->validity ? (const uint64_t*)keys[c]->validity->ptr : nullptr; pc.type[c] = storage_type(keys[c]->type); pc.nullable[c] = keys[c]->validity ? 1 : 0;
         const int w = type_width(keys[c]->type); if (w != 1 && w != 2 && w != 4 && w != 8) fail(DFGPU_INTERNAL, "agg_preaggregate: key column %d of type %d has no integer width", c, keys[c]->type); }      // the kernels read w bytes per row: checked here, not assumed there
       if (cached) { packed = ctx->pa_pack; for (int c = 0; c < nkeys; c++) { pc.mn[c] = ctx->pa_pack_min[c]; pc.stride[c] = ctx->pa_pack_stride[c]; pc.range[c] = ctx->pa_pack_range[c]; } }
       else {
@@ -540,7 +541,7 @@ extern "C" dfgpu_status dfgpu_agg_preaggregate_flags(dfgpu_ctx* ctx, const dfgpu
     HIP_CHECK(hipMemsetAsync(ctx->d_scratch64, 0, 24, ctx->stream));          // the sample's three counters
     { KernelTimer kt_(ctx, "pa_sample");
 #define PA_SAMPLE(T) hipLaunchKernelGGL((k_pa_sample<T>), dim3(grid_for(s, BLOCK * 8, 256)), dim3(BLOCK), 0, ctx->stream, (const T*)kptr, mk, n, s, stride, (unsigned long long*)table->ptr, cap - 1, (unsigned long long*)ctx->d_scratch64)
-      switch (ktype) { case DFGPU_INT64: PA_SAMPLE(int64_t); break; case DFGPU_UINT64: PA_SAMPLE(uint64_t); break; case DFGPU_UINT32: PA_SAMPLE(uint32_t); break; default: PA_SAMPLE(int32_t); break; }
+      switch (storage_type(ktype)) { case DFGPU_INT64: PA_SAMPLE(int64_t); break; case DFGPU_UINT64: PA_SAMPLE(uint64_t); break; case DFGPU_UINT32: PA_SAMPLE(uint32_t); break; default: PA_SAMPLE(int32_t); break; }
 #undef PA_SAMPLE
       KERNEL_CHECK(); }
     ctx->count_sync("sync:pa_sample"); fetch_to_pinned(ctx, 0, ctx->d_scratch64, 24);
@@ -596,7 +597,7 @@ extern "C" dfgpu_status dfgpu_agg_preaggregate_flags(dfgpu_ctx* ctx, const dfgpu
     bind_cells();
     RpResult r;
 #define PA_PART(T) r = rp_partition(ctx, RpHashInt<T>{ (const T*)kptr, nullptr, mk }, n, (uint32_t)P1, cols, false, ctx->d_scratch64 + 9, "pa_hist", "pa_scan", "pa_scatter")
-    switch (ktype) { case DFGPU_INT64: case DFGPU_UINT64: PA_PART(int64_t); break; case DFGPU_UINT32: PA_PART(uint32_t); break; default: PA_PART(int32_t); break; }
+    switch (storage_type(ktype)) { case DFGPU_INT64: case DFGPU_UINT64: PA_PART(int64_t); break; case DFGPU_UINT32: PA_PART(uint32_t); break; default: PA_PART(int32_t); break; }
 #undef PA_PART
     packed.reset();
     if (two_level) {
@@ -692,7 +693,7 @@ extern "C" dfgpu_status dfgpu_agg_preaggregate_flags(dfgpu_ctx* ctx, const dfgpu
     const uint32_t* pp = first_seen ? (const uint32_t*)perm->ptr : nullptr; dim3 grid(grid_for(m, BLOCK));          // any order: the records leave as the partitions wrote them
     ArrayHolder ok(new_fixed(ctx, ktype, m));
     PaEmit em{}; auto add = [&](int word, void* dst, int narrow, int dstride = 1, int doff = 0) { if (em.n >= 2 + 2 * PA_MAX_AGGS) fail(DFGPU_NOT_IMPLEMENTED, "agg_preaggregate: more output columns than one emit pass writes"); em.word[em.n] = word; em.dst[em.n] = dst; em.narrow[em.n] = narrow; em.dstride[em.n] = dstride; em.doff[em.n] = doff; em.n++; };
-    add(0, ok.get()->values->ptr, (ktype == DFGPU_INT64 || ktype == DFGPU_UINT64) ? 0 : 1);
+    add(0, ok.get()->values->ptr, type_width(ktype) == 8 ? 0 : 1);
     std::vector<ArrayHolder> st((size_t)n_aggs * 2);
     // the values-seen count of every nullable column, once (UInt64 words): COUNT(x) / AVG counts copy it, state validities derive from it
     std::vector<BufferPtr> nval_buf((size_t)PA_MAX_AGGS);

@@ -478,8 +478,8 @@ __global__ void __launch_bounds__(BLOCK) k_pj_expand(const uint32_t* rows, const
 static void pj_set_lds(const void* fn, size_t bytes) { if (bytes > 48 * 1024) HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)); }     // per device, per call: cheap and free of process-wide state
 
 static bool pj_key_type_ok(const dfgpu_array* a) {
-  switch (a->type) {
-    case DFGPU_INT8: case DFGPU_INT16: case DFGPU_INT32: case DFGPU_INT64: case DFGPU_DATE32:
+  switch (storage_type(a->type)) {
+    case DFGPU_INT8: case DFGPU_INT16: case DFGPU_INT32: case DFGPU_INT64:
     case DFGPU_UINT8: case DFGPU_UINT16: case DFGPU_UINT32: case DFGPU_UINT64: return true;
     default: return false;
   }
@@ -515,8 +515,8 @@ static PjOffsets pj_partition_t(dfgpu_ctx* ctx, H hs, int64_t n, uint32_t P, RpR
 static PjOffsets pj_partition(dfgpu_ctx* ctx, const dfgpu_array* key, const uint64_t* mask, uint32_t P, RpRec12* recs, uint64_t* d_total, const char* th, const char* ts, const char* tw) {
   const uint64_t* valid = key->validity ? (const uint64_t*)key->validity->ptr : nullptr; const int64_t n = key->length;
 #define PJ_PART(T) return pj_partition_t(ctx, RpHashInt<T>{ (const T*)key->values->ptr, valid, mask }, n, P, recs, d_total, th, ts, tw)
-  switch (key->type) {
-    case DFGPU_INT8: PJ_PART(int8_t); case DFGPU_INT16: PJ_PART(int16_t); case DFGPU_INT32: case DFGPU_DATE32: PJ_PART(int32_t);
+  switch (storage_type(key->type)) {
+    case DFGPU_INT8: PJ_PART(int8_t); case DFGPU_INT16: PJ_PART(int16_t); case DFGPU_INT32: PJ_PART(int32_t);
     case DFGPU_UINT8: PJ_PART(uint8_t); case DFGPU_UINT16: PJ_PART(uint16_t); case DFGPU_UINT32: PJ_PART(uint32_t);
     default: PJ_PART(int64_t);          // INT64 / UINT64: the same 64-bit pattern
   }

@@ -1,5 +1,7 @@
 // scalar_fn.hip -- a12: ScalarFunctionExpr (physical-expr/src/scalar_function.rs, dispatch in functions.rs) for the built-in functions the measured queries call:
 //   date_part(part, Date32) -> Float64      datetime_expressions.rs:1019-1061 (arrow-arith temporal kernels over chrono), epoch :1128-1130
+//   date_part(part, Timestamp) -> Float64   the same, all fourteen parts (to_ticks :1063-1076, epoch :1116-1126)      k_ts_part<UNIT, PART, VEC>
+//   date_trunc(granularity, Timestamp) -> Timestamp   datetime_expressions.rs:429-692                                   k_ts_trunc<UNIT, GRAN, VEC>
 //   character_length(Utf8)  -> Int32        unicode_expressions.rs:42-60      code points, not bytes
 //   substr(Utf8, start [, count]) -> Utf8   unicode_expressions.rs:361-415
 //   left / right(Utf8, n)   -> Utf8         unicode_expressions.rs:65-91, :206-
@@ -9,7 +11,7 @@
 // date_part: civil-from-days in 64-bit integer arithmetic (days since 1970-01-01 -> proleptic Gregorian year / month / day; the divisions by 146097, 36524, 1460
 // and 153 are by constants), so no Int32 day count overflows or faults.  Outside 0001-01-01 .. 9999-12-31 the value is whatever that arithmetic gives (the
 // reference answers NULL only beyond chrono's own range; nothing pins that).  hour is 0.0 for a date, epoch is days * 86400.0; the sub-hour parts are
-// NOT_IMPLEMENTED for Date32.  k_date_part gives every lane four days (one 16-B load, two 16-B stores) when the slice is 16-byte aligned.
+// NOT_IMPLEMENTED for Date32 (a Timestamp has them: see the Timestamp section below).  k_date_part gives every lane four days (one 16-B load, two 16-B stores) when the slice is 16-byte aligned.
 //
 // Strings: one pass turns each row into a byte range [begin, end) of the source (or into its number of code points).  A code point starts at every byte b with
 // (b & 0xC0) != 0x80; these lead bytes are counted a word at a time (popcount over a masked 8- or 16-byte load), never byte by byte.
@@ -22,7 +24,7 @@
 // A negative substr count on a selected row whose string, start and count are all non-NULL raises DFGPU_FLAG_SUBSTR_LENGTH.
 // A dictionary column that is the only column and has fewer entries than rows is evaluated once per entry: a Utf8 result stays a dictionary over the same codes,
 // other results are gathered through the codes.  Every other dictionary argument (a dictionary as large as the column, one beside another column, a substr whose
-// count can raise -- its errors belong to rows) is decoded with a take and goes row by row.
+// count can raise and every date_trunc -- their errors belong to rows) is decoded with a take and goes row by row.
 #include <strings.h>
 #include "device_utils.h"
 
@@ -30,14 +32,12 @@ namespace dfgpu {
 
 constexpr int64_t STR_MAX = 0x7fffffff;              // Utf8 offsets are Int32: no row holds more code points than this
 
-enum { DP_YEAR = 0, DP_QUARTER, DP_MONTH, DP_WEEK, DP_DAY, DP_DOY, DP_DOW, DP_HOUR, DP_EPOCH, DP_COUNT };
+enum { DP_YEAR = 0, DP_QUARTER, DP_MONTH, DP_WEEK, DP_DAY, DP_DOY, DP_DOW, DP_HOUR, DP_EPOCH, DP_MINUTE, DP_SECOND, DP_MILLISECOND, DP_MICROSECOND, DP_NANOSECOND, DP_COUNT };      // from DP_MINUTE on: Timestamp only
 
 // ---------------------------------------------------------------- date_part
 __device__ inline bool dp_leap(int64_t y) { return (y % 4 == 0) && (y % 100 != 0 || y % 400 == 0); }
-template <int PART> __device__ inline double date_part_of(int32_t days32) {
-  const int64_t days = days32;
-  if (PART == DP_HOUR) return 0.0;
-  if (PART == DP_EPOCH) return (double)days * 86400.0;
+// the parts that depend on the day number alone (year .. dow), days since 1970-01-01
+template <int PART> __device__ inline double day_part_of(int64_t days) {
   const int dow = (int)(((days % 7) + 11) % 7);                    // 1970-01-01 was a Thursday; days from Sunday
   if (PART == DP_DOW) return (double)dow;
   // civil from days: eras of 400 years = 146097 days starting on 0000-03-01
@@ -64,6 +64,11 @@ template <int PART> __device__ inline double date_part_of(int32_t days32) {
   else if (week == 53 && yday - (365 + leap) - wd + 10 >= 7) week = 1;            // already week 1 of the next year
   return (double)week;
 }
+template <int PART> __device__ inline double date_part_of(int32_t days32) {
+  if (PART == DP_HOUR) return 0.0;
+  if (PART == DP_EPOCH) return (double)days32 * 86400.0;
+  return day_part_of<PART>(days32);
+}
 // VEC: `in` and `out` are 16-byte aligned; every lane takes four days per step, the ragged tail goes one day per lane
 template <int PART, bool VEC> __global__ void __launch_bounds__(BLOCK) k_date_part(const int32_t* __restrict__ in, int64_t n, double* __restrict__ out) {
   const int64_t tid = (int64_t)blockIdx.x * BLOCK + threadIdx.x, stride = (int64_t)gridDim.x * BLOCK;
@@ -85,6 +90,144 @@ template <int PART> static void launch_date_part(dfgpu_ctx* ctx, const int32_t* 
   const bool vec = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
   if (vec) hipLaunchKernelGGL((k_date_part<PART, true>), dim3(grid_for((n >> 2) + 4, BLOCK, (int64_t)ctx->num_cus * 8)), dim3(BLOCK), 0, ctx->stream, in, n, out);
   else hipLaunchKernelGGL((k_date_part<PART, false>), dim3(grid_for(n, BLOCK, (int64_t)ctx->num_cus * 8)), dim3(BLOCK), 0, ctx->stream, in, n, out);
+}
+
+// ---------------------------------------------------------------- Timestamp: date_part and date_trunc
+// UNIT: 0 second, 1 millisecond, 2 microsecond, 3 nanosecond -- a template parameter, so every division below is by a compile-time constant
+template <int UNIT> struct TsUnit { static constexpr int64_t PER_SEC = UNIT == 0 ? 1ll : UNIT == 1 ? 1000ll : UNIT == 2 ? 1000000ll : 1000000000ll; static constexpr int64_t PER_DAY = 86400ll * PER_SEC; };
+__device__ inline int64_t floor_div(int64_t a, int64_t b) { const int64_t q = a / b; return (a % b != 0 && (a < 0)) ? q - 1 : q; }      // b > 0: div_euclid
+
+// date_part over a Timestamp (datetime_expressions.rs:1019-1142): the instant is split with floor semantics (arrow's split_second is div_euclid / rem_euclid)
+// into days, second of the day and nanosecond of the second.  second .. nanosecond keep the operation order of to_ticks (:1063-1076) and epoch that of :1123-1126,
+// with contraction off: no fma of the add and the multiply, the division stays a division -- the results are those of IEEE double evaluation.
+template <int UNIT, int PART> __device__ inline double ts_part_of(int64_t v) {
+#pragma clang fp contract(off)
+  constexpr int64_t U = TsUnit<UNIT>::PER_SEC;
+  if (PART == DP_EPOCH) return (double)v / (double)U;
+  const int64_t sec = floor_div(v, U);
+  const int64_t days = floor_div(sec, 86400);
+  if (PART <= DP_DOW) return day_part_of<PART>(days);
+  const int32_t sod = (int32_t)(sec - days * 86400);               // [0, 86399]
+  if (PART == DP_HOUR) return (double)(sod / 3600);
+  if (PART == DP_MINUTE) return (double)((sod % 3600) / 60);
+  const int64_t rem = v % U;                                       // no product: sec * U leaves an Int64 for v next to INT64_MIN
+  const int32_t nanos = (int32_t)((rem < 0 ? rem + U : rem) * (1000000000ll / U));      // [0, 999999999]
+  const double s = (double)(sod % 60) + (double)nanos / 1000000000.0;
+  const double frac = PART == DP_SECOND ? 1.0 : PART == DP_MILLISECOND ? 1000.0 : PART == DP_MICROSECOND ? 1000000.0 : 1000000000.0;
+  return s * frac;
+}
+// VEC: `in` and `out` are 16-byte aligned; every lane takes two instants per step (one 16-B load, one 16-B store), the odd last row goes alone
+template <int UNIT, int PART, bool VEC> __global__ void __launch_bounds__(BLOCK) k_ts_part(const int64_t* __restrict__ in, int64_t n, double* __restrict__ out) {
+  const int64_t tid = (int64_t)blockIdx.x * BLOCK + threadIdx.x, stride = (int64_t)gridDim.x * BLOCK;
+  if (VEC) {
+    const int64_t n2 = n >> 1;
+    for (int64_t g = tid; g < n2; g += stride) {
+      const longlong2 t = ((const longlong2*)in)[g];
+      double2 r; r.x = ts_part_of<UNIT, PART>(t.x); r.y = ts_part_of<UNIT, PART>(t.y);
+      ((double2*)out)[g] = r;
+    }
+    if (tid == 0 && (n & 1)) out[n - 1] = ts_part_of<UNIT, PART>(in[n - 1]);
+  } else {
+    for (int64_t i = tid; i < n; i += stride) out[i] = ts_part_of<UNIT, PART>(in[i]);
+  }
+}
+
+// date_trunc (datetime_expressions.rs:429-692).  The reference converts every unit to nanoseconds, clears the fields below the granularity on a chrono
+// NaiveDateTime (floor semantics, week = back to Monday) and divides back with `/`; here the same is computed in the column's own unit:
+//   year .. second        floor to the period (civil arithmetic for year / quarter / month)
+//   millisecond, microsecond   general_date_trunc's integer division, which truncates TOWARD ZERO: -1500 us at 'millisecond' is -1000 us, while -1500 ms at
+//                         'second' is -2000 ms.  A granularity as fine as the unit or finer is the identity.
+// The reference is defined only where the instant and its truncation fit an Int64 of nanoseconds; a row outside that window raises DFGPU_FLAG_TS_RANGE (the
+// caller passes null for NULL or deselected rows' flag word) and gets 0.
+enum { TG_YEAR = 0, TG_QUARTER, TG_MONTH, TG_WEEK, TG_DAY, TG_HOUR, TG_MINUTE, TG_SECOND, TG_MILLISECOND, TG_MICROSECOND, TG_COUNT };
+__device__ inline int64_t days_from_civil(int64_t y, uint32_t m) {          // day number of y-m-01
+  y -= m <= 2 ? 1 : 0;
+  const int64_t era = (y >= 0 ? y : y - 399) / 400;
+  const uint32_t yoe = (uint32_t)(y - era * 400);
+  const uint32_t doy = (153 * (m > 2 ? m - 3 : m + 9) + 2) / 5;
+  const uint32_t doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
+  return era * 146097 + (int64_t)doe - 719468;
+}
+template <int UNIT, int GRAN> __device__ inline int64_t ts_trunc_of(int64_t v, bool* out_of_range) {
+  constexpr int64_t U = TsUnit<UNIT>::PER_SEC, DAY = TsUnit<UNIT>::PER_DAY, NS = 1000000000ll / U;      // NS: nanoseconds per unit
+  constexpr int64_t LO = INT64_MIN / NS, HI = INT64_MAX / NS;             // the window in this unit (`/` rounds toward zero: inward on both sides)
+  if (v < LO || v > HI) { *out_of_range = true; return 0; }
+  if (GRAN >= TG_MILLISECOND) {
+    constexpr int64_t G = GRAN == TG_MILLISECOND ? 1000ll : 1000000ll;    // granules per second
+    if (U > G) { constexpr int64_t D = U / G; return v / D * D; }
+    return v;
+  }
+  if (GRAN >= TG_DAY) {                                                    // a fixed period that divides the day
+    constexpr int64_t P = GRAN == TG_DAY ? DAY : GRAN == TG_HOUR ? 3600 * U : GRAN == TG_MINUTE ? 60 * U : U;
+    const int64_t q = floor_div(v, P);
+    if (q < LO / P) { *out_of_range = true; return 0; }                    // q * P would lie below the window
+    return q * P;
+  }
+  const int64_t days = floor_div(v, DAY);                                 // |days| <= 106752 inside the window
+  int64_t first;
+  if (GRAN == TG_WEEK) { const int64_t wd = (days % 7 + 10) % 7; first = days - wd; }      // 1970-01-01 was a Thursday: days since Monday
+  else {
+    const int64_t z = days + 719468;
+    const int64_t era = (z >= 0 ? z : z - 146096) / 146097;
+    const uint32_t doe = (uint32_t)(z - era * 146097);
+    const uint32_t yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;
+    const uint32_t doy = doe - (365 * yoe + yoe / 4 - yoe / 100);
+    const uint32_t mp = (5 * doy + 2) / 153;
+    const uint32_t m = mp < 10 ? mp + 3 : mp - 9;
+    const int64_t y = (int64_t)yoe + era * 400 + (m <= 2 ? 1 : 0);
+    first = days_from_civil(y, GRAN == TG_YEAR ? 1u : GRAN == TG_QUARTER ? (m - 1) / 3 * 3 + 1 : m);
+  }
+  if (first < LO / DAY) { *out_of_range = true; return 0; }
+  return first * DAY;
+}
+struct TsTruncArgs { const int64_t* in; int64_t* out; const uint64_t* valid; const uint64_t* selected; uint32_t* flags; int64_t* bad; };      // bad: d_scratch64[TS_BAD_SLOT] receives one of the instants that raised, for check_flags' message
+
+template <int UNIT, int GRAN> __device__ inline int64_t ts_trunc_row(const TsTruncArgs& A, int64_t i, int64_t v) {
+  bool oor = false;
+  const int64_t r = ts_trunc_of<UNIT, GRAN>(v, &oor);
+  if (oor && valid_at(A.valid, i) && valid_at(A.selected, i)) { atomicOr(A.flags, DFGPU_FLAG_TS_RANGE); *A.bad = v; }
+  return r;
+}
+template <int UNIT, int GRAN, bool VEC> __global__ void __launch_bounds__(BLOCK) k_ts_trunc(TsTruncArgs A, int64_t n) {
+  const int64_t tid = (int64_t)blockIdx.x * BLOCK + threadIdx.x, stride = (int64_t)gridDim.x * BLOCK;
+  if (VEC) {
+    const int64_t n2 = n >> 1;
+    for (int64_t g = tid; g < n2; g += stride) {
+      const longlong2 t = ((const longlong2*)A.in)[g];
+      longlong2 r; r.x = ts_trunc_row<UNIT, GRAN>(A, 2 * g, t.x); r.y = ts_trunc_row<UNIT, GRAN>(A, 2 * g + 1, t.y);
+      ((longlong2*)A.out)[g] = r;
+    }
+    if (tid == 0 && (n & 1)) A.out[n - 1] = ts_trunc_row<UNIT, GRAN>(A, n - 1, A.in[n - 1]);
+  } else {
+    for (int64_t i = tid; i < n; i += stride) A.out[i] = ts_trunc_row<UNIT, GRAN>(A, i, A.in[i]);
+  }
+}
+template <int UNIT, int PART> static void launch_ts_part(dfgpu_ctx* ctx, const int64_t* in, int64_t n, double* out) {
+  const bool vec = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
+  if (vec) hipLaunchKernelGGL((k_ts_part<UNIT, PART, true>), dim3(grid_for((n >> 1) + 1, BLOCK, (int64_t)ctx->num_cus * 8)), dim3(BLOCK), 0, ctx->stream, in, n, out);
+  else hipLaunchKernelGGL((k_ts_part<UNIT, PART, false>), dim3(grid_for(n, BLOCK, (int64_t)ctx->num_cus * 8)), dim3(BLOCK), 0, ctx->stream, in, n, out);
+}
+template <int UNIT> static void launch_ts_part_unit(dfgpu_ctx* ctx, int part, const int64_t* in, int64_t n, double* out) {
+  switch (part) {
+#define TP_CASE(P) case P: launch_ts_part<UNIT, P>(ctx, in, n, out); break;
+    TP_CASE(DP_YEAR) TP_CASE(DP_QUARTER) TP_CASE(DP_MONTH) TP_CASE(DP_WEEK) TP_CASE(DP_DAY) TP_CASE(DP_DOY) TP_CASE(DP_DOW) TP_CASE(DP_HOUR) TP_CASE(DP_EPOCH)
+    TP_CASE(DP_MINUTE) TP_CASE(DP_SECOND) TP_CASE(DP_MILLISECOND) TP_CASE(DP_MICROSECOND) TP_CASE(DP_NANOSECOND)
+#undef TP_CASE
+    default: fail(DFGPU_INTERNAL, "date_part: part %d", part);
+  }
+}
+template <int UNIT, int GRAN> static void launch_ts_trunc(dfgpu_ctx* ctx, const TsTruncArgs& A, int64_t n) {
+  const bool vec = (((uintptr_t)A.in | (uintptr_t)A.out) & 15) == 0;
+  if (vec) hipLaunchKernelGGL((k_ts_trunc<UNIT, GRAN, true>), dim3(grid_for((n >> 1) + 1, BLOCK, (int64_t)ctx->num_cus * 8)), dim3(BLOCK), 0, ctx->stream, A, n);
+  else hipLaunchKernelGGL((k_ts_trunc<UNIT, GRAN, false>), dim3(grid_for(n, BLOCK, (int64_t)ctx->num_cus * 8)), dim3(BLOCK), 0, ctx->stream, A, n);
+}
+template <int UNIT> static void launch_ts_trunc_unit(dfgpu_ctx* ctx, int gran, const TsTruncArgs& A, int64_t n) {
+  switch (gran) {
+#define TG_CASE(G) case G: launch_ts_trunc<UNIT, G>(ctx, A, n); break;
+    TG_CASE(TG_YEAR) TG_CASE(TG_QUARTER) TG_CASE(TG_MONTH) TG_CASE(TG_WEEK) TG_CASE(TG_DAY) TG_CASE(TG_HOUR) TG_CASE(TG_MINUTE) TG_CASE(TG_SECOND) TG_CASE(TG_MILLISECOND) TG_CASE(TG_MICROSECOND)
+#undef TG_CASE
+    default: fail(DFGPU_INTERNAL, "date_trunc: granularity %d", gran);
+  }
 }
 
 // the scalar part name (length, validity, up to 16 bytes) in one read-back: slots 0..3
@@ -336,36 +479,80 @@ static StrCol str_col(const dfgpu_array* a, int32_t scalar) { return StrCol{a->v
 static IntCol int_col(const dfgpu_array* a, int32_t scalar) { return IntCol{(const int64_t*)a->values->ptr, scalar ? 0 : 1}; }
 
 static int date_part_code(const char* name, size_t len) {
-  static const char* names[DP_COUNT] = {"year", "quarter", "month", "week", "day", "doy", "dow", "hour", "epoch"};
+  static const char* names[DP_COUNT] = {"year", "quarter", "month", "week", "day", "doy", "dow", "hour", "epoch", "minute", "second", "millisecond", "microsecond", "nanosecond"};
   for (int p = 0; p < DP_COUNT; p++) if (strlen(names[p]) == len && !strncasecmp(names[p], name, len)) return p;
-  static const char* later[] = {"minute", "second", "millisecond", "microsecond", "nanosecond"};
-  for (const char* l : later) if (strlen(l) == len && !strncasecmp(l, name, len)) return -2;
   return -1;
+}
+static int date_trunc_code(const char* name, size_t len) {
+  static const char* names[TG_COUNT] = {"year", "quarter", "month", "week", "day", "hour", "minute", "second", "millisecond", "microsecond"};
+  for (int g = 0; g < TG_COUNT; g++) if (strlen(names[g]) == len && !strncasecmp(names[g], name, len)) return g;
+  return -1;
+}
+// the scalar Utf8 name argument of date_part / date_trunc: its length (negative: offsets decrease), validity and first 16 bytes
+static int64_t probe_name(dfgpu_ctx* ctx, const dfgpu_array* part, bool* valid, char name[17]) {
+  hipLaunchKernelGGL(k_fn_probe_name, dim3(1), dim3(64), 0, ctx->stream, (const int32_t*)part->offsets->ptr, part->values ? (const uint8_t*)part->values->ptr : nullptr, words_of(part->validity), ctx->d_scratch64);
+  KERNEL_CHECK();
+  const uint64_t* sc = read_scratch_range(ctx, 0, 4);
+  *valid = sc[1] != 0; memset(name, 0, 17); memcpy(name, sc + 2, 16);
+  return (int64_t)sc[0];
 }
 
 static dfgpu_array* date_part(dfgpu_ctx* ctx, const dfgpu_array* part, const dfgpu_array* dates) {
   const int64_t n = dates->length;
-  hipLaunchKernelGGL(k_fn_probe_name, dim3(1), dim3(64), 0, ctx->stream, (const int32_t*)part->offsets->ptr, part->values ? (const uint8_t*)part->values->ptr : nullptr, words_of(part->validity), ctx->d_scratch64);
-  KERNEL_CHECK();
-  const uint64_t* sc = read_scratch_range(ctx, 0, 4);
-  const int64_t len = (int64_t)sc[0]; const bool part_valid = sc[1] != 0;
-  char name[17] = {0}; memcpy(name, sc + 2, 16);
+  bool part_valid = false; char name[17];
+  const int64_t len = probe_name(ctx, part, &part_valid, name);
   if (!part_valid) { ArrayHolder h(new_fixed(ctx, DFGPU_FLOAT64, n, 0, 0, true)); if (n) HIP_CHECK(hipMemsetAsync(h.get()->values->ptr, 0, (size_t)n * 8, ctx->stream)); h.get()->null_count = n; return h.release(); }
   if (len < 0) fail(DFGPU_INVALID_ARGUMENT, "date_part: the part name's offsets decrease");
   const int p = len <= 16 ? date_part_code(name, (size_t)len) : -1;
-  if (p == -2) fail(DFGPU_NOT_IMPLEMENTED, "date_part('%s', Date32) is not implemented on the device", name);
+  const bool ts = is_timestamp(dates->type);
+  if (p >= DP_MINUTE && !ts) fail(DFGPU_NOT_IMPLEMENTED, "date_part('%s', Date32) is not implemented on the device", name);
   if (p < 0) fail(DFGPU_EXECUTION, "Date part '%s' not supported", len <= 16 ? name : "(a name of more than 16 bytes)");
   ArrayHolder h(new_fixed(ctx, DFGPU_FLOAT64, n));
   if (dates->validity) { h.get()->validity = dates->validity; h.get()->null_count = dates->null_count; }       // shared, not copied
   if (n) {
-    KernelTimer kt_(ctx, "k_date_part");
+    KernelTimer kt_(ctx, ts ? "k_ts_part" : "k_date_part");
     const int32_t* in = (const int32_t*)dates->values->ptr; double* out = (double*)h.get()->values->ptr;
-    switch (p) {
+    if (ts) {
+      const int64_t* tin = (const int64_t*)dates->values->ptr;
+      switch (dates->type) {
+        case DFGPU_TIMESTAMP_SECOND: launch_ts_part_unit<0>(ctx, p, tin, n, out); break;
+        case DFGPU_TIMESTAMP_MILLISECOND: launch_ts_part_unit<1>(ctx, p, tin, n, out); break;
+        case DFGPU_TIMESTAMP_MICROSECOND: launch_ts_part_unit<2>(ctx, p, tin, n, out); break;
+        default: launch_ts_part_unit<3>(ctx, p, tin, n, out); break;
+      }
+    } else switch (p) {
 #define DP_CASE(P) case P: launch_date_part<P>(ctx, in, n, out); break;
       DP_CASE(DP_YEAR) DP_CASE(DP_QUARTER) DP_CASE(DP_MONTH) DP_CASE(DP_WEEK) DP_CASE(DP_DAY) DP_CASE(DP_DOY) DP_CASE(DP_DOW) DP_CASE(DP_HOUR) DP_CASE(DP_EPOCH)
 #undef DP_CASE
     }
     KERNEL_CHECK();
+  }
+  return h.release();
+}
+
+// date_trunc(granularity, Timestamp) -> Timestamp of the same unit; `gran` is a scalar (the caller checked), `ts` a plain column or a scalar (a dictionary was
+// decoded: errors belong to rows)
+static dfgpu_array* date_trunc(dfgpu_ctx* ctx, const dfgpu_array* gran, const dfgpu_array* ts) {
+  const int64_t n = ts->length;
+  bool gran_valid = false; char name[17];
+  const int64_t len = probe_name(ctx, gran, &gran_valid, name);
+  if (!gran_valid) fail(DFGPU_EXECUTION, "Granularity of `date_trunc` must be non-null scalar Utf8");
+  if (len < 0) fail(DFGPU_INVALID_ARGUMENT, "date_trunc: the granularity's offsets decrease");
+  const int g = len <= 16 ? date_trunc_code(name, (size_t)len) : -1;
+  if (g < 0) fail(DFGPU_EXECUTION, "Unsupported date_trunc granularity: %s", len <= 16 ? name : "(a name of more than 16 bytes)");
+  ArrayHolder h(new_fixed(ctx, ts->type, n));
+  if (ts->validity) { h.get()->validity = ts->validity; h.get()->null_count = ts->null_count; }       // shared, not copied
+  if (n) {
+    KernelTimer kt_(ctx, "k_ts_trunc");
+    const TsTruncArgs A{(const int64_t*)ts->values->ptr, (int64_t*)h.get()->values->ptr, words_of(ts->validity), row_selection_words(ctx, n), ctx->d_flags, (int64_t*)(ctx->d_scratch64 + TS_BAD_SLOT)};
+    switch (ts->type) {
+      case DFGPU_TIMESTAMP_SECOND: launch_ts_trunc_unit<0>(ctx, g, A, n); break;
+      case DFGPU_TIMESTAMP_MILLISECOND: launch_ts_trunc_unit<1>(ctx, g, A, n); break;
+      case DFGPU_TIMESTAMP_MICROSECOND: launch_ts_trunc_unit<2>(ctx, g, A, n); break;
+      default: launch_ts_trunc_unit<3>(ctx, g, A, n); break;
+    }
+    KERNEL_CHECK();
+    check_flags(ctx, "date_trunc");
   }
   return h.release();
 }
@@ -472,7 +659,7 @@ dfgpu_status dfgpu_scalar_function(dfgpu_ctx* ctx, int32_t fn, const dfgpu_array
     if (nargs < 1 || nargs > 3) fail(DFGPU_NOT_IMPLEMENTED, "scalar_function: function %d with %d arguments is not implemented on the device", fn, nargs);
     for (int32_t k = 0; k < nargs; k++) if (!args[k]) fail(DFGPU_INVALID_ARGUMENT, "scalar_function: null argument");
     // the table of include/dfgpu.h: argument counts and logical types
-    static const int32_t I = DFGPU_INT64, U = DFGPU_UTF8, D = DFGPU_DATE32;
+    static const int32_t I = DFGPU_INT64, U = DFGPU_UTF8, D = DFGPU_DATE32, T = -1;      // T: a Timestamp of any unit; D of DATE_PART takes one too
     int32_t want[3] = {0, 0, 0}, result = 0; bool ok = false;
     switch (fn) {
       case DFGPU_FN_DATE_PART: ok = nargs == 2; want[0] = U; want[1] = D; result = DFGPU_FLOAT64; break;
@@ -480,6 +667,7 @@ dfgpu_status dfgpu_scalar_function(dfgpu_ctx* ctx, int32_t fn, const dfgpu_array
       case DFGPU_FN_SUBSTR: ok = nargs == 2 || nargs == 3; want[0] = U; want[1] = I; want[2] = I; result = U; break;
       case DFGPU_FN_LEFT: case DFGPU_FN_RIGHT: ok = nargs == 2; want[0] = U; want[1] = I; result = U; break;
       case DFGPU_FN_STARTS_WITH: ok = nargs == 2; want[0] = U; want[1] = U; result = DFGPU_BOOL; break;
+      case DFGPU_FN_DATE_TRUNC: ok = nargs == 2; want[0] = U; want[1] = T; break;          // result: the type of argument 1
       default: fail(DFGPU_NOT_IMPLEMENTED, "scalar_function: function %d is not implemented on the device", fn);
     }
     if (!ok) fail(DFGPU_NOT_IMPLEMENTED, "scalar_function: function %d with %d arguments is not implemented on the device", fn, nargs);
@@ -487,7 +675,9 @@ dfgpu_status dfgpu_scalar_function(dfgpu_ctx* ctx, int32_t fn, const dfgpu_array
     for (int32_t k = 0; k < nargs; k++) {
       const dfgpu_array* a = args[k];
       if (a->type == DFGPU_DICTIONARY && !a->dictionary) fail(DFGPU_INVALID_ARGUMENT, "scalar_function: dictionary argument without a dictionary");
-      if (logical_type(a) != want[k]) fail(DFGPU_NOT_IMPLEMENTED, "scalar_function: function %d takes type %d as argument %d, not %d; the planner coerces first", fn, want[k], k, logical_type(a));
+      const bool ts_arg = is_timestamp(logical_type(a)) && (want[k] == T || (want[k] == D && fn == DFGPU_FN_DATE_PART));
+      if (want[k] == T && ts_arg) result = logical_type(a);
+      if (logical_type(a) != want[k] && !ts_arg) fail(DFGPU_NOT_IMPLEMENTED, "scalar_function: function %d takes type %d as argument %d, not %d; the planner coerces first", fn, want[k], k, logical_type(a));
       if (arg_is_scalar[k]) { if (a->length != 1) fail(DFGPU_INVALID_ARGUMENT, "scalar_function: a scalar argument must have length 1, not %lld", (long long)a->length); }
       else if (n < 0) n = a->length;
       else if (n != a->length) fail(DFGPU_INVALID_ARGUMENT, "scalar_function: argument lengths differ (%lld vs %lld)", (long long)n, (long long)a->length);
@@ -495,6 +685,7 @@ dfgpu_status dfgpu_scalar_function(dfgpu_ctx* ctx, int32_t fn, const dfgpu_array
     }
     if (n < 0) n = 1;                          // every argument is a scalar
     if (fn == DFGPU_FN_DATE_PART && !arg_is_scalar[0]) fail(DFGPU_NOT_IMPLEMENTED, "date_part: the part name must be a scalar");
+    if (fn == DFGPU_FN_DATE_TRUNC && (!arg_is_scalar[0] || args[0]->type == DFGPU_DICTIONARY)) fail(DFGPU_EXECUTION, "Granularity of `date_trunc` must be non-null scalar Utf8");
     if (dk >= 0) {
       // Once per dictionary entry and then through the codes, when that is less work (a dictionary smaller than the column, as dfgpu_like decides) and the
       // only column; a substr that can raise stays with the rows, because its errors belong to rows inside the row selection, not to dictionary entries.
@@ -502,6 +693,7 @@ dfgpu_status dfgpu_scalar_function(dfgpu_ctx* ctx, int32_t fn, const dfgpu_array
       for (int32_t k = 0; k < nargs; k++) if (k != dk && !arg_is_scalar[k]) per_entry = false;
       int64_t c = 0;
       if (fn == DFGPU_FN_SUBSTR && nargs == 3 && !host_scalar_null(args[2]) && !(host_scalar_i64(args[2], &c) && c >= 0)) per_entry = false;
+      if (fn == DFGPU_FN_DATE_TRUNC) per_entry = false;          // a row outside the nanosecond window raises: rows, not entries
       if (!per_entry) {                        // decode, then row by row
         ArrayHolder decoded(decode_dictionary(ctx, args[dk]));
         const dfgpu_array* plain[3] = {nullptr, nullptr, nullptr};
@@ -519,6 +711,7 @@ dfgpu_status dfgpu_scalar_function(dfgpu_ctx* ctx, int32_t fn, const dfgpu_array
     }
     if (n == 0) { *out = empty_result(ctx, result); return; }
     if (fn == DFGPU_FN_DATE_PART) { *out = date_part(ctx, args[0], args[1]); return; }
+    if (fn == DFGPU_FN_DATE_TRUNC) { *out = date_trunc(ctx, args[0], args[1]); return; }
     *out = string_function(ctx, fn, args, arg_is_scalar, nargs, n);
   });
 }

@@ -716,7 +716,7 @@ static void sort_impl(dfgpu_ctx* ctx, const dfgpu_array* const* cols, const uint
       for (int c = 0; c < k && ok; c++) {
         const dfgpu_array* a = cols[c];
         ok = a->type != DFGPU_DICTIONARY && a->type != DFGPU_UTF8 && a->type != DFGPU_BOOL && type_width(a->type) > 0;
-        pc.c[c].v = ok ? a->values->ptr : nullptr; pc.c[c].valid = a->validity ? (const uint64_t*)a->validity->ptr : nullptr; pc.c[c].type = a->type;
+        pc.c[c].v = ok ? a->values->ptr : nullptr; pc.c[c].valid = a->validity ? (const uint64_t*)a->validity->ptr : nullptr; pc.c[c].type = storage_type(a->type);
         pc.c[c].desc = descending && descending[c]; pc.c[c].nulls_first = nulls_first ? nulls_first[c] : 1;
       }
       // The value ranges cost a pass over the key columns (0.64 ms for a Decimal128 + Date32 pair over 100 M rows).  A large input takes them from a sample first (every

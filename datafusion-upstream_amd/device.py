@@ -141,10 +141,11 @@ class Context:
         return self._wrap(out)
 
     def wrap_tensor(self, tensor, dtype: int, precision: int = 0, scale: int = 0) -> "Array":
-        """Zero-copy view of a contiguous torch CUDA tensor as a non-null fixed-width column."""
+        """Zero-copy view of a contiguous torch CUDA tensor as a non-null fixed-width column (a Timestamp of any unit: an int64 tensor of counts since the epoch)."""
         d = capi.ArrayDesc()
         width = {capi.INT8: 1, capi.UINT8: 1, capi.INT16: 2, capi.UINT16: 2, capi.INT32: 4, capi.UINT32: 4, capi.FLOAT32: 4, capi.DATE32: 4,
-                 capi.INT64: 8, capi.UINT64: 8, capi.FLOAT64: 8, capi.DECIMAL128: 16}[dtype]
+                 capi.INT64: 8, capi.UINT64: 8, capi.FLOAT64: 8, capi.DECIMAL128: 16,
+                 capi.TIMESTAMP_SECOND: 8, capi.TIMESTAMP_MILLISECOND: 8, capi.TIMESTAMP_MICROSECOND: 8, capi.TIMESTAMP_NANOSECOND: 8}[dtype]
         nbytes = tensor.numel() * tensor.element_size()
         assert tensor.is_contiguous() and nbytes % width == 0
         d.type, d.precision, d.scale, d.length, d.null_count = dtype, precision, scale, nbytes // width, 0
@@ -249,7 +250,7 @@ class Context:
         return self._wrap(out)
 
     def scalar_function(self, fn: int, args, scalars=None) -> "Array":
-        """dfgpu_scalar_function: fn = FN_DATE_PART .. FN_STARTS_WITH over 1 to 3 arrays; scalars[k]: args[k] is a length-1 array that stands for every row"""
+        """dfgpu_scalar_function: fn = FN_DATE_PART .. FN_DATE_TRUNC (a DFGPU_FN_* of include/dfgpu.h) over 1 to 3 arrays; scalars[k]: args[k] is a length-1 array that stands for every row"""
         n = len(args)
         scalars = [False] * n if scalars is None else list(scalars)
         ah = (C.c_void_p * n)(*[a.h for a in args])

@@ -265,7 +265,7 @@ class LikeExpr(PhysicalExpr):
         return _ExprH(out)
 
 
-FN_DATE_PART, FN_CHARACTER_LENGTH, FN_SUBSTR, FN_LEFT, FN_RIGHT, FN_STARTS_WITH = 1, 2, 3, 4, 5, 6          # DFGPU_FN_* (include/dfgpu.h)
+FN_DATE_PART, FN_CHARACTER_LENGTH, FN_SUBSTR, FN_LEFT, FN_RIGHT, FN_STARTS_WITH, FN_DATE_TRUNC = 1, 2, 3, 4, 5, 6, 7          # DFGPU_FN_* (include/dfgpu.h)
 
 
 class ScalarFunctionExpr(PhysicalExpr):
@@ -284,8 +284,32 @@ class ScalarFunctionExpr(PhysicalExpr):
 
 
 def date_part(part: PhysicalExpr, date: PhysicalExpr) -> ScalarFunctionExpr:
-    """date_part(part, Date32) -> Float64; `part` is a Utf8 literal: year, quarter, month, week, day, doy, dow, hour, epoch"""
+    """date_part(part, Date32 | Timestamp) -> Float64; `part` is a Utf8 literal: year, quarter, month, week, day, doy, dow, hour, epoch and, over a
+    Timestamp, minute, second, millisecond, microsecond, nanosecond"""
     return ScalarFunctionExpr(FN_DATE_PART, [part, date])
+
+
+def date_trunc(granularity: PhysicalExpr, ts: PhysicalExpr) -> ScalarFunctionExpr:
+    """date_trunc(granularity, Timestamp) -> Timestamp of the same unit; `granularity` is a Utf8 literal: year, quarter, month, week (to Monday), day, hour,
+    minute, second (floor), millisecond, microsecond (toward zero).  A row outside the range of an Int64 of nanoseconds raises."""
+    return ScalarFunctionExpr(FN_DATE_TRUNC, [granularity, ts])
+
+
+def to_timestamp_seconds(arg: PhysicalExpr) -> "CastExpr":
+    """to_timestamp_seconds(Int64): the cast to Timestamp(Second) -- the values unchanged"""
+    return CastExpr(arg, capi.TIMESTAMP_SECOND)
+
+
+def to_timestamp_millis(arg: PhysicalExpr) -> "CastExpr":
+    return CastExpr(arg, capi.TIMESTAMP_MILLISECOND)
+
+
+def to_timestamp_micros(arg: PhysicalExpr) -> "CastExpr":
+    return CastExpr(arg, capi.TIMESTAMP_MICROSECOND)
+
+
+def to_timestamp_nanos(arg: PhysicalExpr) -> "CastExpr":
+    return CastExpr(arg, capi.TIMESTAMP_NANOSECOND)
 
 
 def character_length(s: PhysicalExpr) -> ScalarFunctionExpr:

@@ -39,7 +39,24 @@ enum { DFGPU_OK = 0, DFGPU_EXECUTION = 1, DFGPU_INTERNAL = 2, DFGPU_RESOURCES_EX
 enum { DFGPU_BOOL = 1, DFGPU_INT8 = 2, DFGPU_INT16 = 3, DFGPU_INT32 = 4, DFGPU_INT64 = 5,
        DFGPU_UINT8 = 6, DFGPU_UINT16 = 7, DFGPU_UINT32 = 8, DFGPU_UINT64 = 9,
        DFGPU_FLOAT32 = 10, DFGPU_FLOAT64 = 11, DFGPU_DATE32 = 12, DFGPU_DECIMAL128 = 13,
-       DFGPU_UTF8 = 14, DFGPU_DICTIONARY = 15 };
+       DFGPU_UTF8 = 14, DFGPU_DICTIONARY = 15,
+       DFGPU_TIMESTAMP_SECOND = 16, DFGPU_TIMESTAMP_MILLISECOND = 17, DFGPU_TIMESTAMP_MICROSECOND = 18, DFGPU_TIMESTAMP_NANOSECOND = 19 };
+/* Timestamp(unit, None): 8-byte signed counts since the Unix epoch, as Arrow lays them out (C formats "tss:", "tsm:", "tsu:", "tsn:").  No time zone: a
+ * format with a non-empty zone ("tsu:UTC") is DFGPU_NOT_IMPLEMENTED at import, like every other unsupported format.  The bytes are an Int64 column's and
+ * create_hashes hashes a timestamp as its i64, so every operator that takes an Int64 column takes a Timestamp column and computes what it computes over the
+ * same buffer typed Int64 -- comparisons (column / column and column / scalar OF THE SAME UNIT; two units are two types and "the planner coerces first"), IN
+ * lists, IS NULL, CASE values, take / filter / concat / slice, sort keys and payloads, group keys, join keys and the fused probe predicate, hash and
+ * round-robin partitioning and the exchange, MIN / MAX / COUNT / COUNT(DISTINCT), sort-merge and nested-loop join keys, the spill paths -- and output columns
+ * carry the Timestamp type.  Not supported: arithmetic on timestamps (ts - ts, ts + interval need Duration / Interval types: DFGPU_NOT_IMPLEMENTED), SUM and
+ * AVG over a Timestamp (refused, as in the reference), Utf8 <-> Timestamp casts, Parquet and CSV timestamp columns, Date64 / Time32 / Time64.
+ * dfgpu_cast (arrow-cast 50 with safe = false, as CastExpr calls it; that crate is not part of the reference tree, so where a .slt file of the tree pins a
+ * cast result the .slt wins):
+ *   Int64 <-> Timestamp(any unit)           the values unchanged; a plain column shares its buffers
+ *   Timestamp(a) -> finer Timestamp(b)      checked multiply; an overflow on a valid row inside the row selection is DFGPU_EXECUTION (arithmetic overflow)
+ *   Timestamp(a) -> coarser Timestamp(b)    integer division truncating TOWARD ZERO (the crate's `/`): -1500 ms -> -1 s
+ *   Date32 -> Timestamp(unit)               days x 86400 x units per second, a checked multiply: microseconds (beyond day 106751991) and nanoseconds (beyond day 106751) can overflow (DFGPU_EXECUTION)
+ *   Timestamp(unit) -> Date32               value / (units per day), toward zero, then narrowed to Int32 (`as i32`)
+ * to_timestamp_seconds / _millis / _micros / _nanos(Int64) are these casts. */
 
 /* Plain description of an Arrow column (host or device pointers, bit offset 0). */
 typedef struct dfgpu_array_desc {
@@ -313,7 +330,7 @@ DFGPU_API dfgpu_status dfgpu_like(dfgpu_ctx *ctx, const dfgpu_array *values, con
                                   int32_t case_insensitive, dfgpu_array **out);
 /* ScalarFunctionExpr (scalar_function.rs, functions.rs): the built-in functions below, row-wise.  arg_is_scalar[k]: args[k] is a length-1 array that stands
  * for every row; the result has the row count of the other arguments, or length 1 when every argument is a scalar.  A NULL in any argument of a row makes
- * that row NULL.  A Utf8 or Date32 argument may be a dictionary.  When it is the only column, has fewer entries than rows and no row can raise, the function
+ * that row NULL.  A Utf8, Date32 or Timestamp argument may be a dictionary.  When it is the only column, has fewer entries than rows and no row can raise, the function
  * is evaluated once per dictionary entry: a Utf8 result is a dictionary over the same codes (entries may repeat), any other result is gathered through the
  * codes.  Otherwise the dictionary is decoded first and the result is plain.
  *   DATE_PART         (Utf8 scalar part, Date32) -> Float64   year, quarter, month, week (ISO-8601), day, doy (1-based), dow (days from Sunday), hour (0),
@@ -321,6 +338,25 @@ DFGPU_API dfgpu_status dfgpu_like(dfgpu_ctx *ctx, const dfgpu_array *values, con
  *                                                             microsecond, nanosecond: DFGPU_NOT_IMPLEMENTED; any other name: DFGPU_EXECUTION "Date part
  *                                                             '<name>' not supported".  Proleptic Gregorian calendar in 64-bit arithmetic: no Int32 day count
  *                                                             faults; outside 0001-01-01 .. 9999-12-31 the value is what that arithmetic gives.
+ *   DATE_PART         (Utf8 scalar part, Timestamp of any unit) -> Float64   all fourteen parts.  The instant is split with FLOOR semantics (div_euclid /
+ *                                                             rem_euclid) into day number, second of the day and nanosecond of the second: year .. dow from
+ *                                                             the day number as for Date32, hour and minute from the second of the day, second =
+ *                                                             (double)second_of_minute + (double)nanos / 1e9, millisecond / microsecond / nanosecond = that
+ *                                                             value * 1e3 / 1e6 / 1e9, epoch = (double)value / units per second -- evaluated in that order
+ *                                                             without fused multiply-add or reciprocals, so bit-identical to IEEE double evaluation.
+ *                                                             Years outside 1..9999 are unpinned and do not fault.
+ *   DATE_TRUNC        (Utf8 scalar granularity, Timestamp column or scalar) -> Timestamp of the same unit.  Exactly two arguments.  year, quarter, month,
+ *                                                             week (to Monday), day, hour, minute, second: FLOOR to the period.  millisecond, microsecond:
+ *                                                             the reference's integer division, which truncates TOWARD ZERO -- -1500 us at 'millisecond'
+ *                                                             is -1000 us, while -1500 ms at 'second' is -2000 ms.  A granularity as fine as the unit or
+ *                                                             finer is the identity.  Names match case-insensitively; any other name: DFGPU_EXECUTION
+ *                                                             "Unsupported date_trunc granularity: <name>"; a NULL or per-row granularity: DFGPU_EXECUTION
+ *                                                             "Granularity of `date_trunc` must be non-null scalar Utf8".  The reference computes in
+ *                                                             nanoseconds, so it is defined only where the instant and its truncation fit an Int64 of
+ *                                                             nanoseconds (1677-09-21T00:12:43.145224192 .. 2262-04-11T23:47:16.854775807); the arithmetic
+ *                                                             here stays in the column's unit, and a valid row inside the row selection whose input or
+ *                                                             result lies outside that window is DFGPU_EXECUTION "Timestamp <v> out of range" (<v>: one of the offending instants).  A dictionary
+ *                                                             argument is decoded first: errors belong to rows, not entries.
  *   CHARACTER_LENGTH  (Utf8) -> Int32                         code points
  *   SUBSTR            (Utf8, Int64 start [, Int64 count]) -> Utf8   positions count code points from 1.  Two arguments: start <= 0 is the whole string.  Three:
  *                                                             skip max(0, start - 1), take max(0, count + (start < 1 ? start - 1 : 0)); a count < 0 on a row
@@ -329,7 +365,7 @@ DFGPU_API dfgpu_status dfgpu_like(dfgpu_ctx *ctx, const dfgpu_array *values, con
  *   LEFT / RIGHT      (Utf8, Int64 n) -> Utf8                 the first / last n code points; n < 0: all but the last / first |n|; n = 0: ''
  *   STARTS_WITH       (Utf8, Utf8) -> Boolean                 byte prefix
  * Huge |start|, |count|, |n| saturate.  Any other function, argument count or argument type (the planner coerces first) is DFGPU_NOT_IMPLEMENTED. */
-enum { DFGPU_FN_DATE_PART = 1, DFGPU_FN_CHARACTER_LENGTH = 2, DFGPU_FN_SUBSTR = 3, DFGPU_FN_LEFT = 4, DFGPU_FN_RIGHT = 5, DFGPU_FN_STARTS_WITH = 6 };
+enum { DFGPU_FN_DATE_PART = 1, DFGPU_FN_CHARACTER_LENGTH = 2, DFGPU_FN_SUBSTR = 3, DFGPU_FN_LEFT = 4, DFGPU_FN_RIGHT = 5, DFGPU_FN_STARTS_WITH = 6, DFGPU_FN_DATE_TRUNC = 7 };
 DFGPU_API dfgpu_status dfgpu_scalar_function(dfgpu_ctx *ctx, int32_t fn, const dfgpu_array *const *args, const int32_t *arg_is_scalar, int32_t nargs,
                                              dfgpu_array **out);
 
@@ -370,8 +406,8 @@ DFGPU_API dfgpu_status dfgpu_join_probe_selection(dfgpu_ctx *ctx, const dfgpu_jo
  * evaluated inside the probe's own pass over the keys, so no predicate bitmap is written or read.  out_form picks the answer: DFGPU_PROBE_PAIRS == dfgpu_join_probe
  * (out_build_idx, out_probe_idx), DFGPU_PROBE_DEFERRED == dfgpu_join_probe_deferred (same two), DFGPU_PROBE_SELECTION == dfgpu_join_probe_selection (out_selection); the outputs
  * of the other forms are not touched.  The answer is exactly that of the unfused call with opt_mask AND-ed with dfgpu_binary(pred_op, pred_column, pred_scalar).
- * Taken only when the table has (or builds on this call) a membership bitmap the probe column can use -- one Int32 / Date32 / Int64 key column of the build key's type without
- * validity -- and the predicate is one the kernel is instantiated for: pred_op DFGPU_OP_EQ .. DFGPU_OP_GTEQ, pred_column Int32 / Date32 / Int64 without validity and as long as
+ * Taken only when the table has (or builds on this call) a membership bitmap the probe column can use -- one Int32 / Date32 / Int64 / Timestamp key column of the build key's type without
+ * validity -- and the predicate is one the kernel is instantiated for: pred_op DFGPU_OP_EQ .. DFGPU_OP_GTEQ, pred_column Int32 / Date32 / Int64 / Timestamp without validity and as long as
  * the keys, pred_scalar a non-NULL scalar (length 1) of pred_column's type.  Anything else -- hash and partitioned tables, narrow or nullable keys, a selection form the table
  * cannot give -- answers DFGPU_NOT_IMPLEMENTED before launching anything, and the caller evaluates the predicate into opt_mask and probes the ordinary way. */
 enum { DFGPU_PROBE_PAIRS = 0, DFGPU_PROBE_DEFERRED = 1, DFGPU_PROBE_SELECTION = 2 };

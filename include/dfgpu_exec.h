@@ -59,7 +59,8 @@ DFGPU_API dfgpu_status dfgpu_expr_case(const dfgpu_expr *base, const dfgpu_expr 
  * other pattern expression is evaluated to a column and parsed per row. */
 DFGPU_API dfgpu_status dfgpu_expr_like(const dfgpu_expr *expr, const dfgpu_expr *pattern, int32_t negated, int32_t case_insensitive, dfgpu_expr **out);
 /* ScalarFunctionExpr (scalar_function.rs): fn is a DFGPU_FN_* of dfgpu_scalar_function, over 1 to 3 argument expressions.  Literal arguments stay scalars.
- * It can raise per row only as a three-argument SUBSTR whose count is not a NULL or non-negative literal; CASE short-circuits around that.  A function or an
+ * It can raise per row as a three-argument SUBSTR whose count is not a NULL or non-negative literal, and as DATE_TRUNC (a row outside the nanosecond window);
+ * CASE short-circuits around both.  A function or an
  * argument count outside that table is DFGPU_NOT_IMPLEMENTED here, when the expression is built. */
 DFGPU_API dfgpu_status dfgpu_expr_scalar_function(int32_t fn, const dfgpu_expr *const *args, int32_t nargs, dfgpu_expr **out);
 DFGPU_API void dfgpu_expr_free(dfgpu_expr *e);

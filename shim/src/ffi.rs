@@ -22,6 +22,9 @@ pub struct dfgpu_comm_vtable {
 pub const OP_ADD: i32 = 0; pub const OP_SUB: i32 = 1; pub const OP_MUL: i32 = 2; pub const OP_DIV: i32 = 3; pub const OP_REM: i32 = 4;
 pub const OP_EQ: i32 = 10; pub const OP_NEQ: i32 = 11; pub const OP_LT: i32 = 12; pub const OP_LTEQ: i32 = 13; pub const OP_GT: i32 = 14; pub const OP_GTEQ: i32 = 15;
 pub const OP_DISTINCT: i32 = 16; pub const OP_NOT_DISTINCT: i32 = 17; pub const OP_AND: i32 = 20; pub const OP_OR: i32 = 21;
+// Timestamp type codes and DFGPU_FN_DATE_TRUNC (include/dfgpu.h): 8-byte signed counts since the Unix epoch, no time zone
+pub const DFGPU_TIMESTAMP_SECOND: i32 = 16; pub const DFGPU_TIMESTAMP_MILLISECOND: i32 = 17; pub const DFGPU_TIMESTAMP_MICROSECOND: i32 = 18; pub const DFGPU_TIMESTAMP_NANOSECOND: i32 = 19;
+pub const DFGPU_FN_DATE_TRUNC: i32 = 7;
 // DFGPU_AGG_*
 pub const AGG_SUM: i32 = 0; pub const AGG_AVG: i32 = 1; pub const AGG_COUNT: i32 = 2; pub const AGG_MIN: i32 = 3; pub const AGG_MAX: i32 = 4;
 
@@ -85,7 +88,7 @@ extern "C" {
     pub fn dfgpu_expr_is_null(e: *const dfgpu_expr, negated: i32, out: *mut *mut dfgpu_expr) -> i32;
     pub fn dfgpu_expr_negative(e: *const dfgpu_expr, out: *mut *mut dfgpu_expr) -> i32;
     pub fn dfgpu_expr_cast(e: *const dfgpu_expr, to_type: i32, precision: i32, scale: i32, out: *mut *mut dfgpu_expr) -> i32;
-    /// ScalarFunctionExpr: fn_ is a DFGPU_FN_* (1 date_part, 2 character_length, 3 substr, 4 left, 5 right, 6 starts_with); literal arguments stay scalars.
+    /// ScalarFunctionExpr: fn_ is a DFGPU_FN_* (1 date_part, 2 character_length, 3 substr, 4 left, 5 right, 6 starts_with, 7 date_trunc); literal arguments stay scalars.
     pub fn dfgpu_expr_scalar_function(fn_: i32, args: *const *const dfgpu_expr, nargs: i32, out: *mut *mut dfgpu_expr) -> i32;
     pub fn dfgpu_expr_free(e: *mut dfgpu_expr);
     pub fn dfgpu_plan_memory(batches: *const *const dfgpu_batch, partition_sizes: *const i32, npartitions: i32, out: *mut *mut dfgpu_plan) -> i32;
