@@ -79,12 +79,17 @@ struct Composed { ArrayRef inner, outer, out; };
 struct TakeMemo { std::map<std::pair<const dfgpu_array*, const dfgpu_array*>, Composed> composed; };
 using MemoPtr = std::shared_ptr<TakeMemo>;
 static ArrayRef take(const TaskContext& tc, const ArrayRef& v, const ArrayRef& idx) { dfgpu_array* o = nullptr; tc.check(dfgpu_take(tc.ctx, v.a, idx.a, &o)); return ArrayRef::adopt(o); }
+static ArrayRef filter_idx(const TaskContext& tc, const ArrayRef& idx, const ArrayRef& mask) { dfgpu_array* o = nullptr; tc.check(dfgpu_filter(tc.ctx, idx.a, mask.a, &o)); return ArrayRef::adopt(o); }
+static ArrayRef slice(const TaskContext& tc, const ArrayRef& a, int64_t off, int64_t len) { dfgpu_array* o = nullptr; tc.check(dfgpu_array_slice(tc.ctx, a.a, off, len, &o)); return ArrayRef::adopt(o); }
+static ArrayRef cast_to(const TaskContext& tc, const ArrayRef& a, int32_t type) { dfgpu_array* o = nullptr; tc.check(dfgpu_cast(tc.ctx, a.a, type, 0, 0, &o)); return ArrayRef::adopt(o); }
 // n host values as a device array: a literal (n == 1), a row list, or the empty array (n == 0, `v` is not read: the descriptor wants a non-null `values` even then
 // and points at itself)
 static ArrayRef host_array(const TaskContext& tc, int32_t type, const void* v, int64_t n) {
   dfgpu_array_desc d{}; d.type = type; d.length = n; d.values = n ? v : &d;
   dfgpu_array* a = nullptr; tc.check(dfgpu_array_import_host(tc.ctx, &d, &a)); return ArrayRef::adopt(a);
 }
+// n NULLs of a type: the rows of an outer join's absent side, or row indices a gather turns into NULL rows
+static ArrayRef null_array(const TaskContext& tc, int32_t type, int32_t precision, int32_t scale, int64_t n) { dfgpu_array* a = nullptr; tc.check(dfgpu_array_new_null(tc.ctx, type, precision, scale, n, &a)); return ArrayRef::adopt(a); }
 static ArrayRef host_u32(const TaskContext& tc, const uint32_t* v, int64_t n) { return host_array(tc, DFGPU_UINT32, v, n); }
 static ArrayRef host_u64(const TaskContext& tc, const uint64_t* v, int64_t n) { return host_array(tc, DFGPU_UINT64, v, n); }
 // The innermost stage of a pending gather can be a join's build-row lookup that has not run yet (dfgpu_join_probe_deferred): the chain then indexes the join's matched
@@ -101,7 +106,7 @@ struct LazyLookup {
     ArrayRef sel = rows;
     if (idx) {
       ArrayRef i32 = idx; dfgpu_array_desc d; dfgpu_array_describe(idx.a, &d);
-      if (d.type != DFGPU_UINT32) { dfgpu_array* c = nullptr; tc.check(dfgpu_cast(tc.ctx, idx.a, DFGPU_UINT32, 0, 0, &c)); i32 = ArrayRef::adopt(c); }
+      if (d.type != DFGPU_UINT32) i32 = cast_to(tc, idx, DFGPU_UINT32);
       sel = dfgpu_array_is_identity(rows.a) ? i32 : take(tc, rows, i32);
     }
     const dfgpu_array* kp = probe_key.a; dfgpu_array* b = nullptr; tc.check(dfgpu_join_lookup(tc.ctx, table, &kp, 1, sel.a, &b)); ArrayRef out = ArrayRef::adopt(b);
@@ -634,7 +639,7 @@ static Batch materialize_subset(const TaskContext& tc, Batch& b, const std::set<
   ArrayRef filler; MemoPtr memo = std::make_shared<TakeMemo>();
   for (size_t i = 0; i < b.cols.size(); i++) {
     if (needed.count((int)i)) o.cols.push_back(col_take(b.cols[i], sel, memo));
-    else { if (!filler) { dfgpu_array* f = nullptr; tc.check(dfgpu_array_new_null(tc.ctx, DFGPU_INT8, 0, 0, o.base_rows, &f)); filler = ArrayRef::adopt(f); } o.cols.push_back(col_of(filler)); }
+    else { if (!filler) filler = null_array(tc, DFGPU_INT8, 0, 0, o.base_rows); o.cols.push_back(col_of(filler)); }
   }
   return o;
 }
@@ -739,6 +744,11 @@ struct CoalescePartitionsExec : Plan {   // coalesce_partitions.rs
   }
 };
 
+struct Keys { std::vector<ArrayRef> arr; std::vector<const dfgpu_array*> ptr; };      // key columns as the C ABI takes them: ptr[i] = arr[i].a
+static Keys eval_keys(const TaskContext& tc, const std::vector<ExprPtr>& exprs, Batch& b) {
+  Keys k; for (auto& e : exprs) { k.arr.push_back(into_array(tc, e->eval(tc, b), b.base_rows)); k.ptr.push_back(k.arr.back().a); }
+  return k;
+}
 // ≙ BatchPartitioner::partition_iter for Partitioning::Hash (repartition/mod.rs:148-221); honours a fused selection
 static void partition_batch(const TaskContext& tc, Batch& b, const std::vector<ExprPtr>& exprs, int n, std::vector<std::vector<Batch>>& outs) {
   if (b.base_rows == 0) return;
@@ -749,22 +759,20 @@ static void partition_batch(const TaskContext& tc, Batch& b, const std::vector<E
     // through the grouped row numbers
     const ArrayRef bsel = b.selection(tc);
     Batch kb = b; kb.set_selection(ArrayRef());
-    std::vector<ArrayRef> keys; std::vector<const dfgpu_array*> kp;
-    for (auto& e : exprs) { keys.push_back(into_array(tc, e->eval(tc, kb), kb.base_rows)); kp.push_back(keys.back().a); }
+    Keys keys = eval_keys(tc, exprs, kb);
     std::vector<const dfgpu_array*> cp; for (auto& c : b.cols) cp.push_back(c.arr ? c.arr.a : nullptr);
     std::vector<dfgpu_array*> oc(b.cols.size(), nullptr); std::vector<int64_t> counts((size_t)n); dfgpu_array* idx = nullptr;
-    tc.check(dfgpu_partition_columns(tc.ctx, kp.data(), (int32_t)kp.size(), n, cp.data(), (int32_t)cp.size(), bsel.a, oc.data(), &idx, counts.data()));
+    tc.check(dfgpu_partition_columns(tc.ctx, keys.ptr.data(), (int32_t)keys.ptr.size(), n,cp.data(), (int32_t)cp.size(), bsel.a, oc.data(), &idx, counts.data()));
     ArrayRef indices = ArrayRef::adopt(idx); std::vector<ArrayRef> moved; for (auto* x : oc) moved.push_back(ArrayRef::adopt(x));
     int64_t off = 0;
     for (int d = 0; d < n; d++) {
       const int64_t cnt = counts[(size_t)d];
       if (cnt) {
-        auto slice = [&](const ArrayRef& a) { dfgpu_array* s = nullptr; tc.check(dfgpu_array_slice(tc.ctx, a.a, off, cnt, &s)); return ArrayRef::adopt(s); };
         ArrayRef rows;
         Batch o; o.schema = b.schema; o.base_rows = cnt; MemoPtr memo = std::make_shared<TakeMemo>();
         for (size_t c = 0; c < b.cols.size(); c++) {
-          if (moved[c]) o.cols.push_back(col_of(slice(moved[c])));
-          else { if (!rows) rows = slice(indices); o.cols.push_back(col_take(b.cols[c], rows, memo)); }
+          if (moved[c]) o.cols.push_back(col_of(slice(tc, moved[c], off, cnt)));
+          else { if (!rows) rows = slice(tc, indices, off, cnt); o.cols.push_back(col_take(b.cols[c], rows, memo)); }
         }
         outs[(size_t)d].push_back(std::move(o));
       }
@@ -775,14 +783,13 @@ static void partition_batch(const TaskContext& tc, Batch& b, const std::vector<E
   ArrayRef sel; Batch kb = b;
   if (b.filtered()) { std::set<int> need; for (auto& e : exprs) e->columns(need); sel = mask_indices(tc, b.selection(tc)); kb = materialize_subset(tc, b, need); }
   if (kb.base_rows == 0) return;
-  std::vector<ArrayRef> keys; std::vector<const dfgpu_array*> kp;
-  for (auto& e : exprs) { keys.push_back(into_array(tc, e->eval(tc, kb), kb.base_rows)); kp.push_back(keys.back().a); }
+  Keys keys = eval_keys(tc, exprs, kb);
   std::vector<int64_t> counts((size_t)n); dfgpu_array* idx = nullptr;
-  tc.check(dfgpu_hash_partition(tc.ctx, kp.data(), (int32_t)kp.size(), n, &idx, counts.data()));
+  tc.check(dfgpu_hash_partition(tc.ctx, keys.ptr.data(), (int32_t)keys.ptr.size(), n, &idx, counts.data()));
   ArrayRef indices = ArrayRef::adopt(idx); int64_t off = 0;
   for (int d = 0; d < n; d++) {
     if (counts[(size_t)d]) {
-      dfgpu_array* s = nullptr; tc.check(dfgpu_array_slice(tc.ctx, indices.a, off, counts[(size_t)d], &s)); ArrayRef part = ArrayRef::adopt(s);
+      ArrayRef part = slice(tc, indices, off, counts[(size_t)d]);
       ArrayRef rows = sel ? take(tc, sel, part) : part;
       Batch o; o.schema = b.schema; o.base_rows = counts[(size_t)d];
       MemoPtr memo = std::make_shared<TakeMemo>(); for (auto& c : b.cols) o.cols.push_back(col_take(c, rows, memo));
@@ -819,32 +826,76 @@ struct RepartitionExec : Plan {   // repartition/mod.rs:232-294; all inputs are 
   }
 };
 
+// ------------------------------------------------------------------ joins: what the three operators share
+static bool left_only(int jt) { return jt == DFGPU_JOIN_LEFT_SEMI || jt == DFGPU_JOIN_LEFT_ANTI; }
+static bool right_only(int jt) { return jt == DFGPU_JOIN_RIGHT_SEMI || jt == DFGPU_JOIN_RIGHT_ANTI; }
+static SchemaPtr join_schema(const PlanPtr& left, const PlanPtr& right, int jt) {       // build_join_schema (joins/utils.rs:657-729)
+  auto s = std::make_shared<Schema>(); auto l = left->schema(), r = right->schema();
+  if (!right_only(jt) && l) s->f.insert(s->f.end(), l->f.begin(), l->f.end());
+  if (!left_only(jt) && r) s->f.insert(s->f.end(), r->f.begin(), r->f.end());
+  return s;
+}
+// `rows` NULL rows of the schema's columns: the absent side of an outer join's rows
+static void push_null_cols(const TaskContext& tc, const SchemaPtr& s, int64_t rows, std::vector<Col>& out) {
+  if (s) for (auto& f : s->f) out.push_back(col_of(null_array(tc, f.type, f.precision, f.scale, rows)));
+}
+// what stands for an input without a single batch: typed empty columns, so that outer joins still null-pad it
+static Batch empty_batch(const TaskContext& tc, const PlanPtr& p) { Batch b; b.schema = p->schema(); push_null_cols(tc, b.schema, 0, b.cols); return b; }
+
+// JoinFilter (joins/utils.rs:531-541): column i of the intermediate batch the expression runs over = column index[i] of side side[i] (0 left, 1 right)
+struct JoinFilter { ExprPtr expr; std::vector<int> side, index; explicit operator bool() const { return (bool)expr; } };
+// The filter over the pairs (li[i], ri[i]) of rows of `left` and `right`, as a mask without NULLs: a NULL result drops the pair like a false one (apply_join_filter_to_indices,
+// joins/utils.rs:1143-1176)
+static ArrayRef join_filter_mask(const TaskContext& tc, const JoinFilter& f, Batch& left, Batch& right, const ArrayRef& li, const ArrayRef& ri) {
+  Batch inter; inter.schema = std::make_shared<Schema>(); inter.base_rows = li.len();
+  for (size_t i = 0; i < f.side.size(); i++) {
+    Col t = col_take((f.side[i] == 0 ? left : right).cols.at((size_t)f.index[i]), f.side[i] == 0 ? li : ri);
+    inter.cols.push_back(col_of(col_get(tc, t))); inter.schema->f.push_back(Field{"x"});
+  }
+  return known_mask(tc, into_array(tc, f.expr->eval(tc, inter), inter.base_rows));
+}
+static void filter_pairs(const TaskContext& tc, const JoinFilter& f, Batch& left, Batch& right, ArrayRef& li, ArrayRef& ri) {      // keeps the pairs that pass; no filter keeps all
+  if (!f || !li.len()) return;
+  ArrayRef m = join_filter_mask(tc, f, left, right, li, ri); li = filter_idx(tc, li, m); ri = filter_idx(tc, ri, m);
+}
+
+// adjust_indices_by_join_type (joins/utils.rs:1234-1279) over the probe rows [r0, r1).  The index algebra is the hash join's, whose probe side is the right input: b indexes the
+// other side (UInt64), p the probe side (UInt32), and `as_type` names the join with the probe side on the right.
+struct IndexPair { ArrayRef b, p; };
+static IndexPair adjust_indices(const TaskContext& tc, const ArrayRef& b, const ArrayRef& p, int64_t r0, int64_t r1, int as_type) {
+  dfgpu_array *b2 = nullptr, *p2 = nullptr; tc.check(dfgpu_join_adjust_indices(tc.ctx, b.a, p.a, r0, r1, as_type, &b2, &p2));
+  return IndexPair{ArrayRef::adopt(b2), ArrayRef::adopt(p2)};
+}
+// a join type as seen from the side that plays the probe side (the hash join's right input, the sort-merge join's streamed side, the nested-loop join's outer side), as
+// adjust_indices takes it: that side's rows padded (Left / Right / Full -- the other half of a Full join is its operator's last batch), kept if matched, kept if unmatched
+static int as_probe_side(int jt) {
+  switch (jt) {
+    case DFGPU_JOIN_LEFT: case DFGPU_JOIN_RIGHT: case DFGPU_JOIN_FULL: return DFGPU_JOIN_RIGHT;
+    case DFGPU_JOIN_LEFT_SEMI: case DFGPU_JOIN_RIGHT_SEMI: return DFGPU_JOIN_RIGHT_SEMI;
+    case DFGPU_JOIN_LEFT_ANTI: case DFGPU_JOIN_RIGHT_ANTI: return DFGPU_JOIN_RIGHT_ANTI;
+    default: return DFGPU_JOIN_INNER;
+  }
+}
+
 // ------------------------------------------------------------------ HashJoinExec
 struct JoinTableRef { dfgpu_join_table* t = nullptr; ~JoinTableRef() { if (t) dfgpu_join_table_free(t); } };
 struct BuildSide { Batch batch; std::shared_ptr<JoinTableRef> table; std::vector<int64_t> segments; bool empty = true; };
 
 struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
-  PlanPtr left, right; std::vector<ExprPtr> on_l, on_r; ExprPtr filter; std::vector<int> f_side, f_index;
+  PlanPtr left, right; std::vector<ExprPtr> on_l, on_r; JoinFilter filter;
   int join_type, mode; bool null_equals_null; bool swap_small_right = true;
   // set by the operator above when it fuses a selection into its own pass (another join's build or probe, a hash repartition): only then may this join answer with the probe
   // batch under a selection (dfgpu_join_probe_selection) instead of index vectors -- an aggregate or a sort above would have to compact it first and gains nothing
   mutable bool selection_consumer = false;
   mutable std::mutex mu; mutable std::shared_ptr<BuildSide> shared;     // CollectLeft: OnceAsync (joins/utils.rs:736-776)
   PlanPtr fresh() const override {
-    auto j = std::make_shared<HashJoinExec>(); j->left = left->fresh(); j->right = right->fresh(); j->on_l = on_l; j->on_r = on_r; j->filter = filter; j->f_side = f_side; j->f_index = f_index;
+    auto j = std::make_shared<HashJoinExec>(); j->left = left->fresh(); j->right = right->fresh(); j->on_l = on_l; j->on_r = on_r; j->filter = filter;
     j->join_type = join_type; j->mode = mode; j->null_equals_null = null_equals_null; j->swap_small_right = swap_small_right; j->selection_consumer = selection_consumer; return j;
   }
   std::vector<std::shared_ptr<const Plan>> children() const override { return {left, right}; }
   const char* name() const override { return "HashJoinExec"; }
   bool swap_allowed(const TaskContext& tc) const { int64_t v = 1; dfgpu_ctx_get_option(tc.ctx, "join_swap_small_semi", &v); return swap_small_right && v != 0; }
-  bool left_only() const { return join_type == DFGPU_JOIN_LEFT_SEMI || join_type == DFGPU_JOIN_LEFT_ANTI; }
-  bool right_only() const { return join_type == DFGPU_JOIN_RIGHT_SEMI || join_type == DFGPU_JOIN_RIGHT_ANTI; }
-  SchemaPtr schema() const override {       // build_join_schema (joins/utils.rs:657-729)
-    auto s = std::make_shared<Schema>(); auto l = left->schema(), r = right->schema();
-    if (!right_only() && l) s->f.insert(s->f.end(), l->f.begin(), l->f.end());
-    if (!left_only() && r) s->f.insert(s->f.end(), r->f.begin(), r->f.end());
-    return s;
-  }
+  SchemaPtr schema() const override { return join_schema(left, right, join_type); }
   int partitions() const override { return right->partitions(); }
   // collect_left_input (hash_join.rs:678-768); the device table indexes the build side in ORIGINAL input order
   std::shared_ptr<BuildSide> collect_left(int partition, const TaskContext& tc, ArrayRef* fused) const {
@@ -861,27 +912,63 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
   }
   void build_table(const std::shared_ptr<BuildSide>& bs, const ArrayRef& fused, const TaskContext& tc) const {
     if (bs->empty) return;
-    std::vector<ArrayRef> keys; std::vector<const dfgpu_array*> kp;
-    for (auto& e : on_l) { keys.push_back(into_array(tc, e->eval(tc, bs->batch), bs->batch.base_rows)); kp.push_back(keys.back().a); }
+    Keys k = eval_keys(tc, on_l, bs->batch);
     bs->table = std::make_shared<JoinTableRef>();
-    tc.check(dfgpu_join_build(tc.ctx, kp.data(), (int32_t)kp.size(), fused.a, null_equals_null ? 1 : 0, &bs->table->t));
+    tc.check(dfgpu_join_build(tc.ctx, k.ptr.data(), (int32_t)k.ptr.size(), fused.a, null_equals_null ? 1 : 0, &bs->table->t));
   }
   std::shared_ptr<BuildSide> collect_build(int partition, const TaskContext& tc) const {
     SpanGuard sp(tc, met.get(), 1);            // build_time (joins/utils.rs:1370): collecting the build input + building the table
     ArrayRef fused; auto bs = collect_left(partition, tc, &fused); build_table(bs, fused, tc); return bs;
   }
   struct S : Stream {
-    const HashJoinExec* op; TaskContext tc; int partition; std::unique_ptr<Stream> probe; std::shared_ptr<BuildSide> bs; Batch swapped; int state = 0;
+    // HashJoinStreamState (hash_join.rs:1003-1015); SwappedResult: the whole answer of a LeftSemi / LeftAnti join that probed with its left side waits to be handed out
+    enum State { WaitBuildSide, ProbeBatches, FinalPass, Done, SwappedResult };
+    const HashJoinExec* op; TaskContext tc; int partition; std::unique_ptr<Stream> probe; std::shared_ptr<BuildSide> bs; Batch swapped; State state = WaitBuildSide;
     // reference-sized probe batches are answered in the reference's output chunks (get_matched_indices_with_limit_offset, joins/utils.rs:284-348;
     // process_probe_batch, hash_join.rs:1238-1343): `batch_size` candidate pairs per emitted batch, index alignment per chunk
-    Batch chunk_pb; ArrayRef chunk_b, chunk_p; int64_t chunk_k = -1, chunk_total = 0, chunk_joined = -1; std::vector<uint32_t> chunk_last;     // chunk_last: without a JoinFilter, every chunk's last joined probe row (one read-back per probe batch)   // 0 WaitBuildSide, 1 probing, 2 final pass, 3 done, 4 swapped semi/anti result pending
+    Batch chunk_pb; ArrayRef chunk_b, chunk_p; int64_t chunk_k = -1, chunk_total = 0, chunk_joined = -1;
+    std::vector<uint32_t> chunk_last;     // without a JoinFilter, every chunk's last joined probe row (one read-back per probe batch)
     SchemaPtr out_schema;
+    const bool need_final;                // need_produce_result_in_final: the build rows' turn comes after the last probe batch
     bool lazy_build_rows = true, selection_output = true;
-    S(const HashJoinExec* o, int p, TaskContext t) : op(o), tc(t), partition(p) { int64_t v = 1; if (dfgpu_ctx_get_option(tc.ctx, "join_lazy_build_rows", &v) == DFGPU_OK) lazy_build_rows = v != 0;
+    S(const HashJoinExec* o, int p, TaskContext t) : op(o), tc(t), partition(p), need_final(o->join_type == DFGPU_JOIN_LEFT || o->join_type == DFGPU_JOIN_FULL || left_only(o->join_type)) {
+      int64_t v = 1; if (dfgpu_ctx_get_option(tc.ctx, "join_lazy_build_rows", &v) == DFGPU_OK) lazy_build_rows = v != 0;
       v = 1; if (dfgpu_ctx_get_option(tc.ctx, "join_selection_output", &v) == DFGPU_OK) selection_output = v != 0; }
+    bool next(Batch& out) override {
+      for (;;) switch (state) {
+        case WaitBuildSide: wait_build_side(); break;
+        case SwappedResult: state = Done; if (swapped.base_rows == 0) return false; out = std::move(swapped); return true;
+        case ProbeBatches: if (probe_batch(out)) return true; break;
+        case FinalPass: state = Done; return final_pass(out);
+        case Done: return false;
+      }
+    }
+    void wait_build_side() {      // WaitBuildSide (hash_join.rs:1149-1193)
+      // CollectLeft shares ONE build side between the probe partitions; the reference gives every stream a visited bitmap of its own
+      // (hash_join.rs:1172-1190), so with several probe partitions each stream would emit unmatched build rows from a partial view.
+      // That plan shape is refused rather than answered differently from either reading.
+      if (need_final && op->mode == 0 && op->right->partitions() > 1)
+        fail(DFGPU_NOT_IMPLEMENTED, "HashJoinExec mode=CollectLeft with %d probe partitions and a join type that emits build rows in a final pass; repartition both sides (Partitioned) or coalesce the probe side", op->right->partitions());
+      state = ProbeBatches;
+      if (left_only(op->join_type) && op->swap_allowed(tc) && (op->mode != 0 || op->right->partitions() == 1)) {
+        // LeftSemi / LeftAnti keep only left rows, in ascending index of the collected left batch, so WHICH side the device table indexes
+        // is not observable: with a right side much smaller than the left (TPC-H Q18: 600 M joined rows IN a few thousand order keys)
+        // the table is built on the right and the collected left batch probes it once.
+        ArrayRef fused; bs = op->collect_left(op->mode == 0 ? -1 : partition, tc, &fused);
+        std::vector<Batch> rin; drain(op->right, partition, tc, rin);
+        Batch rb; bool have_right = concat_batches(tc, rin, &rb) && rb.base_rows > 0;       // selections applied: base_rows is the row count
+        out_schema = op->schema();
+        if (!bs->empty && rb.base_rows * 8 <= bs->batch.base_rows) { swapped = semi_by_probing_left(fused, have_right ? &rb : nullptr); state = SwappedResult; }
+        else { op->build_table(bs, fused, tc); std::vector<Batch> one; if (have_right) one.push_back(std::move(rb)); probe.reset(new VecStream(std::move(one))); }
+        return;
+      }
+      if (op->mode == 0) { std::lock_guard<std::mutex> l(op->mu); if (!op->shared) op->shared = op->collect_build(-1, tc); bs = op->shared; }
+      else bs = op->collect_build(partition, tc);
+      probe = op->right->run(partition, tc); out_schema = op->schema();
+    }
     int64_t last_u32(const ArrayRef& a) {
       int64_t n = a.len(); if (!n) return -1;
-      dfgpu_array* s1 = nullptr; tc.check(dfgpu_array_slice(tc.ctx, a.a, n - 1, 1, &s1)); ArrayRef one = ArrayRef::adopt(s1);
+      ArrayRef one = slice(tc, a, n - 1, 1);
       uint32_t v = 0; tc.check(dfgpu_array_export_host(tc.ctx, one.a, &v, nullptr, nullptr)); return (int64_t)v;
     }
     // The probe row of the last pair of every `bsz`-pair chunk: the reference resumes the next chunk from an in-memory offset (hash_join.rs:1332-1340); here the
@@ -893,41 +980,33 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
       ArrayRef ends = take(tc, pidx, host_u32(tc, pos.data(), (int64_t)pos.size())); chunk_last.resize(pos.size());
       tc.check(dfgpu_array_export_host(tc.ctx, ends.a, chunk_last.data(), nullptr, nullptr));
     }
-    ArrayRef slice_of(const ArrayRef& a, int64_t off, int64_t len) { dfgpu_array* s1 = nullptr; tc.check(dfgpu_array_slice(tc.ctx, a.a, off, len, &s1)); return ArrayRef::adopt(s1); }
-    void apply_filter(Batch& pb, ArrayRef& bidx, ArrayRef& pidx) {      // apply_join_filter_to_indices (joins/utils.rs:1143-1176)
-      if (!op->filter || !bidx.len()) return;
-      Batch inter; inter.schema = std::make_shared<Schema>(); inter.base_rows = bidx.len();
-      for (size_t i = 0; i < op->f_side.size(); i++) {
-        Col src = op->f_side[i] == 0 ? bs->batch.cols.at((size_t)op->f_index[i]) : pb.cols.at((size_t)op->f_index[i]);
-        Col t = col_take(src, op->f_side[i] == 0 ? bidx : pidx); inter.cols.push_back(col_of(col_get(tc, t))); inter.schema->f.push_back(Field{"x"});
-      }
-      ArrayRef m = into_array(tc, op->filter->eval(tc, inter), inter.base_rows);
-      ArrayRef nb = filter_idx(bidx, m), np = filter_idx(pidx, m); bidx = nb; pidx = np;
+    // What the join type makes of the filtered pairs of the probe rows [r0, r1) (adjust_indices_by_join_type, joins/utils.rs:1234-1279): Right / Full / RightSemi / RightAnti
+    // go through the index algebra, LeftSemi / LeftAnti emit nothing before the final pass (false), Inner / Left emit the pairs as they are
+    bool finish_pairs(ArrayRef& b, ArrayRef& p, int64_t r0, int64_t r1) {
+      const int jt = op->join_type;
+      if (left_only(jt)) return false;
+      if (jt == DFGPU_JOIN_RIGHT || jt == DFGPU_JOIN_FULL || right_only(jt)) { IndexPair a = adjust_indices(tc, b, p, r0, r1, as_probe_side(jt)); b = a.b; p = a.p; }
+      return true;
     }
     // one output chunk of the current reference-sized probe batch
-    void emit_chunk(Batch& out, bool need_final) {
+    void emit_chunk(Batch& out) {
       const int64_t bsz = tc.batch_size > 0 ? tc.batch_size : 8192, m = chunk_b.len(), off = chunk_k * bsz;
       const int64_t len = off >= m ? 0 : (m - off < bsz ? m - off : bsz);
       const bool last = chunk_k == chunk_total - 1;
-      ArrayRef b = slice_of(chunk_b, off < m ? off : m, len), p = slice_of(chunk_p, off < m ? off : m, len);
-      apply_filter(chunk_pb, b, p);
+      ArrayRef b = slice(tc, chunk_b, off < m ? off : m, len), p = slice(tc, chunk_p, off < m ? off : m, len);
+      filter_pairs(tc, op->filter, bs->batch, chunk_pb, b, p);
       if (need_final && !bs->empty && b.len()) tc.check(dfgpu_join_mark_visited(tc.ctx, bs->table->t, b.a));
       // counts as joined after the key comparison and the join filter; without a filter the chunk's last pair is known since the probe (chunk_last_rows)
       const int64_t last_joined = op->filter ? last_u32(p) : (len > 0 ? (int64_t)chunk_last[(size_t)chunk_k] : -1);
       const int64_t r0 = chunk_joined + 1, r1 = last ? chunk_pb.base_rows : (last_joined >= 0 ? last_joined + 1 : 0);
       if (!last && last_joined >= 0) chunk_joined = last_joined;
-      const int jt = op->join_type;
-      if (jt == DFGPU_JOIN_RIGHT || jt == DFGPU_JOIN_FULL || op->right_only()) {
-        dfgpu_array *b2 = nullptr, *p2 = nullptr;
-        tc.check(dfgpu_join_adjust_indices(tc.ctx, b.a, p.a, r0, r1, jt, &b2, &p2)); b = ArrayRef::adopt(b2); p = ArrayRef::adopt(p2);
-      } else if (op->left_only()) { b = slice_of(b, 0, 0); p = slice_of(p, 0, 0); }
+      if (!finish_pairs(b, p, r0, r1)) { b = slice(tc, b, 0, 0); p = slice(tc, p, 0, 0); }         // a chunk is a batch of the stream even when it is empty
       out = build_batch(bs->empty ? nullptr : &bs->batch, chunk_pb, b, p);
       if (last) { chunk_k = -1; chunk_pb = Batch(); chunk_b = ArrayRef(); chunk_p = ArrayRef(); } else chunk_k++;
     }
-    ArrayRef filter_idx(const ArrayRef& idx, const ArrayRef& m) { dfgpu_array* o = nullptr; tc.check(dfgpu_filter(tc.ctx, idx.a, m.a, &o)); return ArrayRef::adopt(o); }
     std::vector<int> key_aliases(Batch* build, Batch& probe_b) {      // build column -> the probe column that holds the same values in every output row, or -1
       auto lf = op->left->schema(); std::vector<int> alias(lf ? lf->f.size() : 0, -1);
-      if (build && op->join_type == DFGPU_JOIN_INNER && !op->null_equals_null && !op->right_only() && !op->left_only())
+      if (build && op->join_type == DFGPU_JOIN_INNER && !op->null_equals_null)
         for (size_t k = 0; k < op->on_l.size(); k++) {
           const int bi = op->on_l[k]->column_index(), pi = op->on_r[k]->column_index();
           if (bi < 0 || pi < 0 || bi >= (int)build->cols.size() || pi >= (int)probe_b.cols.size() || bi >= (int)alias.size()) continue;
@@ -946,171 +1025,134 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
       // from the probe column through pidx (ascending 32-bit indices; the column itself when every probe row matched once) instead of through bidx (a random 8-byte gather
       // from the build batch).  TPC-H Q18 joins 600 M lineitems to their orders and then feeds o_orderkey into the next join: that column is l_orderkey, untouched.
       std::vector<int> alias = key_aliases(build, probe_b);
-      if (!op->right_only()) for (size_t i = 0; i < (lf ? lf->f.size() : 0); i++) {
-        if (build && alias[i] >= 0) o.cols.push_back(col_take(probe_b.cols[(size_t)alias[i]], pidx, memo));
-        else if (build && lazy) { Col c; c.source = build->cols[i].arr; c.lookup = lazy; c.memo = memo; o.cols.push_back(std::move(c)); }       // build rows not looked up yet
-        else if (build) o.cols.push_back(col_take(build->cols[i], bidx, memo));
-        else { dfgpu_array* nn = nullptr; tc.check(dfgpu_array_new_null(tc.ctx, lf->f[i].type, lf->f[i].precision, lf->f[i].scale, o.base_rows, &nn)); o.cols.push_back(col_of(ArrayRef::adopt(nn))); }
+      if (!right_only(op->join_type) && !build) push_null_cols(tc, lf, o.base_rows, o.cols);         // an empty build side
+      else if (!right_only(op->join_type)) for (size_t i = 0; i < (lf ? lf->f.size() : 0); i++) {
+        if (alias[i] >= 0) o.cols.push_back(col_take(probe_b.cols[(size_t)alias[i]], pidx, memo));
+        else if (lazy) { Col c; c.source = build->cols[i].arr; c.lookup = lazy; c.memo = memo; o.cols.push_back(std::move(c)); }       // build rows not looked up yet
+        else o.cols.push_back(col_take(build->cols[i], bidx, memo));
       }
-      if (!op->left_only()) for (auto& c : probe_b.cols) o.cols.push_back(col_take(c, pidx, memo));
+      if (!left_only(op->join_type)) for (auto& c : probe_b.cols) o.cols.push_back(col_take(c, pidx, memo));
       return o;
     }
-    bool next(Batch& out) override {
-      if (state == 0) {           // WaitBuildSide (hash_join.rs:1149-1193)
-        if (op->left_only() && op->swap_allowed(tc) && (op->mode != 0 || op->right->partitions() == 1)) {
-          // LeftSemi / LeftAnti keep only left rows, in ascending index of the collected left batch, so WHICH side the device table indexes
-          // is not observable: with a right side much smaller than the left (TPC-H Q18: 600 M joined rows IN a few thousand order keys)
-          // the table is built on the right and the collected left batch probes it once.
-          ArrayRef fused; bs = op->collect_left(op->mode == 0 ? -1 : partition, tc, &fused);
-          std::vector<Batch> rin; drain(op->right, partition, tc, rin);
-          Batch rb; bool have_right = concat_batches(tc, rin, &rb) && rb.base_rows > 0;       // selections applied: base_rows is the row count
-          out_schema = op->schema();
-          if (!bs->empty && rb.base_rows * 8 <= bs->batch.base_rows) { swapped = semi_by_probing_left(fused, have_right ? &rb : nullptr); state = 4; }
-          else { op->build_table(bs, fused, tc); std::vector<Batch> one; if (have_right) one.push_back(std::move(rb)); probe.reset(new VecStream(std::move(one))); state = 1; }
-        }
-        else if (op->mode == 0) { std::lock_guard<std::mutex> l(op->mu); if (!op->shared) op->shared = op->collect_build(-1, tc); bs = op->shared; }
-        else bs = op->collect_build(partition, tc);
-        if (state == 0) { probe = op->right->run(partition, tc); out_schema = op->schema(); state = 1; }
+    // the rows of one probe batch that are probed: its selection bitmap (empty = every row) and the predicate a FilterExec below left pending, if any
+    struct ProbeRows { ArrayRef mask; PendingPredicate pend; int64_t base_rows = 0; };
+    // One probe in the form asked for, with the pending predicate folded in (dfgpu_join_probe_fused).  A table or form that does not take the predicate
+    // (DFGPU_NOT_IMPLEMENTED, nothing launched) gets it evaluated into in.mask -- Batch::selection, the one resolver -- and is probed as before, this route and the next.
+    dfgpu_status probe_as(int form, const Keys& keys, ProbeRows& in, dfgpu_array** ob, dfgpu_array** opi, dfgpu_array** os) {
+      dfgpu_join_table* t = bs->table->t; const dfgpu_array* const* kp = keys.ptr.data(); const int32_t nk = (int32_t)keys.ptr.size();
+      if (in.pend) {
+        dfgpu_status st = dfgpu_join_probe_fused(tc.ctx, t, kp, nk, in.mask.a, in.pend.column.a, in.pend.op, in.pend.scalar.a, form, ob, opi, os);
+        if (st != DFGPU_NOT_IMPLEMENTED) return st;
+        Batch r; r.base_rows = in.base_rows; r.set_selection(in.mask); r.set_pending(in.pend.column, in.pend.op, in.pend.scalar); in.mask = r.selection(tc); in.pend = PendingPredicate();
       }
-      if (state == 4) { state = 3; if (swapped.base_rows == 0) return false; out = std::move(swapped); return true; }
-      bool need_final = op->join_type == DFGPU_JOIN_LEFT || op->join_type == DFGPU_JOIN_FULL || op->left_only();     // need_produce_result_in_final
-      // CollectLeft shares ONE build side between the probe partitions; the reference gives every stream a visited bitmap of its own
-      // (hash_join.rs:1172-1190), so with several probe partitions each stream would emit unmatched build rows from a partial view.
-      // That plan shape is refused rather than answered differently from either reading.
-      if (need_final && op->mode == 0 && op->right->partitions() > 1 && state != 4)
-        fail(DFGPU_NOT_IMPLEMENTED, "HashJoinExec mode=CollectLeft with %d probe partitions and a join type that emits build rows in a final pass; repartition both sides (Partitioned) or coalesce the probe side", op->right->partitions());
-      while (state == 1) {        // FetchProbeBatch / ProcessProbeBatch (:1199-1343)
-        if (chunk_k >= 0) { SpanGuard join_span(tc, op->met.get(), 2); emit_chunk(out, need_final); return true; }
-        Batch pb; if (!probe->next(pb)) { state = 2; break; }
-        if (pb.base_rows == 0) continue;
-        SpanGuard join_span(tc, op->met.get(), 2);        // join_time (joins/utils.rs:1381): probing one batch and building its output
-        // a probe batch of the reference's size (<= max(batch_size, 8192) rows) comes out in the reference's chunks; the device's own
-        // whole-partition batches are answered in one piece (their consumers re-slice to batch_size)
-        const bool chunked = pb.base_rows <= (tc.batch_size > 8192 ? tc.batch_size : 8192);
-        if (chunked && pb.filtered()) { pb = materialize(tc, pb); if (pb.base_rows == 0) continue; }
-        // Right / Full / RightSemi / RightAnti emit the probe rows WITHOUT a match (adjust_indices_by_join_type over the batch's row range,
-        // joins/utils.rs:1234-1279): rows a fused FilterExec dropped must not come back as unmatched rows, so the selection is applied first
-        if (pb.filtered() && (op->join_type == DFGPU_JOIN_RIGHT || op->join_type == DFGPU_JOIN_FULL || op->right_only())) { pb = materialize(tc, pb); if (pb.base_rows == 0) continue; }
-        // a predicate the FilterExec below left pending goes into the probe itself; without a table to probe it is evaluated like anywhere else
-        PendingPredicate pend; ArrayRef mask;
-        if (pb.has_pending() && !bs->empty) mask = pb.take_filter(&pend); else { mask = pb.selection(tc); pb.set_selection(ArrayRef()); }
-        ArrayRef bidx, pidx;
-        if (bs->empty) { bidx = host_u64(tc, nullptr, 0); pidx = host_u32(tc, nullptr, 0); }
-        else {
-          std::vector<ArrayRef> keys; std::vector<const dfgpu_array*> kp;
-          for (auto& e : op->on_r) { keys.push_back(into_array(tc, e->eval(tc, pb), pb.base_rows)); kp.push_back(keys.back().a); }
-          dfgpu_array *b = nullptr, *p = nullptr;
-          // One probe in the form asked for, with the pending predicate folded in (dfgpu_join_probe_fused).  A table or form that does not take the predicate
-          // (DFGPU_NOT_IMPLEMENTED, nothing launched) gets it evaluated into the mask -- Batch::selection, the one resolver -- and is probed as before, this route and the next.
-          auto probe_as = [&](int form, dfgpu_array** ob, dfgpu_array** opi, dfgpu_array** os) -> dfgpu_status {
-            if (pend) {
-              dfgpu_status st = dfgpu_join_probe_fused(tc.ctx, bs->table->t, kp.data(), (int32_t)kp.size(), mask.a, pend.column.a, pend.op, pend.scalar.a, form, ob, opi, os);
-              if (st != DFGPU_NOT_IMPLEMENTED) return st;
-              Batch r; r.base_rows = pb.base_rows; r.set_selection(mask); r.set_pending(pend.column, pend.op, pend.scalar); mask = r.selection(tc); pend = PendingPredicate();
-            }
-            if (form == DFGPU_PROBE_SELECTION) return dfgpu_join_probe_selection(tc.ctx, bs->table->t, kp.data(), (int32_t)kp.size(), mask.a, os);
-            if (form == DFGPU_PROBE_DEFERRED) return dfgpu_join_probe_deferred(tc.ctx, bs->table->t, kp.data(), (int32_t)kp.size(), mask.a, ob, opi);
-            return dfgpu_join_probe(tc.ctx, bs->table->t, kp.data(), (int32_t)kp.size(), mask.a, ob, opi);
-          };
-          // an Inner join whose build rows nothing here needs (no filter, no final pass, one piece): the table may leave them for later (LazyLookup)
-          bool defer = !chunked && op->join_type == DFGPU_JOIN_INNER && !op->filter && !need_final && kp.size() == 1 && lazy_build_rows;
-          // An Inner join over a unique build of which nothing but (aliased) key columns leaves the build side: its output is the probe batch under the selection
-          // "row is selected and finds its key" -- the probe's match bits.  No index vector, no gather, no row count on the host: the consumer fuses the selection
-          // (the next join's build or probe, a repartition, an aggregate) or compacts it when it must.  TPC-H Q3: customer x orders hands the orders table itself,
-          // under a selection, to the build of the join with lineitem.
-          if (defer && selection_output && op->selection_consumer) {
-            std::vector<int> al = key_aliases(&bs->batch, pb); bool all = !al.empty(); for (int a : al) all = all && a >= 0;
-            if (all) {
-              dfgpu_array* s = nullptr; dfgpu_status st = probe_as(DFGPU_PROBE_SELECTION, nullptr, nullptr, &s);
-              if (st == DFGPU_OK) {
-                Batch o; o.schema = out_schema; o.base_rows = pb.base_rows; o.set_selection(ArrayRef::adopt(s));
-                for (int a : al) o.cols.push_back(pb.cols[(size_t)a]);
-                for (auto& c : pb.cols) o.cols.push_back(c);
-                out = std::move(o); return true;
-              }
-              if (st != DFGPU_NOT_IMPLEMENTED) tc.check(st);
-            }
+      if (form == DFGPU_PROBE_SELECTION) return dfgpu_join_probe_selection(tc.ctx, t, kp, nk, in.mask.a, os);
+      if (form == DFGPU_PROBE_DEFERRED) return dfgpu_join_probe_deferred(tc.ctx, t, kp, nk, in.mask.a, ob, opi);
+      return dfgpu_join_probe(tc.ctx, t, kp, nk, in.mask.a, ob, opi);
+    }
+    // The probe of one batch in the cheapest form its consumers allow.  true: `out` is the answer already (the probe batch under a selection, or build rows left for later);
+    // false: the key-matched pairs are in bidx / pidx
+    bool probe_pairs(Batch& pb, const Keys& keys, ProbeRows& in, bool chunked, ArrayRef& bidx, ArrayRef& pidx, Batch& out) {
+      dfgpu_array *b = nullptr, *p = nullptr;
+      // an Inner join whose build rows nothing here needs (no filter, no final pass, one piece): the table may leave them for later (LazyLookup)
+      bool defer = !chunked && op->join_type == DFGPU_JOIN_INNER && !op->filter && !need_final && keys.ptr.size() == 1 && lazy_build_rows;
+      // An Inner join over a unique build of which nothing but (aliased) key columns leaves the build side: its output is the probe batch under the selection
+      // "row is selected and finds its key" -- the probe's match bits.  No index vector, no gather, no row count on the host: the consumer fuses the selection
+      // (the next join's build or probe, a repartition, an aggregate) or compacts it when it must.  TPC-H Q3: customer x orders hands the orders table itself,
+      // under a selection, to the build of the join with lineitem.
+      if (defer && selection_output && op->selection_consumer) {
+        std::vector<int> al = key_aliases(&bs->batch, pb); bool all = !al.empty(); for (int a : al) all = all && a >= 0;
+        if (all) {
+          dfgpu_array* s = nullptr; dfgpu_status st = probe_as(DFGPU_PROBE_SELECTION, keys, in, nullptr, nullptr, &s);
+          if (st == DFGPU_OK) {
+            Batch o; o.schema = out_schema; o.base_rows = pb.base_rows; o.set_selection(ArrayRef::adopt(s));
+            for (int a : al) o.cols.push_back(pb.cols[(size_t)a]);
+            for (auto& c : pb.cols) o.cols.push_back(c);
+            out = std::move(o); return true;
           }
-          for (auto& c : bs->batch.cols) defer = defer && (bool)c.arr;
-          if (defer) {
-            tc.check(probe_as(DFGPU_PROBE_DEFERRED, &b, &p, nullptr)); pidx = ArrayRef::adopt(p);
-            if (!b) {
-              auto lz = std::make_shared<LazyLookup>(); lz->keep = bs; lz->table = bs->table->t; lz->probe_key = keys[0]; lz->rows = pidx; lz->m = pidx.len();
-              // Left for later when that can only win: every probe row matched (the lookup is the big one, and a later operator may thin the rows first -- Q18), or no
-              // build column but aliased key columns leaves this join (nobody will ever ask -- Q3's customer side).  Otherwise now, while keys and bitmap are in cache:
-              // deferring the lookup of a 15 % match cost TPC-H Q5 0.3 ms of 7.2.
-              bool wanted = false; { std::vector<int> al = key_aliases(&bs->batch, pb); for (int a : al) wanted |= a < 0; }
-              if (!wanted || (dfgpu_array_is_identity(pidx.a) && pidx.len() == pb.base_rows)) { out = build_batch(&bs->batch, pb, ArrayRef(), pidx, lz); return true; }
-              bidx = lz->resolve(tc, ArrayRef());
-            } else bidx = ArrayRef::adopt(b);
-          } else { tc.check(probe_as(DFGPU_PROBE_PAIRS, &b, &p, nullptr)); bidx = ArrayRef::adopt(b); pidx = ArrayRef::adopt(p); }
-          if (!chunked) { apply_filter(pb, bidx, pidx); if (need_final) tc.check(dfgpu_join_mark_visited(tc.ctx, bs->table->t, bidx.a)); }
+          if (st != DFGPU_NOT_IMPLEMENTED) tc.check(st);
         }
-        if (chunked) {
-          // chunks of `batch_size` pairs; one more (empty) lookup follows when the limit was hit before the scan reached the end of the batch
-          // (chain_traverse!, joins/utils.rs:147-187: next_offset is None only at the last chain element of the last probe row)
-          const int64_t bsz = tc.batch_size > 0 ? tc.batch_size : 8192, m = bidx.len();
-          chunk_total = m == 0 ? 1 : (m + bsz - 1) / bsz;
-          chunk_last_rows(pidx, bsz);
-          if (m > 0 && m % bsz == 0 && (int64_t)chunk_last.back() != pb.base_rows - 1) chunk_total++;
-          chunk_pb = std::move(pb); chunk_b = bidx; chunk_p = pidx; chunk_k = 0; chunk_joined = -1;
-          continue;
-        }
-        int jt = op->join_type;
-        if (jt == DFGPU_JOIN_RIGHT || jt == DFGPU_JOIN_FULL || op->right_only()) {
-          dfgpu_array *b2 = nullptr, *p2 = nullptr;
-          tc.check(dfgpu_join_adjust_indices(tc.ctx, bidx.a, pidx.a, 0, pb.base_rows, jt, &b2, &p2)); bidx = ArrayRef::adopt(b2); pidx = ArrayRef::adopt(p2);
-        } else if (op->left_only()) continue;
-        out = build_batch(bs->empty ? nullptr : &bs->batch, pb, bidx, pidx); return true;
       }
-      if (state == 2) {           // ExhaustedProbeSide -> process_unmatched_build_batch (:1348-1388)
-        state = 3;
-        if (!need_final || bs->empty) return false;
-        dfgpu_array* f = nullptr; tc.check(dfgpu_join_final_indices(tc.ctx, bs->table->t, op->join_type, &f)); ArrayRef fidx = ArrayRef::adopt(f);
-        fidx = reference_final_order(fidx);
-        Batch o; o.schema = out_schema; o.base_rows = fidx.len();
-        MemoPtr memo = std::make_shared<TakeMemo>(); for (auto& c : bs->batch.cols) o.cols.push_back(col_take(c, fidx, memo));
-        if (!op->left_only()) { auto rf = op->right->schema(); for (auto& fd : rf->f) { dfgpu_array* nn = nullptr; tc.check(dfgpu_array_new_null(tc.ctx, fd.type, fd.precision, fd.scale, o.base_rows, &nn)); o.cols.push_back(col_of(ArrayRef::adopt(nn))); } }
-        out = std::move(o); return true;
+      for (auto& c : bs->batch.cols) defer = defer && (bool)c.arr;
+      if (!defer) { tc.check(probe_as(DFGPU_PROBE_PAIRS, keys, in, &b, &p, nullptr)); bidx = ArrayRef::adopt(b); pidx = ArrayRef::adopt(p); return false; }
+      tc.check(probe_as(DFGPU_PROBE_DEFERRED, keys, in, &b, &p, nullptr)); pidx = ArrayRef::adopt(p);
+      if (b) { bidx = ArrayRef::adopt(b); return false; }
+      auto lz = std::make_shared<LazyLookup>(); lz->keep = bs; lz->table = bs->table->t; lz->probe_key = keys.arr[0]; lz->rows = pidx; lz->m = pidx.len();
+      // Left for later when that can only win: every probe row matched (the lookup is the big one, and a later operator may thin the rows first -- Q18), or no
+      // build column but aliased key columns leaves this join (nobody will ever ask -- Q3's customer side).  Otherwise now, while keys and bitmap are in cache:
+      // deferring the lookup of a 15 % match cost TPC-H Q5 0.3 ms of 7.2.
+      bool wanted = false; { std::vector<int> al = key_aliases(&bs->batch, pb); for (int a : al) wanted |= a < 0; }
+      if (!wanted || (dfgpu_array_is_identity(pidx.a) && pidx.len() == pb.base_rows)) { out = build_batch(&bs->batch, pb, ArrayRef(), pidx, lz); return true; }
+      bidx = lz->resolve(tc, ArrayRef()); return false;
+    }
+    // FetchProbeBatch / ProcessProbeBatch (hash_join.rs:1199-1343): the next chunk of the current probe batch, or the next probe batch.  false: nothing emitted this time
+    bool probe_batch(Batch& out) {
+      if (chunk_k >= 0) { SpanGuard join_span(tc, op->met.get(), 2); emit_chunk(out); return true; }
+      Batch pb; if (!probe->next(pb)) { state = FinalPass; return false; }
+      if (pb.base_rows == 0) return false;
+      SpanGuard join_span(tc, op->met.get(), 2);        // join_time (joins/utils.rs:1381): probing one batch and building its output
+      // a probe batch of the reference's size (<= max(batch_size, 8192) rows) comes out in the reference's chunks; the device's own
+      // whole-partition batches are answered in one piece (their consumers re-slice to batch_size)
+      const bool chunked = pb.base_rows <= (tc.batch_size > 8192 ? tc.batch_size : 8192);
+      if (chunked && pb.filtered()) { pb = materialize(tc, pb); if (pb.base_rows == 0) return false; }
+      // Right / Full / RightSemi / RightAnti emit the probe rows WITHOUT a match (adjust_indices_by_join_type over the batch's row range,
+      // joins/utils.rs:1234-1279): rows a fused FilterExec dropped must not come back as unmatched rows, so the selection is applied first
+      if (pb.filtered() && (op->join_type == DFGPU_JOIN_RIGHT || op->join_type == DFGPU_JOIN_FULL || right_only(op->join_type))) { pb = materialize(tc, pb); if (pb.base_rows == 0) return false; }
+      // a predicate the FilterExec below left pending goes into the probe itself; without a table to probe it is evaluated like anywhere else
+      ProbeRows in; in.base_rows = pb.base_rows;
+      if (pb.has_pending() && !bs->empty) in.mask = pb.take_filter(&in.pend); else { in.mask = pb.selection(tc); pb.set_selection(ArrayRef()); }
+      ArrayRef bidx, pidx;
+      if (bs->empty) { bidx = host_u64(tc, nullptr, 0); pidx = host_u32(tc, nullptr, 0); }
+      else {
+        Keys keys = eval_keys(tc, op->on_r, pb);
+        if (probe_pairs(pb, keys, in, chunked, bidx, pidx, out)) return true;
+        if (!chunked) { filter_pairs(tc, op->filter, bs->batch, pb, bidx, pidx); if (need_final) tc.check(dfgpu_join_mark_visited(tc.ctx, bs->table->t, bidx.a)); }
       }
-      return false;
+      if (chunked) {
+        // chunks of `batch_size` pairs; one more (empty) lookup follows when the limit was hit before the scan reached the end of the batch
+        // (chain_traverse!, joins/utils.rs:147-187: next_offset is None only at the last chain element of the last probe row)
+        const int64_t bsz = tc.batch_size > 0 ? tc.batch_size : 8192, m = bidx.len();
+        chunk_total = m == 0 ? 1 : (m + bsz - 1) / bsz;
+        chunk_last_rows(pidx, bsz);
+        if (m > 0 && m % bsz == 0 && (int64_t)chunk_last.back() != pb.base_rows - 1) chunk_total++;
+        chunk_pb = std::move(pb); chunk_b = bidx; chunk_p = pidx; chunk_k = 0; chunk_joined = -1;
+        return false;
+      }
+      if (!finish_pairs(bidx, pidx, 0, pb.base_rows)) return false;
+      out = build_batch(bs->empty ? nullptr : &bs->batch, pb, bidx, pidx); return true;
+    }
+    bool final_pass(Batch& out) {      // ExhaustedProbeSide -> process_unmatched_build_batch (hash_join.rs:1348-1388)
+      if (!need_final || bs->empty) return false;
+      dfgpu_array* f = nullptr; tc.check(dfgpu_join_final_indices(tc.ctx, bs->table->t, op->join_type, &f)); ArrayRef fidx = ArrayRef::adopt(f);
+      fidx = reference_final_order(fidx);
+      Batch o; o.schema = out_schema; o.base_rows = fidx.len();
+      MemoPtr memo = std::make_shared<TakeMemo>(); for (auto& c : bs->batch.cols) o.cols.push_back(col_take(c, fidx, memo));
+      if (!left_only(op->join_type)) push_null_cols(tc, op->right->schema(), o.base_rows, o.cols);
+      out = std::move(o); return true;
     }
     Batch semi_by_probing_left(ArrayRef fused, Batch* right_rows) {
       Batch o; o.schema = out_schema;
-      const bool have_right = right_rows != nullptr; Batch none; Batch& rb = have_right ? *right_rows : none;
       Batch& lb = bs->batch;
       const bool anti = op->join_type == DFGPU_JOIN_LEFT_ANTI;
       if (anti && fused) {          // the complement below runs over every row of the left batch: apply a fused selection first
         Batch sel = lb; sel.set_selection(fused); lb = materialize(tc, sel); fused = ArrayRef(); bs->segments = { lb.base_rows };
       }
+      if (!right_rows && !anti) return o;
       ArrayRef lidx;
-      if (!have_right) {
-        if (!anti) return o;
-        ArrayRef b0 = host_u64(tc, nullptr, 0), p0 = host_u32(tc, nullptr, 0);
-        dfgpu_array *b2 = nullptr, *p2 = nullptr; tc.check(dfgpu_join_adjust_indices(tc.ctx, b0.a, p0.a, 0, lb.base_rows, DFGPU_JOIN_RIGHT_ANTI, &b2, &p2)); ArrayRef drop = ArrayRef::adopt(b2); lidx = ArrayRef::adopt(p2);
-      } else {
-        std::vector<ArrayRef> rk, lk; std::vector<const dfgpu_array*> rp, lp;
-        for (auto& e : op->on_r) { rk.push_back(into_array(tc, e->eval(tc, rb), rb.base_rows)); rp.push_back(rk.back().a); }
-        JoinTableRef table; tc.check(dfgpu_join_build(tc.ctx, rp.data(), (int32_t)rp.size(), nullptr, op->null_equals_null ? 1 : 0, &table.t));
-        for (auto& e : op->on_l) { lk.push_back(into_array(tc, e->eval(tc, lb), lb.base_rows)); lp.push_back(lk.back().a); }
-        dfgpu_array *b = nullptr, *p = nullptr;
-        tc.check(dfgpu_join_probe(tc.ctx, table.t, lp.data(), (int32_t)lp.size(), fused.a, &b, &p)); ArrayRef ridx = ArrayRef::adopt(b); lidx = ArrayRef::adopt(p);
-        if (op->filter && ridx.len()) {       // the filter's side 0 is still the left input
-          Batch inter; inter.schema = std::make_shared<Schema>(); inter.base_rows = ridx.len();
-          for (size_t i = 0; i < op->f_side.size(); i++) {
-            Col src = op->f_side[i] == 0 ? lb.cols.at((size_t)op->f_index[i]) : rb.cols.at((size_t)op->f_index[i]);
-            Col t = col_take(src, op->f_side[i] == 0 ? lidx : ridx); inter.cols.push_back(col_of(col_get(tc, t))); inter.schema->f.push_back(Field{"x"});
-          }
-          ArrayRef m = into_array(tc, op->filter->eval(tc, inter), inter.base_rows);
-          ArrayRef nr = filter_idx(ridx, m), nl = filter_idx(lidx, m); ridx = nr; lidx = nl;
+      {
+        Keys rk, lk; JoinTableRef table; ArrayRef ridx;          // the table of the right rows and the pairs it gave go when the index algebra has run
+        if (!right_rows) { ridx = host_u64(tc, nullptr, 0); lidx = host_u32(tc, nullptr, 0); }
+        else {
+          Batch& rb = *right_rows;
+          rk = eval_keys(tc, op->on_r, rb);
+          tc.check(dfgpu_join_build(tc.ctx, rk.ptr.data(), (int32_t)rk.ptr.size(), nullptr, op->null_equals_null ? 1 : 0, &table.t));
+          lk = eval_keys(tc, op->on_l, lb);
+          dfgpu_array *b = nullptr, *p = nullptr;
+          tc.check(dfgpu_join_probe(tc.ctx, table.t, lk.ptr.data(), (int32_t)lk.ptr.size(), fused.a, &b, &p)); ridx = ArrayRef::adopt(b); lidx = ArrayRef::adopt(p);
+          filter_pairs(tc, op->filter, lb, rb, lidx, ridx);       // the filter's side 0 is still the left input
         }
-        dfgpu_array *b2 = nullptr, *p2 = nullptr;       // get_semi_indices / get_anti_indices over the left rows (joins/utils.rs:1309-1364)
-        tc.check(dfgpu_join_adjust_indices(tc.ctx, ridx.a, lidx.a, 0, lb.base_rows, anti ? DFGPU_JOIN_RIGHT_ANTI : DFGPU_JOIN_RIGHT_SEMI, &b2, &p2));
-        ArrayRef drop = ArrayRef::adopt(b2); lidx = ArrayRef::adopt(p2);
+        lidx = adjust_indices(tc, ridx, lidx, 0, lb.base_rows, as_probe_side(op->join_type)).p;       // get_semi_indices / get_anti_indices over the left rows (joins/utils.rs:1309-1364)
       }
-      if (bs->segments.size() > 1 && lidx.len()) {
-        dfgpu_array* w = nullptr; tc.check(dfgpu_cast(tc.ctx, lidx.a, DFGPU_UINT64, 0, 0, &w)); lidx = reference_final_order(ArrayRef::adopt(w));
-      }
+      if (bs->segments.size() > 1 && lidx.len()) lidx = reference_final_order(cast_to(tc, lidx, DFGPU_UINT64));
       o.base_rows = lidx.len();
       MemoPtr memo = std::make_shared<TakeMemo>(); for (auto& c : lb.cols) o.cols.push_back(col_take(c, lidx, memo));
       return o;
@@ -1124,11 +1166,11 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
         auto scalar = [&](uint64_t v) { return host_u64(tc, &v, 1); };
         std::vector<ArrayRef> pieces;
         for (size_t sg = bs->segments.size(); sg-- > 0;) {
-          ArrayRef lo = scalar((uint64_t)bounds[sg]), hi = scalar((uint64_t)bounds[sg + 1]); dfgpu_array *ge = nullptr, *lt = nullptr, *both = nullptr, *part = nullptr;
+          ArrayRef lo = scalar((uint64_t)bounds[sg]), hi = scalar((uint64_t)bounds[sg + 1]); dfgpu_array *ge = nullptr, *lt = nullptr, *both = nullptr;
           tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_GTEQ, fidx.a, 0, lo.a, 1, &ge)); ArrayRef a = ArrayRef::adopt(ge);
           tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_LT, fidx.a, 0, hi.a, 1, &lt)); ArrayRef b = ArrayRef::adopt(lt);
           tc.check(dfgpu_binary(tc.ctx, DFGPU_OP_AND, a.a, 0, b.a, 0, &both)); ArrayRef m = ArrayRef::adopt(both);
-          tc.check(dfgpu_filter(tc.ctx, fidx.a, m.a, &part)); ArrayRef pc = ArrayRef::adopt(part);
+          ArrayRef pc = filter_idx(tc, fidx, m);
           if (pc.len()) pieces.push_back(pc);
         }
         if (pieces.size() == 1) return pieces[0];
@@ -1157,39 +1199,40 @@ struct HashJoinExec : Plan {      // joins/hash_join.rs:283-330
 // batch by batch as its buffered cursor advances, :1001-1077; its two Full tests, :2094-2121 and :2451-2497, compare sorted rows, and so do ours).
 // RightSemi (refused by the reference too, :107-111) and JoinFilters answer NotImplemented.
 struct SortMergeJoinExec : Plan {
-  PlanPtr left, right; std::vector<ExprPtr> on_l, on_r; int join_type = 0; bool null_equals_null = false;
-  ExprPtr filter; std::vector<int> f_side, f_index;          // JoinFilter: column i of the intermediate batch = column f_index[i] of side f_side[i] (0 left, 1 right)
-  PlanPtr fresh() const override { auto j = std::make_shared<SortMergeJoinExec>(); j->left = left->fresh(); j->right = right->fresh(); j->on_l = on_l; j->on_r = on_r; j->join_type = join_type; j->null_equals_null = null_equals_null; j->filter = filter; j->f_side = f_side; j->f_index = f_index; return j; }
+  PlanPtr left, right; std::vector<ExprPtr> on_l, on_r; int join_type = 0; bool null_equals_null = false; JoinFilter filter;
+  PlanPtr fresh() const override { auto j = std::make_shared<SortMergeJoinExec>(); j->left = left->fresh(); j->right = right->fresh(); j->on_l = on_l; j->on_r = on_r; j->join_type = join_type; j->null_equals_null = null_equals_null; j->filter = filter; return j; }
   std::vector<std::shared_ptr<const Plan>> children() const override { return {left, right}; }
   const char* name() const override { return "SortMergeJoinExec"; }
-  bool left_only() const { return join_type == DFGPU_JOIN_LEFT_SEMI || join_type == DFGPU_JOIN_LEFT_ANTI; }
-  bool right_only() const { return join_type == DFGPU_JOIN_RIGHT_ANTI; }
-  SchemaPtr schema() const override {
-    auto s = std::make_shared<Schema>(); auto l = left->schema(), r = right->schema();
-    if (!right_only() && l) s->f.insert(s->f.end(), l->f.begin(), l->f.end());
-    if (!left_only() && r) s->f.insert(s->f.end(), r->f.begin(), r->f.end());
-    return s;
-  }
+  SchemaPtr schema() const override { return join_schema(left, right, join_type); }      // never RightSemi: the constructor refuses it
   int partitions() const override { return left->partitions(); }
+  // stable re-order of the pairs by streamed row: unmatched and NULL-joined rows back into their places, after the row's passing pairs
+  static void order_by_streamed(const TaskContext& tc, ArrayRef& bidx, ArrayRef& sidx) {
+    if (!sidx.len()) return;
+    const dfgpu_array* kp = sidx.a; uint8_t no = 0; dfgpu_array* perm = nullptr;
+    tc.check(dfgpu_sort_to_indices(tc.ctx, &kp, &no, &no, 1, -1, &perm)); ArrayRef pm = ArrayRef::adopt(perm);
+    bidx = take(tc, bidx, pm); sidx = take(tc, sidx, pm);
+  }
+  // Full (streamed side = left): one batch of NULLs joined with these buffered rows
+  Batch null_joined(const TaskContext& tc, Batch& lb, Batch& rb, const ArrayRef& buffered_rows) const {
+    ArrayRef nulls = null_array(tc, DFGPU_UINT32, 0, 0, buffered_rows.len());
+    Batch u; u.schema = schema(); u.base_rows = buffered_rows.len(); MemoPtr memo = std::make_shared<TakeMemo>();
+    for (auto& c : lb.cols) u.cols.push_back(col_take(c, nulls, memo));
+    for (auto& c : rb.cols) u.cols.push_back(col_take(c, buffered_rows, memo));
+    return u;
+  }
   std::unique_ptr<Stream> execute(int p, const TaskContext& tc) const override {
     if (left->partitions() != right->partitions()) fail(DFGPU_INTERNAL, "Invalid SortMergeJoinExec, partition count mismatch %d!=%d, consider using RepartitionExec", left->partitions(), right->partitions());   // :294-300
     const bool stream_left = join_type != DFGPU_JOIN_RIGHT && join_type != DFGPU_JOIN_RIGHT_ANTI;      // :160-175
-    auto collect = [&](const PlanPtr& side, Batch* out) {
-      std::vector<Batch> in; drain(side, p, tc, in);
-      if (!concat_batches(tc, in, out)) { out->schema = side->schema(); out->base_rows = 0; for (auto& f : out->schema->f) { dfgpu_array* nn = nullptr; tc.check(dfgpu_array_new_null(tc.ctx, f.type, f.precision, f.scale, 0, &nn)); out->cols.push_back(col_of(ArrayRef::adopt(nn))); } }
-    };
-    Batch lb, rb; collect(left, &lb); collect(right, &rb);
+    auto collect = [&](const PlanPtr& side) { std::vector<Batch> in; drain(side, p, tc, in); Batch b; if (!concat_batches(tc, in, &b)) b = empty_batch(tc, side); return b; };
+    Batch lb = collect(left), rb = collect(right);
     Batch& sb = stream_left ? lb : rb; Batch& bb = stream_left ? rb : lb;
-    const auto& on_s = stream_left ? on_l : on_r; const auto& on_b = stream_left ? on_r : on_l;
-    std::vector<Batch> outv;
     SpanGuard join_span(tc, met.get(), 2);
+    // probe: the key pairs, by streamed row
     ArrayRef bidx, sidx, unmatched_b;            // unmatched_b (Full): buffered rows no streamed row matched
     {
-      std::vector<ArrayRef> bk, sk; std::vector<const dfgpu_array*> bp, sp;
-      for (auto& e : on_b) { bk.push_back(into_array(tc, e->eval(tc, bb), bb.base_rows)); bp.push_back(bk.back().a); }
-      for (auto& e : on_s) { sk.push_back(into_array(tc, e->eval(tc, sb), sb.base_rows)); sp.push_back(sk.back().a); }
-      JoinTableRef table; tc.check(dfgpu_join_build(tc.ctx, bp.data(), (int32_t)bp.size(), nullptr, null_equals_null ? 1 : 0, &table.t));
-      dfgpu_array *b = nullptr, *s = nullptr; tc.check(dfgpu_join_probe(tc.ctx, table.t, sp.data(), (int32_t)sp.size(), nullptr, &b, &s)); bidx = ArrayRef::adopt(b); sidx = ArrayRef::adopt(s);
+      Keys bk = eval_keys(tc, stream_left ? on_r : on_l, bb), sk = eval_keys(tc, stream_left ? on_l : on_r, sb);
+      JoinTableRef table; tc.check(dfgpu_join_build(tc.ctx, bk.ptr.data(), (int32_t)bk.ptr.size(), nullptr, null_equals_null ? 1 : 0, &table.t));
+      dfgpu_array *b = nullptr, *s = nullptr; tc.check(dfgpu_join_probe(tc.ctx, table.t, sk.ptr.data(), (int32_t)sk.ptr.size(), nullptr, &b, &s)); bidx = ArrayRef::adopt(b); sidx = ArrayRef::adopt(s);
       if (join_type == DFGPU_JOIN_FULL) {        // the table indexes the buffered side: its unvisited rows are what the Full join adds (≙ the visited bitmap of a HashJoinExec Full join)
         tc.check(dfgpu_join_mark_visited(tc.ctx, table.t, bidx.a));
         dfgpu_array* u = nullptr; tc.check(dfgpu_join_final_indices(tc.ctx, table.t, DFGPU_JOIN_LEFT_ANTI, &u)); unmatched_b = ArrayRef::adopt(u);
@@ -1198,63 +1241,38 @@ struct SortMergeJoinExec : Plan {
     // JoinFilter (:1156-1300), as the reference applies it: over the joined PAIRS of a chunk.  A pair that passes is an output row.  For Left / Right / Full a pair that fails is
     // ALSO an output row -- its streamed row joined with NULLs (one per failing pair, not one per streamed row without a passing pair: sort_merge_join.slt:137-147 holds the
     // reference to exactly that), and for Full a second one, NULLs joined with its buffered row.  Buffered rows count as joined by their key match alone.
-    ArrayRef fail_b, fail_s; const int64_t npairs = sidx.len();
+    const bool outer = join_type != DFGPU_JOIN_INNER; const int64_t npairs = sidx.len();
+    ArrayRef fail_b, fail_s;
     if (filter && npairs) {
-      Batch inter; inter.schema = std::make_shared<Schema>(); inter.base_rows = npairs;
-      for (size_t i = 0; i < f_side.size(); i++) {
-        const bool from_left = f_side[i] == 0; Batch& side = from_left ? lb : rb;
-        Col t = col_take(side.cols.at((size_t)f_index[i]), from_left == stream_left ? sidx : bidx); inter.cols.push_back(col_of(col_get(tc, t))); inter.schema->f.push_back(Field{"x"});
-      }
-      ArrayRef m = known_mask(tc, into_array(tc, filter->eval(tc, inter), npairs));
-      auto pick = [&](const ArrayRef& a, const ArrayRef& mask) { dfgpu_array* o = nullptr; tc.check(dfgpu_filter(tc.ctx, a.a, mask.a, &o)); return ArrayRef::adopt(o); };
-      if (join_type != DFGPU_JOIN_INNER) { dfgpu_array* nm = nullptr; tc.check(dfgpu_not(tc.ctx, m.a, &nm)); ArrayRef notm = ArrayRef::adopt(nm); fail_b = pick(bidx, notm); fail_s = pick(sidx, notm); }
-      ArrayRef pb = pick(bidx, m), ps = pick(sidx, m);
-      if (join_type == DFGPU_JOIN_INNER) { bidx = pb; sidx = ps; }
-      else {
-        // streamed rows without a key match, from the index algebra over ALL key pairs; then passing pairs + failing pairs (buffered side NULL) + those rows
-        dfgpu_array *b2 = nullptr, *s2 = nullptr; tc.check(dfgpu_join_adjust_indices(tc.ctx, bidx.a, sidx.a, 0, sb.base_rows, DFGPU_JOIN_RIGHT, &b2, &s2)); ArrayRef ab = ArrayRef::adopt(b2), as_ = ArrayRef::adopt(s2);
-        dfgpu_array *ub = nullptr, *us = nullptr; tc.check(dfgpu_array_slice(tc.ctx, ab.a, npairs, ab.len() - npairs, &ub)); ArrayRef unb = ArrayRef::adopt(ub);
-        tc.check(dfgpu_array_slice(tc.ctx, as_.a, npairs, as_.len() - npairs, &us)); ArrayRef uns = ArrayRef::adopt(us);
-        dfgpu_array* nn = nullptr; tc.check(dfgpu_array_new_null(tc.ctx, DFGPU_UINT64, 0, 0, fail_s.len(), &nn)); ArrayRef fnull = ArrayRef::adopt(nn);
+      ArrayRef m = join_filter_mask(tc, filter, lb, rb, stream_left ? sidx : bidx, stream_left ? bidx : sidx);
+      if (outer) { dfgpu_array* nm = nullptr; tc.check(dfgpu_not(tc.ctx, m.a, &nm)); ArrayRef notm = ArrayRef::adopt(nm); fail_b = filter_idx(tc, bidx, notm); fail_s = filter_idx(tc, sidx, notm); }
+      ArrayRef pb = filter_idx(tc, bidx, m), ps = filter_idx(tc, sidx, m);
+      if (outer) {
+        // index algebra over ALL key pairs: the streamed rows without a key match follow the pairs; then passing pairs + failing pairs (buffered side NULL) + those rows
+        IndexPair all = adjust_indices(tc, bidx, sidx, 0, sb.base_rows, as_probe_side(join_type));
+        ArrayRef unb = slice(tc, all.b, npairs, all.b.len() - npairs), uns = slice(tc, all.p, npairs, all.p.len() - npairs);
+        ArrayRef fnull = null_array(tc, DFGPU_UINT64, 0, 0, fail_s.len());
         std::vector<ArrayRef> bv, sv;
         if (pb.len()) { bv.push_back(pb); sv.push_back(ps); }
         if (fail_s.len()) { bv.push_back(fnull); sv.push_back(fail_s); }
         if (unb.len()) { bv.push_back(unb); sv.push_back(uns); }
-        if (bv.empty()) { bidx = pb; sidx = ps; } else if (bv.size() == 1) { bidx = bv[0]; sidx = sv[0]; } else { bidx = concat_arrays(tc, bv); sidx = concat_arrays(tc, sv); }
-        if (sidx.len()) {                                  // back into streamed order, a row's passing pairs before its NULL-joined ones (stable)
-          const dfgpu_array* kp = sidx.a; uint8_t no = 0; dfgpu_array* perm = nullptr;
-          tc.check(dfgpu_sort_to_indices(tc.ctx, &kp, &no, &no, 1, -1, &perm)); ArrayRef pm = ArrayRef::adopt(perm);
-          bidx = take(tc, bidx, pm); sidx = take(tc, sidx, pm);
-        }
+        if (bv.size() > 1) { pb = concat_arrays(tc, bv); ps = concat_arrays(tc, sv); } else if (bv.size() == 1) { pb = bv[0]; ps = sv[0]; }
       }
+      bidx = pb; sidx = ps;
+      if (outer) order_by_streamed(tc, bidx, sidx);          // a row's passing pairs before its NULL-joined ones
+    } else if (outer) {
+      // index algebra: the streamed side plays the probe side.  Left / Right / Full: the unmatched streamed rows follow the pairs and go back into their places
+      IndexPair a = adjust_indices(tc, bidx, sidx, 0, sb.base_rows, as_probe_side(join_type)); bidx = a.b; sidx = a.p;
+      if (as_probe_side(join_type) == DFGPU_JOIN_RIGHT) order_by_streamed(tc, bidx, sidx);
     }
-    if (join_type != DFGPU_JOIN_INNER && !(filter && npairs)) {
-      const int as = (join_type == DFGPU_JOIN_LEFT || join_type == DFGPU_JOIN_RIGHT || join_type == DFGPU_JOIN_FULL) ? DFGPU_JOIN_RIGHT : join_type == DFGPU_JOIN_LEFT_SEMI ? DFGPU_JOIN_RIGHT_SEMI : DFGPU_JOIN_RIGHT_ANTI;
-      dfgpu_array *b2 = nullptr, *s2 = nullptr; tc.check(dfgpu_join_adjust_indices(tc.ctx, bidx.a, sidx.a, 0, sb.base_rows, as, &b2, &s2)); bidx = ArrayRef::adopt(b2); sidx = ArrayRef::adopt(s2);
-      if (as == DFGPU_JOIN_RIGHT && sidx.len()) {         // unmatched streamed rows back into their places: stable order by streamed row
-        const dfgpu_array* kp = sidx.a; uint8_t no = 0; dfgpu_array* perm = nullptr;
-        tc.check(dfgpu_sort_to_indices(tc.ctx, &kp, &no, &no, 1, -1, &perm)); ArrayRef pm = ArrayRef::adopt(perm);
-        bidx = take(tc, bidx, pm); sidx = take(tc, sidx, pm);
-      }
-    }
+    // assemble
+    std::vector<Batch> outv;
     Batch o; o.schema = schema(); o.base_rows = sidx.len(); MemoPtr memo = std::make_shared<TakeMemo>();
-    if (!right_only()) for (auto& c : lb.cols) o.cols.push_back(col_take(c, stream_left ? sidx : bidx, memo));
-    if (!left_only()) for (auto& c : rb.cols) o.cols.push_back(col_take(c, stream_left ? bidx : sidx, memo));
+    if (!right_only(join_type)) for (auto& c : lb.cols) o.cols.push_back(col_take(c, stream_left ? sidx : bidx, memo));
+    if (!left_only(join_type)) for (auto& c : rb.cols) o.cols.push_back(col_take(c, stream_left ? bidx : sidx, memo));
     if (o.base_rows > 0) outv.push_back(std::move(o));
-    if (join_type == DFGPU_JOIN_FULL && fail_b && fail_b.len() > 0) {      // Full with a filter: NULLs joined with the buffered row of every failing pair (:1262-1300)
-      const int64_t m = fail_b.len(); dfgpu_array* nn = nullptr; tc.check(dfgpu_array_new_null(tc.ctx, DFGPU_UINT32, 0, 0, m, &nn)); ArrayRef nulls = ArrayRef::adopt(nn);
-      Batch u; u.schema = schema(); u.base_rows = m; MemoPtr memo2 = std::make_shared<TakeMemo>();
-      for (auto& c : lb.cols) u.cols.push_back(col_take(c, nulls, memo2));
-      for (auto& c : rb.cols) u.cols.push_back(col_take(c, fail_b, memo2));
-      outv.push_back(std::move(u));
-    }
-    if (unmatched_b && unmatched_b.len() > 0) {      // Full: streamed (left) columns NULL, buffered (right) columns from the unmatched rows
-      const int64_t m = unmatched_b.len(); dfgpu_array* nn = nullptr; tc.check(dfgpu_array_new_null(tc.ctx, DFGPU_UINT32, 0, 0, m, &nn)); ArrayRef nulls = ArrayRef::adopt(nn);
-      Batch u; u.schema = schema(); u.base_rows = m; MemoPtr memo2 = std::make_shared<TakeMemo>();
-      for (auto& c : lb.cols) u.cols.push_back(col_take(c, nulls, memo2));
-      for (auto& c : rb.cols) u.cols.push_back(col_take(c, unmatched_b, memo2));
-      outv.push_back(std::move(u));
-    }
+    if (join_type == DFGPU_JOIN_FULL && fail_b && fail_b.len() > 0) outv.push_back(null_joined(tc, lb, rb, fail_b));      // Full with a filter: the buffered row of every failing pair (:1262-1300)
+    if (unmatched_b && unmatched_b.len() > 0) outv.push_back(null_joined(tc, lb, rb, unmatched_b));                      // Full: the buffered rows no streamed row matched
     return std::unique_ptr<Stream>(new VecStream(std::move(outv)));
   }
 };
@@ -1266,20 +1284,13 @@ struct SortMergeJoinExec : Plan {
 // no batch matched (:505-531).  Rows and row order per outer batch are the reference's; candidate pairs are generated in runs of left rows so that a
 // large cross product never sits in memory at once.
 struct NestedLoopJoinExec : Plan {
-  PlanPtr left, right; ExprPtr filter; std::vector<int> f_side, f_index; int join_type = 0;
+  PlanPtr left, right; JoinFilter filter; int join_type = 0;
   mutable std::mutex mu; mutable std::shared_ptr<Batch> inner;          // OnceFut<JoinLeftData>
   bool build_left() const { return join_type == DFGPU_JOIN_RIGHT || join_type == DFGPU_JOIN_RIGHT_SEMI || join_type == DFGPU_JOIN_RIGHT_ANTI || join_type == DFGPU_JOIN_FULL; }
-  bool left_only() const { return join_type == DFGPU_JOIN_LEFT_SEMI || join_type == DFGPU_JOIN_LEFT_ANTI; }
-  bool right_only() const { return join_type == DFGPU_JOIN_RIGHT_SEMI || join_type == DFGPU_JOIN_RIGHT_ANTI; }
-  PlanPtr fresh() const override { auto j = std::make_shared<NestedLoopJoinExec>(); j->left = left->fresh(); j->right = right->fresh(); j->filter = filter; j->f_side = f_side; j->f_index = f_index; j->join_type = join_type; return j; }
+  PlanPtr fresh() const override { auto j = std::make_shared<NestedLoopJoinExec>(); j->left = left->fresh(); j->right = right->fresh(); j->filter = filter; j->join_type = join_type; return j; }
   std::vector<std::shared_ptr<const Plan>> children() const override { return {left, right}; }
   const char* name() const override { return "NestedLoopJoinExec"; }
-  SchemaPtr schema() const override {
-    auto s = std::make_shared<Schema>(); auto l = left->schema(), r = right->schema();
-    if (!right_only() && l) s->f.insert(s->f.end(), l->f.begin(), l->f.end());
-    if (!left_only() && r) s->f.insert(s->f.end(), r->f.begin(), r->f.end());
-    return s;
-  }
+  SchemaPtr schema() const override { return join_schema(left, right, join_type); }
   int partitions() const override { return build_left() ? right->partitions() : left->partitions(); }
   std::shared_ptr<Batch> collect_inner(const TaskContext& tc) const {
     std::lock_guard<std::mutex> l(mu);
@@ -1288,10 +1299,7 @@ struct NestedLoopJoinExec : Plan {
       const PlanPtr& side = build_left() ? left : right;
       std::vector<Batch> in; for (int p = 0; p < side->partitions(); p++) drain(side, p, tc, in);
       auto b = std::make_shared<Batch>();
-      if (!concat_batches(tc, in, b.get())) {           // a side without a single batch: typed empty columns, so that outer joins still null-pad it
-        b->schema = side->schema(); b->base_rows = 0;
-        for (auto& f : b->schema->f) { dfgpu_array* nn = nullptr; tc.check(dfgpu_array_new_null(tc.ctx, f.type, f.precision, f.scale, 0, &nn)); b->cols.push_back(col_of(ArrayRef::adopt(nn))); }
-      }
+      if (!concat_batches(tc, in, b.get())) *b = empty_batch(tc, side);
       inner = b;
     }
     return inner;
@@ -1300,14 +1308,12 @@ struct NestedLoopJoinExec : Plan {
     const NestedLoopJoinExec* op; TaskContext tc; std::unique_ptr<Stream> outer; std::shared_ptr<Batch> in; SchemaPtr out_schema; int state = 0;
     std::vector<ArrayRef> matched_left;        // Full: per outer batch, the left rows that joined (ascending, distinct)
     S(const NestedLoopJoinExec* o, int p, TaskContext t) : op(o), tc(t) { in = op->collect_inner(tc); outer = (op->build_left() ? op->right : op->left)->run(p, tc); out_schema = op->schema(); }
-    ArrayRef filter_idx(const ArrayRef& idx, const ArrayRef& m) { dfgpu_array* o = nullptr; tc.check(dfgpu_filter(tc.ctx, idx.a, m.a, &o)); return ArrayRef::adopt(o); }
-    ArrayRef cast_to(const ArrayRef& a, int32_t t) { dfgpu_array* o = nullptr; tc.check(dfgpu_cast(tc.ctx, a.a, t, 0, 0, &o)); return ArrayRef::adopt(o); }
     ArrayRef empty_idx(int32_t t) { dfgpu_array* o = nullptr; tc.check(dfgpu_array_new_zeros(tc.ctx, t, 0, 0, 0, &o)); return ArrayRef::adopt(o); }
     ArrayRef cat(std::vector<ArrayRef>& v, int32_t t) { if (v.empty()) return empty_idx(t); if (v.size() == 1) return v[0]; return concat_arrays(tc, v); }
     Batch build_batch(Batch& lb, Batch& rb, const ArrayRef& li, const ArrayRef& ri, int64_t rows) {
       Batch o; o.schema = out_schema; o.base_rows = rows; MemoPtr memo = std::make_shared<TakeMemo>();
-      if (!op->right_only()) for (auto& c : lb.cols) o.cols.push_back(col_take(c, li, memo));
-      if (!op->left_only()) for (auto& c : rb.cols) o.cols.push_back(col_take(c, ri, memo));
+      if (!right_only(op->join_type)) for (auto& c : lb.cols) o.cols.push_back(col_take(c, li, memo));
+      if (!left_only(op->join_type)) for (auto& c : rb.cols) o.cols.push_back(col_take(c, ri, memo));
       return o;
     }
     // all filtered pairs of one (left batch, right batch), left-major
@@ -1319,15 +1325,7 @@ struct NestedLoopJoinExec : Plan {
         const int64_t cnt = std::min(run, nl - first);
         dfgpu_array *a = nullptr, *b = nullptr; tc.check(dfgpu_cross_join_indices(tc.ctx, first, cnt, nr, bl ? 1 : 0, &a, &b));
         ArrayRef l = ArrayRef::adopt(a), r = ArrayRef::adopt(b);
-        if (op->filter) {
-          Batch inter; inter.schema = std::make_shared<Schema>(); inter.base_rows = l.len();
-          for (size_t i = 0; i < op->f_side.size(); i++) {
-            Col src = op->f_side[i] == 0 ? lb.cols.at((size_t)op->f_index[i]) : rb.cols.at((size_t)op->f_index[i]);
-            Col t = col_take(src, op->f_side[i] == 0 ? l : r); inter.cols.push_back(col_of(col_get(tc, t))); inter.schema->f.push_back(Field{"x"});
-          }
-          ArrayRef m = into_array(tc, op->filter->eval(tc, inter), inter.base_rows);
-          l = filter_idx(l, m); r = filter_idx(r, m);
-        }
+        filter_pairs(tc, op->filter, lb, rb, l, r);
         if (l.len()) { ls.push_back(l); rs.push_back(r); }
       }
       *li = cat(ls, bl ? DFGPU_UINT64 : DFGPU_UINT32); *ri = cat(rs, bl ? DFGPU_UINT32 : DFGPU_UINT64);
@@ -1341,30 +1339,25 @@ struct NestedLoopJoinExec : Plan {
         Batch& lb = bl ? *in : ob; Batch& rb = bl ? ob : *in;
         ArrayRef li, ri; pairs(lb, rb, &li, &ri);
         if (jt == DFGPU_JOIN_FULL && li.len()) {          // visited_left_side.set_bit (:620-625)
-          ArrayRef l32 = cast_to(li, DFGPU_UINT32), r64 = cast_to(ri, DFGPU_UINT64); dfgpu_array *b2 = nullptr, *p2 = nullptr;
-          tc.check(dfgpu_join_adjust_indices(tc.ctx, r64.a, l32.a, 0, lb.base_rows, DFGPU_JOIN_RIGHT_SEMI, &b2, &p2)); ArrayRef drop = ArrayRef::adopt(b2); matched_left.push_back(ArrayRef::adopt(p2));
+          ArrayRef l32 = cast_to(tc, li, DFGPU_UINT32), r64 = cast_to(tc, ri, DFGPU_UINT64);
+          matched_left.push_back(adjust_indices(tc, r64, l32, 0, lb.base_rows, DFGPU_JOIN_RIGHT_SEMI).p);
         }
         if (jt != DFGPU_JOIN_INNER) {                      // adjust_indices_by_join_type (:652-708): the streamed side plays the probe side of the hash join's index algebra
-          dfgpu_array *b2 = nullptr, *p2 = nullptr;
-          if (bl) { tc.check(dfgpu_join_adjust_indices(tc.ctx, li.a, ri.a, 0, rb.base_rows, jt == DFGPU_JOIN_FULL ? DFGPU_JOIN_RIGHT : jt, &b2, &p2)); li = ArrayRef::adopt(b2); ri = ArrayRef::adopt(p2); }
-          else {
-            int as = jt == DFGPU_JOIN_LEFT ? DFGPU_JOIN_RIGHT : jt == DFGPU_JOIN_LEFT_SEMI ? DFGPU_JOIN_RIGHT_SEMI : DFGPU_JOIN_RIGHT_ANTI;
-            tc.check(dfgpu_join_adjust_indices(tc.ctx, ri.a, li.a, 0, lb.base_rows, as, &b2, &p2)); ri = ArrayRef::adopt(b2); li = ArrayRef::adopt(p2);
-          }
+          ArrayRef& bi = bl ? li : ri; ArrayRef& pi = bl ? ri : li;
+          IndexPair a = adjust_indices(tc, bi, pi, 0, ob.base_rows, as_probe_side(jt)); bi = a.b; pi = a.p;
         }
-        const int64_t rows = (op->right_only() ? ri : li).len();
+        const int64_t rows = (right_only(jt) ? ri : li).len();
         out = build_batch(lb, rb, li, ri, rows); return true;           // one output batch per outer batch, empty ones included (the reference's stream does the same)
       }
       if (state == 1) {
         state = 2;
         if (jt == DFGPU_JOIN_FULL) {                      // get_final_indices_from_bit_map: left rows no right batch matched, right side NULL
           SpanGuard join_span(tc, op->met.get(), 2);
-          ArrayRef all = cat(matched_left, DFGPU_UINT32), all64 = cast_to(all, DFGPU_UINT64); dfgpu_array *b2 = nullptr, *p2 = nullptr;
-          tc.check(dfgpu_join_adjust_indices(tc.ctx, all64.a, all.a, 0, in->base_rows, DFGPU_JOIN_RIGHT_ANTI, &b2, &p2)); ArrayRef drop = ArrayRef::adopt(b2); ArrayRef un = ArrayRef::adopt(p2);
+          ArrayRef all = cat(matched_left, DFGPU_UINT32), all64 = cast_to(tc, all, DFGPU_UINT64);
+          IndexPair rest = adjust_indices(tc, all64, all, 0, in->base_rows, DFGPU_JOIN_RIGHT_ANTI); const ArrayRef& un = rest.p;
           Batch o; o.schema = out_schema; o.base_rows = un.len(); MemoPtr memo = std::make_shared<TakeMemo>();
           for (auto& c : in->cols) o.cols.push_back(col_take(c, un, memo));
-          auto rf = op->right->schema();
-          for (size_t i = 0; i < (rf ? rf->f.size() : 0); i++) { dfgpu_array* nn = nullptr; tc.check(dfgpu_array_new_null(tc.ctx, rf->f[i].type, rf->f[i].precision, rf->f[i].scale, o.base_rows, &nn)); o.cols.push_back(col_of(ArrayRef::adopt(nn))); }
+          push_null_cols(tc, op->right->schema(), o.base_rows, o.cols);
           out = std::move(o); return true;
         }
       }
@@ -1391,7 +1384,6 @@ static const char* agg_fun_name(int k) { switch (k) { case DFGPU_AGG_SUM: return
 struct StringMinMax {
   bool is_max = false; ArrayRef gids, vals;
   static ArrayRef true1(const TaskContext& tc) { const uint64_t one = 1; return host_array(tc, DFGPU_BOOL, &one, 1); }
-  static ArrayRef slice(const TaskContext& tc, const ArrayRef& a, int64_t off, int64_t len) { dfgpu_array* o = nullptr; tc.check(dfgpu_array_slice(tc.ctx, a.a, off, len, &o)); return ArrayRef::adopt(o); }
   void reduce(const TaskContext& tc, ArrayRef g, ArrayRef v) {
     const int64_t n = g.len();
     if (n == 0) { gids = g; vals = v; return; }
@@ -1413,7 +1405,7 @@ struct StringMinMax {
     reduce(tc, g, v);
   }
   ArrayRef emit(const TaskContext& tc, int64_t total) {          // one row per group 0 .. total-1, NULL where no value was seen: a NULL candidate per group orders last
-    dfgpu_array *io = nullptr, *nl = nullptr; tc.check(dfgpu_array_iota(tc.ctx, total, &io)); ArrayRef g = ArrayRef::adopt(io); tc.check(dfgpu_array_new_null(tc.ctx, DFGPU_UTF8, 0, 0, total, &nl)); ArrayRef v = ArrayRef::adopt(nl);
+    dfgpu_array* io = nullptr; tc.check(dfgpu_array_iota(tc.ctx, total, &io)); ArrayRef g = ArrayRef::adopt(io), v = null_array(tc, DFGPU_UTF8, 0, 0, total);
     if (gids && gids.len()) { std::vector<ArrayRef> gp{gids, g}, vp{vals, v}; g = concat_arrays(tc, gp); v = concat_arrays(tc, vp); }
     StringMinMax t; t.is_max = is_max; t.reduce(tc, g, v);
     if (t.vals.len() != total) fail(DFGPU_INTERNAL, "string MIN/MAX: %lld rows for %lld groups", (long long)t.vals.len(), (long long)total);
@@ -1437,7 +1429,7 @@ struct CountDistinct {
     const int64_t fresh = dfgpu_groups_len(pairs.g) - before;
     if (fresh > 0) {
       dfgpu_array* keys[2] = { nullptr, nullptr }; tc.check(dfgpu_groups_emit(tc.ctx, pairs.g, keys)); ArrayRef k0 = ArrayRef::adopt(keys[0]), k1 = ArrayRef::adopt(keys[1]);
-      ArrayRef gk = StringMinMax::slice(tc, k0, before, fresh);
+      ArrayRef gk = slice(tc, k0, before, fresh);
       tc.check(dfgpu_acc_update_batch(tc.ctx, cnt.a, nullptr, gk.a, nullptr, total));
     }
   }
@@ -2033,9 +2025,8 @@ struct SortExec : Plan {          // sorts/sort.rs:719-733; sort_batch :584-609
           parts.push_back(std::move(b)); }
         Batch all; if (parts.empty() || !concat_batches(tc, parts, &all) || all.base_rows <= 0) continue;
         parts.clear();
-        std::vector<ArrayRef> keys; std::vector<const dfgpu_array*> kp;
-        for (auto& e : op->exprs) { keys.push_back(into_array(tc, e->eval(tc, all), all.base_rows)); kp.push_back(keys.back().a); }
-        out = sorted_batch(tc, all, op->exprs, kp, op->desc, op->nulls_first, -1); r++; return true;
+        Keys keys = eval_keys(tc, op->exprs, all);
+        out = sorted_batch(tc, all, op->exprs, keys.ptr, op->desc, op->nulls_first, -1); r++; return true;
       }
       return false;
     }
@@ -2051,9 +2042,8 @@ struct SortExec : Plan {          // sorts/sort.rs:719-733; sort_batch :584-609
     Batch all; if (mem.empty() || !concat_batches(tc, mem, &all) || all.base_rows <= 0) { mem.clear(); return; }
     mem.clear();
     Batch sorted;
-    { std::vector<ArrayRef> keys; std::vector<const dfgpu_array*> kp;
-      for (auto& e : exprs) { keys.push_back(into_array(tc, e->eval(tc, all), all.base_rows)); kp.push_back(keys.back().a); }
-      sorted = sorted_batch(tc, all, exprs, kp, desc, nulls_first, -1); all = Batch(); }
+    { Keys keys = eval_keys(tc, exprs, all);
+      sorted = sorted_batch(tc, all, exprs, keys.ptr, desc, nulls_first, -1); all = Batch(); }
     std::vector<ArrayRef> cols; for (auto& c : sorted.cols) cols.push_back(col_get(tc, c));
     Batch view; view.schema = sorted.schema; view.base_rows = sorted.base_rows; for (auto& c : cols) view.cols.push_back(col_of(c));
     std::vector<ArrayRef> skeys; for (auto& e : exprs) skeys.push_back(into_array(tc, e->eval(tc, view), view.base_rows));
@@ -2081,9 +2071,8 @@ struct SortExec : Plan {          // sorts/sort.rs:719-733; sort_batch :584-609
     }
     std::vector<Batch> outv; Batch b;
     if (!in.empty() && concat_batches(tc, in, &b) && b.base_rows > 0) {
-      std::vector<ArrayRef> keys; std::vector<const dfgpu_array*> kp;
-      for (auto& e : exprs) { keys.push_back(into_array(tc, e->eval(tc, b), b.base_rows)); kp.push_back(keys.back().a); }
-      outv.push_back(sorted_batch(tc, b, exprs, kp, desc, nulls_first, fetch));
+      Keys keys = eval_keys(tc, exprs, b);
+      outv.push_back(sorted_batch(tc, b, exprs, keys.ptr, desc, nulls_first, fetch));
     }
     return std::unique_ptr<Stream>(new VecStream(std::move(outv)));
   }
@@ -2133,9 +2122,8 @@ struct SortPreservingMergeExec : Plan {
       return o;
     }
     ArrayRef order_of(Batch& all, int64_t limit) {
-      std::vector<ArrayRef> keys; std::vector<const dfgpu_array*> kp;
-      for (auto& e : op->exprs) { keys.push_back(into_array(tc, e->eval(tc, all), all.base_rows)); kp.push_back(keys.back().a); }
-      dfgpu_array* idx = nullptr; tc.check(dfgpu_sort_to_indices(tc.ctx, kp.data(), op->desc.data(), op->nulls_first.data(), (int32_t)kp.size(), limit, &idx)); return ArrayRef::adopt(idx);
+      Keys keys = eval_keys(tc, op->exprs, all);
+      dfgpu_array* idx = nullptr; tc.check(dfgpu_sort_to_indices(tc.ctx, keys.ptr.data(), op->desc.data(), op->nulls_first.data(), (int32_t)keys.ptr.size(), limit, &idx)); return ArrayRef::adopt(idx);
     }
     Batch gather(const Batch& all, const ArrayRef& ix) { Batch o; o.schema = all.schema; o.base_rows = ix.len(); for (auto& c : all.cols) o.cols.push_back(col_of(take(tc, c.arr, ix))); return o; }
     bool next(Batch& out) override {
@@ -2219,6 +2207,12 @@ template <typename F> static dfgpu_status guard(F&& f) {
 }
 static ExprPtr ex(const dfgpu_expr* e) { if (!e) fail(DFGPU_INVALID_ARGUMENT, "null expression"); return e->e; }
 static PlanPtr pl(const dfgpu_plan* p) { if (!p) fail(DFGPU_INVALID_ARGUMENT, "null plan"); return p->p; }
+static JoinFilter join_filter(const dfgpu_expr* filter, const int32_t* side, const int32_t* index, int32_t n) {      // no expression: no filter
+  JoinFilter f; if (!filter) return f;
+  if (n > 0 && (!side || !index)) fail(DFGPU_INVALID_ARGUMENT, "JoinFilter without column indices");
+  f.expr = ex(filter); for (int i = 0; i < n; i++) { f.side.push_back(side[i]); f.index.push_back(index[i]); }
+  return f;
+}
 
 extern "C" {
 
@@ -2399,7 +2393,7 @@ dfgpu_status dfgpu_plan_hash_join(const dfgpu_plan* left, const dfgpu_plan* righ
     if (join_type < 0 || join_type > DFGPU_JOIN_RIGHT_ANTI) fail(DFGPU_INVALID_ARGUMENT, "unknown join type %d", join_type);
     auto j = std::make_shared<HashJoinExec>(); j->left = pl(left); j->right = pl(right);
     for (int i = 0; i < non; i++) { j->on_l.push_back(ex(on_left[i])); j->on_r.push_back(ex(on_right[i])); }
-    if (filter) { j->filter = ex(filter); for (int i = 0; i < nf; i++) { j->f_side.push_back(fs[i]); j->f_index.push_back(fi[i]); } }
+    j->filter = join_filter(filter, fs, fi, nf);
     j->join_type = join_type; j->mode = mode; j->null_equals_null = nen != 0;
     mark_selection_consumer(j->left); mark_selection_consumer(j->right, true);
     *out = new dfgpu_plan{j};
@@ -2414,9 +2408,8 @@ dfgpu_status dfgpu_plan_sort_merge_join(const dfgpu_plan* left, const dfgpu_plan
     if (join_type < 0 || join_type > DFGPU_JOIN_RIGHT_ANTI) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: SortMergeJoinExec join type %d on the device", join_type);
     if (filter && (join_type == DFGPU_JOIN_LEFT_SEMI || join_type == DFGPU_JOIN_LEFT_ANTI || join_type == DFGPU_JOIN_RIGHT_ANTI))
       fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: SortMergeJoinExec %s with a JoinFilter on the device (Inner, Left, Right and Full take one)", join_type == DFGPU_JOIN_LEFT_SEMI ? "LeftSemi" : join_type == DFGPU_JOIN_LEFT_ANTI ? "LeftAnti" : "RightAnti");
-    if (filter && nf > 0 && (!fs || !fi)) fail(DFGPU_INVALID_ARGUMENT, "sort_merge_join: JoinFilter without column indices");
     auto j = std::make_shared<SortMergeJoinExec>(); j->left = pl(left); j->right = pl(right);
-    if (filter) { j->filter = ex(filter); for (int i = 0; i < nf; i++) { j->f_side.push_back(fs[i]); j->f_index.push_back(fi[i]); } }
+    j->filter = join_filter(filter, fs, fi, nf);
     for (int i = 0; i < non; i++) { j->on_l.push_back(ex(on_left[i])); j->on_r.push_back(ex(on_right[i])); }
     j->join_type = join_type; j->null_equals_null = null_equals_null != 0;
     *out = new dfgpu_plan{j};
@@ -2426,7 +2419,7 @@ dfgpu_status dfgpu_plan_nested_loop_join(const dfgpu_plan* left, const dfgpu_pla
   return guard([&] {
     if (join_type < 0 || join_type > DFGPU_JOIN_RIGHT_ANTI) fail(DFGPU_INVALID_ARGUMENT, "unknown join type %d", join_type);
     auto j = std::make_shared<NestedLoopJoinExec>(); j->left = pl(left); j->right = pl(right); j->join_type = join_type;
-    if (filter) { j->filter = ex(filter); for (int i = 0; i < nf; i++) { j->f_side.push_back(fs[i]); j->f_index.push_back(fi[i]); } }
+    j->filter = join_filter(filter, fs, fi, nf);
     *out = new dfgpu_plan{j};
   });
 }
