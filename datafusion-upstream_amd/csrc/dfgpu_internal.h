@@ -38,6 +38,18 @@ namespace dfgpu { struct Buffer; constexpr int TS_BAD_SLOT = 50; }      // slot 
 // both kernels are exact at every length.  Measured (profiles/scalar_fn_microbench.json, `crossing`: character_length over 256 MB of equal-length rows, ms lane / wave):
 // 64 B 0.10 / 1.00, 96 B 0.22 / 0.64, 128 B 0.54 / 0.48, 256 B 0.44 / 0.24, 1024 B 0.22 / 0.07; left(s, -1) crosses at 128 B too (1.54 / 1.51).
 namespace dfgpu { constexpr int64_t STR_WAVE_ROW_BYTES = 128; }
+namespace dfgpu {
+// pagg.hip: a verdict-only dfgpu_agg_preaggregate call (would this batch be taken?) has sampled the key column and, for 2..4 key columns or a nullable one, packed them into
+// one u64 per row: key = sum((v - min + nullable) * stride), 0 in a nullable column's digit = NULL.  Both are kept for the call that follows on the same columns.
+struct PaVerdictMemo {
+  const void* key = nullptr; const void* mask = nullptr; int64_t n = 0;      // what the sample was taken of: values of the first key column, selection words, rows
+  uint64_t sample[3] = {0, 0, 0};                                            // distinct keys, non-decreasing pairs, pairs
+  std::shared_ptr<Buffer> pack; int pack_n = 0; int64_t pack_min[4] = {0, 0, 0, 0}; uint64_t pack_stride[4] = {0, 0, 0, 0}, pack_range[4] = {0, 0, 0, 0};
+  // taken by the call it answered, and dropped by every decline: a skipped batch's sample must not answer for the next batch at a recycled address
+  void clear() { key = nullptr; pack.reset(); }
+  bool answers(const void* k, const void* m, int64_t rows, bool packed, int nkeys) const { return key == k && n == rows && mask == m && (!packed || (pack && pack_n == nkeys)); }
+};
+}
 struct dfgpu_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -67,9 +79,7 @@ struct dfgpu_ctx {
   bool agg_order_inverse_map = true;   // pre-aggregation with millions of partial rows: first-seen order through an inverse map over the input rows (pagg.hip) instead of a stable sort
   int64_t agg_pack_estimate_min_rows = 1 << 22;   // packed group keys: batches of at least this many rows take their value ranges from a sample (checked row by row while packing)
   bool pa_last_distinct = false;    // the last dfgpu_agg_preaggregate call emitted every key once
-  const void* pa_sample_key = nullptr; const void* pa_sample_mask = nullptr; int64_t pa_sample_n = 0; uint64_t pa_sample[3] = {0, 0, 0};   // sample of a verdict-only dfgpu_agg_preaggregate call
-  // 2..4 key columns packed into one u64 by that verdict-only call (kept for the call that follows on the same columns): key = sum((v - min + nullable) * stride), 0 in a nullable column's digit = NULL
-  std::shared_ptr<dfgpu::Buffer> pa_pack; int pa_pack_n = 0; int64_t pa_pack_min[4] = {0, 0, 0, 0}; uint64_t pa_pack_stride[4] = {0, 0, 0, 0}, pa_pack_range[4] = {0, 0, 0, 0}; bool pa_pack_nullable[4] = {false, false, false, false};
+  dfgpu::PaVerdictMemo pa_memo;     // what a verdict-only dfgpu_agg_preaggregate call leaves for the call that follows
   // row selection of the running operator (dfgpu_ctx_set_row_selection): expression kernels evaluate every row of full-length
   // columns but raise errors only for selected rows
   std::shared_ptr<dfgpu::Buffer> row_selection; int64_t row_selection_len = 0;

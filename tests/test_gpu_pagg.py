@@ -4,6 +4,8 @@ The partial rows of a batch, interned and merged (GroupValues::intern + GroupsAc
 row-by-row update gives: the same groups in the same first-seen order, bit-exact integer / count states, Float64 sums within 1e-9
 relative.  Thresholds are lowered through the ctx options; the LDS table is made to overflow (more groups per partition than slots) to
 cover the flush path, and the key that equals the table's EMPTY marker (-1) gets its own slot."""
+import ctypes as C
+
 import numpy as np
 import pyarrow as pa
 import pytest
@@ -191,6 +193,7 @@ def test_two_level_partition_for_millions_of_groups(ctx):
     wk, want = run_oracle(key, aggs)
     compare(gk, got, wk, want)
     assert m == len(wk)                                   # no key was split over partial rows
+    word_sort_order_equals_inverse_map(ctx)               # the first-seen order above came through the inverse map: now the other route for this many partial rows against it
 
 
 @pytest.mark.parametrize("nbatches", [1, 2, 3])
@@ -294,6 +297,7 @@ def test_nullable_key_columns_and_selection(ctx):
         assert "pa_aggregate" in f.kernels()
     wk, want = run_oracle_multi([k0, k1], aggs, mask=mask)
     compare_multi(gk, got, wk, want)
+    verdict_then_call_shares_sample_and_packed_keys(ctx)          # the same packed-key path entered the way the plan layer enters it: verdict first
 
 
 def test_one_nullable_key_column(ctx):
@@ -589,3 +593,76 @@ def test_many_partition_scatter(ctx):
         assert got.take(pa.array(o1)).cast(pa.int64()).equals(w.take(pa.array(ow)).cast(pa.int64()))
     dec = pa.decimal128(38, 2)
     assert r1[2].take(pa.array(o1)).cast(dec).equals(want[3].take(pa.array(ow)).cast(dec))
+
+
+# ---------------------------------------------------------------------------------------------- the fourth first-seen ordering route, and the verdict memo with packed keys
+def word_sort_order_equals_inverse_map(ctx):
+    """More than 4 Mi partial rows with option agg_order_inverse_map = 0: the (first row, partial row) words go through LSD passes of the stable partition (pa_order_scatter).
+    4.3 M distinct keys, each in exactly two rows of a random permutation: both routes must emit the same keys and the same integer states in the same (first-seen) order --
+    the inverse-map route (checked against the oracle by the 16 M-row two-level test) is the reference of the other one."""
+    import dfgpu
+    card = 4_300_000
+    rng = np.random.default_rng(71)
+    kv = np.repeat(np.arange(card, dtype=np.int64) * 2654435761 - 5, 2)[rng.permutation(2 * card)]
+    key = ctx.from_arrow(pa.array(kv)); v = ctx.from_arrow(pa.array(rng.integers(-10**6, 10**6, 2 * card).astype(np.int64)))
+    saved = ctx.get_option("agg_order_inverse_map")
+    out, ran = {}, {}
+    try:
+        for inverse_map in (1, 0):
+            ctx.set_option("agg_order_inverse_map", inverse_map)
+            with forced(ctx) as f:
+                pk, states = dfgpu.agg_preaggregate(ctx, key, [KIND["SUM"], KIND["COUNT"]], [v, None])
+                ran[inverse_map] = f.kernels()
+            out[inverse_map] = (pk.to_numpy(), [s[0].to_numpy() for s in states])
+    finally:
+        ctx.set_option("agg_order_inverse_map", saved)
+    assert "pa_order_scatter" in ran[0] and "pa_order_scatter" not in ran[1], (sorted(ran[0]), sorted(ran[1]))
+    assert "pa_order" in ran[0] and "pa_order" in ran[1]
+    (k1, s1), (k0, s0) = out[1], out[0]
+    assert len(k1) > (4 << 20)                            # the shape reaches the routes for many partial rows
+    assert np.array_equal(k0, k1)                         # element for element: the same first-seen order
+    for a, b in zip(s0, s1):
+        assert a.dtype == b.dtype and np.array_equal(a, b)
+
+
+def verdict(ctx, keys, mask=None):
+    """dfgpu_agg_preaggregate with null outputs: would the batch be taken?  (raises DfgpuError when not)"""
+    kh = (C.c_void_p * len(keys))(*[k.h for k in keys])
+    ctx.check(ctx.lib.dfgpu_agg_preaggregate(ctx.h, kh, len(keys), None, None, 0, mask.h if mask is not None else None, None, None))
+
+
+def verdict_then_call_shares_sample_and_packed_keys(ctx):
+    """A verdict-only call (null outputs) leaves its sample and its packed keys for the call that follows on the same columns: that call neither samples nor packs again and
+    returns what a call by itself returns on fresh copies of the columns.  A verdict on another column answers for nothing."""
+    import dfgpu
+    n, groups = 200_000, 20_000
+    rng = np.random.default_rng(73)
+    gid = rng.integers(0, groups, n)
+    k0 = pa.array((gid % 400 - 200).astype(np.int32), mask=rng.random(n) < 0.05); k1 = pa.array((gid // 400 * 3).astype(np.int32))
+    v = pa.array(rng.integers(-10**9, 10**9, n).astype(np.int64))
+    kinds = [KIND["SUM"], KIND["COUNT"]]
+    host = lambda pk, states: ([k.to_arrow() for k in pk], [s[0].to_arrow() for s in states])
+    with forced(ctx) as f:
+        ka, va = [ctx.from_arrow(k0), ctx.from_arrow(k1)], ctx.from_arrow(v)
+        alone = host(*dfgpu.agg_preaggregate(ctx, ka, kinds, [va, None]))
+        ran = ctx.profile_read()
+        assert ran["pa_sample"][0] == 1 and "pa_pack" in ran
+        kb, vb = [ctx.from_arrow(k0), ctx.from_arrow(k1)], ctx.from_arrow(v)          # fresh copies; the first ones stay alive, so the addresses differ
+        verdict(ctx, kb)
+        ran = ctx.profile_read()
+        assert ran["pa_sample"][0] == 1 and "pa_pack" in ran and "pa_aggregate" not in ran
+        after = host(*dfgpu.agg_preaggregate(ctx, kb, kinds, [vb, None]))
+        ran = ctx.profile_read()
+        assert "pa_sample" not in ran and "sync:pa_sample" not in ran and "pa_pack" not in ran and "pa_aggregate" in ran, sorted(ran)
+        for a, b in zip(alone[0] + alone[1], after[0] + after[1]):
+            assert a.type == b.type and a.equals(b)
+        assert alone[0][0].null_count > 0 and len(alone[0][0]) > groups // 2
+        # a verdict on one column, the call on another column of the same length: sampled again
+        c0 = ctx.from_arrow(pa.array(rng.integers(0, groups, n).astype(np.int64) * 7919)); c1v = rng.integers(0, groups, n).astype(np.int64) * 104729 + 1; c1 = ctx.from_arrow(pa.array(c1v))
+        verdict(ctx, [c0])
+        assert ctx.profile_read()["pa_sample"][0] == 1
+        pk, states = dfgpu.agg_preaggregate(ctx, c1, [KIND["COUNT"]], [None])
+        assert ctx.profile_read()["pa_sample"][0] == 1
+        dfgpu.agg_preaggregate(ctx, c0, [KIND["COUNT"]], [None])          # takes what the verdict on c0 left: the session's ctx goes on without it
+    uk, first, cnt = np.unique(c1v, return_index=True, return_counts=True); o = np.argsort(first, kind="stable")
+    assert np.array_equal(pk.to_numpy(), uk[o]) and np.array_equal(states[0][0].to_numpy(), cnt[o])
