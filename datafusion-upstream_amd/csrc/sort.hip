@@ -687,284 +687,413 @@ __global__ void __launch_bounds__(BLOCK) k_ws_rank_sort_pairs(const uint64_t* __
 }  // namespace dfgpu
 
 using namespace dfgpu;
-static void sort_impl(dfgpu_ctx* ctx, const dfgpu_array* const* cols, const uint8_t* descending, const uint8_t* nulls_first, int32_t k, int64_t fetch, dfgpu_array** out, dfgpu_array** out_sorted) {
-  {
-    if (!cols || k < 1 || !out) fail(DFGPU_INVALID_ARGUMENT, "Sort requires at least one column");
-    if (k > MAX_KEYS) fail(DFGPU_NOT_IMPLEMENTED, "more than %d sort columns", MAX_KEYS);
-    int64_t n = cols[0]->length;
-    SortCols sc{}; sc.n = k; int W = 0;
-    for (int c = 0; c < k; c++) {
-      if (cols[c]->length != n) fail(DFGPU_INVALID_ARGUMENT, "sort columns differ in length");
-      int32_t lt = logical_type(cols[c]);
-      SortCol& s = sc.c[c]; s.v = make_view(cols[c]); s.byte_off = W; s.max_len = 0;
-      if (lt == DFGPU_UTF8) {
-        HIP_CHECK(hipMemsetAsync(ctx->d_scratch64 + 12, 0, 8, ctx->stream));
-        if (n) hipLaunchKernelGGL(k_max_utf8_len, dim3(grid_for(n, BLOCK * 8, 512)), dim3(BLOCK), 0, ctx->stream, s.v, n, (unsigned int*)(ctx->d_scratch64 + 12));
-        KERNEL_CHECK();
-        uint64_t ml = read_scratch(ctx, 12) & 0xFFFFFFFFull;
-        if (ml > 1024) fail(DFGPU_NOT_IMPLEMENTED, "Utf8 sort keys longer than 1024 bytes (%llu) are not supported on device", (unsigned long long)ml);
-        s.max_len = (int32_t)ml;
-      }
-      s.has_null_byte = (s.v.validity || s.v.key_validity) ? 1 : 0; s.descending = descending && descending[c]; s.nulls_first = nulls_first ? nulls_first[c] : 1;
-      W += s.has_null_byte + (lt == DFGPU_BOOL ? 1 : (lt == DFGPU_UTF8 ? s.max_len + 4 : type_width(lt)));
-    }
-    // ---- packed-key path: large input, fixed-width keys whose value ranges concatenate into 64 bits; with a fetch of at most n / 16 rows only from sort_topk_words_min_rows
-    // rows on and only when key and row number share one word (the select over the words; below, the byte-plane select that follows is the cheaper one)
-    const bool topk = fetch > 0 && fetch * 16 <= n;
-    if (n >= ctx->sort_packed_min_rows && ctx->sort_packed_keys && (!topk || n >= ctx->sort_topk_words_min_rows)) {
-      bool ok = true; PkCols pc{}; pc.n = k;
-      for (int c = 0; c < k && ok; c++) {
-        const dfgpu_array* a = cols[c];
-        ok = a->type != DFGPU_DICTIONARY && a->type != DFGPU_UTF8 && a->type != DFGPU_BOOL && type_width(a->type) > 0;
-        pc.c[c].v = ok ? a->values->ptr : nullptr; pc.c[c].valid = a->validity ? (const uint64_t*)a->validity->ptr : nullptr; pc.c[c].type = storage_type(a->type);
-        pc.c[c].desc = descending && descending[c]; pc.c[c].nulls_first = nulls_first ? nulls_first[c] : 1;
-      }
-      // The value ranges cost a pass over the key columns (0.64 ms for a Decimal128 + Date32 pair over 100 M rows).  A large input takes them from a sample first (every
-      // n / 2^19-th row), widened by 1/32 of the span on either side (the extremes of a sample lie inside the extremes of the rows); the encode pass checks every value
-      // against them and only a miss costs the exact pass.  The packed keys, and with them the indices, do not depend on which ranges were used as long as they hold every value.
-      const bool estimate = ok && ctx->sort_estimate_ranges && n >= ((int64_t)1 << 22) && !topk;      // a TopK asks for the extremes, which a sample misses more often than not (SUM per group over 20 M groups: the sampled maximum plus 1/32 of the span was too low, the sample pass and one encode pass wasted)
-      for (int attempt = estimate ? 0 : 1; ok && attempt < 2; attempt++) {
-        const bool sampled = attempt == 0;
-        const int nblk = (int)std::min<int64_t>(ctx->num_cus * 4, std::max<int64_t>(1, n / (sampled ? std::max<int64_t>(2, n >> 19) : 1) / BLOCK + 1)), nb = 1;
-        BufferPtr mm = alloc_buffer(ctx, (size_t)(nblk + 1) * MAX_KEYS * 32);
-        unsigned long long* folded = (unsigned long long*)mm->ptr + (size_t)nblk * MAX_KEYS * 4;
-        { KernelTimer kt_(ctx, sampled ? "sort_key_sample" : "sort_key_ranges");
-          hipLaunchKernelGGL(k_pk_minmax, dim3(nblk), dim3(BLOCK), 0, ctx->stream, pc, n, sampled ? std::max<int64_t>(2, n >> 19) : (int64_t)1, (unsigned long long*)mm->ptr);
-          hipLaunchKernelGGL(k_pk_minmax_fold, dim3(1), dim3(BLOCK), 0, ctx->stream, (const unsigned long long*)mm->ptr, nblk, k, folded); KERNEL_CHECK(); }
-        std::vector<uint64_t> h((size_t)MAX_KEYS * 4);
-        ctx->count_sync("sync:sort_key_ranges"); fetch_to_host(ctx, h.data(), folded, (size_t)k * 32);
-        int total_bits = 0; int bits_of[MAX_KEYS];
-        for (int c = 0; c < k && ok; c++) {
-          uint64_t mnh = ~0ull, mnl = ~0ull, mxh = 0, mxl = 0;
-          for (int b = 0; b < nb; b++) { const uint64_t* o = &h[((size_t)b * MAX_KEYS + c) * 4];
-            if (o[0] < mnh || (o[0] == mnh && o[1] < mnl)) { mnh = o[0]; mnl = o[1]; } if (mxh < o[2] || (mxh == o[2] && mxl < o[3])) { mxh = o[2]; mxl = o[3]; } }
-          uint64_t span = 1;            // a column of NULLs only: one (unused) value slot
-          if (!(mnh == ~0ull && mnl == ~0ull && mxh == 0 && mxl == 0)) {
-            unsigned __int128 mn = ((unsigned __int128)mnh << 64) | mnl, mx = ((unsigned __int128)mxh << 64) | mxl, d = mx - mn;
-            if (sampled) { const unsigned __int128 margin = (d >> 5) + 1; mn = mn > margin ? mn - margin : 0; mx = mx + margin < mx ? ~(unsigned __int128)0 : mx + margin; d = mx - mn; mnl = (uint64_t)mn; mnh = (uint64_t)(mn >> 64); }
-            if (d >= ((unsigned __int128)1 << 62)) { ok = false; break; }
-            span = (uint64_t)d + 1; pc.c[c].lo_bits = mnl; pc.c[c].hi_bits = mnh;
-          }
-          pc.c[c].span = span;
-          int b = 1; while (((span + 2) >> b) != 0 && b < 64) b++;       // offsets 0 .. span + 1
-          bits_of[c] = b; total_bits += b;
-        }
-        if (sampled && !(ok && total_bits <= 64)) { ok = true; continue; }          // the widened sample does not pack: the exact ranges may
-        if (ok && total_bits <= 64) {
-          int sh = total_bits; for (int c = 0; c < k; c++) { sh -= bits_of[c]; pc.c[c].shift = sh; }
-          int ib = 1; while (((uint64_t)(n - 1) >> ib) != 0) ib++;                     // bits of the largest row number
-          const bool word = total_bits + ib <= 64;
-          for (int c = 0; c < k; c++) { pc.c[c].bits = bits_of[c]; pc.c[c].sorted_dst = nullptr; }
-          BufferPtr k0 = alloc_buffer(ctx, (size_t)n * 8), k1 = alloc_buffer(ctx, (size_t)n * 8), v1 = word ? BufferPtr() : alloc_buffer(ctx, (size_t)n * 4);
-          ArrayHolder idx(new_fixed(ctx, DFGPU_UINT32, (word || topk) && fetch >= 0 && fetch < n ? fetch : n));
-          const int npass = (total_bits + 7) / 8, dbits = (total_bits + npass - 1) / npass;          // up to 8-bit digits, evened out over the passes (9-bit digits double the count table of the stable scatter: 4 passes of 9 measured 6.6 ms against 4.5 ms for 5 of 8 on 100 M rows)
-          // one-sweep passes: word mode, inputs large enough that a pass is bandwidth and not launches, row counts a 30-bit status value holds
-          const int os_r = ctx->sort_onesweep_rows == 16 && n >= ((int64_t)1 << 21) ? 16 : 8;          // 8192-row tiles from 2 M rows on (256 tiles: one per CU); below, the 4096-row tile fills the chip better
-          const bool onesweep = word && !topk && ctx->sort_onesweep_rows > 0 && npass <= 8 && n >= ctx->sort_onesweep_min_rows && n < ((int64_t)1 << 30);
-          const int64_t os_tiles = (n + (int64_t)os_r * OS_NT - 1) / ((int64_t)os_r * OS_NT);
-          BufferPtr os_buf; OsLayout L{}; uint32_t *os_hist = nullptr, *os_base = nullptr, *os_ticket = nullptr, *os_status = nullptr;
-          if (onesweep) {
-            L.npass = npass; for (int p = 0; p < npass; p++) { const int sh = p * dbits, bits = total_bits - sh < dbits ? total_bits - sh : dbits; L.shift[p] = sh + ib; L.mask[p] = (1u << bits) - 1u; }
-            const size_t head = (size_t)(8 * 256 * 2 + 64) * 4;
-            os_buf = alloc_buffer(ctx, head + (size_t)npass * (size_t)os_tiles * 256 * 4);
-            os_hist = (uint32_t*)os_buf->ptr; os_base = os_hist + 8 * 256; os_ticket = os_base + 8 * 256; os_status = os_ticket + 64;
-            HIP_CHECK(hipMemsetAsync(os_buf->ptr, 0, head + (size_t)npass * (size_t)os_tiles * 256 * 4, ctx->stream));
-          }
-          { KernelTimer kt_(ctx, "sort_key_encode");
-            if (sampled) HIP_CHECK(hipMemsetAsync(ctx->d_scratch64 + 14, 0, 8, ctx->stream));
-            if (onesweep) hipLaunchKernelGGL(k_pk_encode_hist, dim3(grid_for(n, BLOCK, ctx->num_cus * 8)), dim3(BLOCK), 0, ctx->stream, pc, n, (uint64_t*)k0->ptr, ib, sampled ? (uint32_t*)(ctx->d_scratch64 + 14) : (uint32_t*)nullptr, L, os_hist);
-            else hipLaunchKernelGGL(k_pk_encode, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, pc, n, (uint64_t*)k0->ptr, word || topk ? (uint32_t*)nullptr : (uint32_t*)idx.get()->values->ptr, word ? ib : 0,
-                               sampled ? (uint32_t*)(ctx->d_scratch64 + 14) : (uint32_t*)nullptr);
-            KERNEL_CHECK(); }
-          if (sampled) { const uint64_t miss = read_scratch(ctx, 14); ctx->count_sync("sync:sort_key_outside"); if (miss) continue; }       // some value lies outside the sampled ranges: exact pass
-          uint64_t* ka = (uint64_t*)k0->ptr; uint64_t* kb = (uint64_t*)k1->ptr; uint32_t* va = (uint32_t*)idx.get()->values->ptr; uint32_t* vb = word ? nullptr : (uint32_t*)v1->ptr;
-          bool fuse_finish = false; std::vector<ArrayHolder> sk_fused((size_t)k);
-          int64_t ns = n;                                // rows the passes sort
-          bool sorted_already = false; ArrayHolder rows;
-          if (topk) {
-            KernelTimer kt_(ctx, "sort_topk_words");
-            BufferPtr hist = alloc_buffer(ctx, 256 * 4 + 8);
-            int sh = total_bits + (word ? ib : 0), pshift = 0, has_prefix = 0; uint64_t prefix = 0; int64_t remaining = fetch, ncand = n;
-            const int grid = grid_for(n, BLOCK * 4, ctx->num_cus * 8);
-            while (sh > 0) {
-              const int bits = sh < 8 ? sh : 8; sh -= bits;
-              HIP_CHECK(hipMemsetAsync(hist->ptr, 0, 256 * 4, ctx->stream));
-              hipLaunchKernelGGL(k_ws_hist, dim3(grid), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)ka, n, sh, (1u << bits) - 1u, has_prefix, pshift, prefix, (uint32_t*)hist->ptr); KERNEL_CHECK();
-              uint32_t hh[256]; ctx->count_sync("sync:topk_histogram"); fetch_to_host(ctx, hh, hist->ptr, sizeof hh);
-              int64_t cum = 0; int d = 0;
-              for (; d < (1 << bits) - 1; d++) { if (cum + (int64_t)hh[d] >= remaining) break; cum += hh[d]; }
-              remaining -= cum; ncand = hh[d]; prefix = (prefix << bits) | (uint64_t)d; pshift = sh; has_prefix = 1;
-              if (ncand <= remaining + 4096) break;
-            }
-            ns = fetch - remaining + ncand;              // rows up to the chosen prefix: the fetch first of the sorted order are among them
-            if (word) {
-              unsigned long long* counter = (unsigned long long*)((uint32_t*)hist->ptr + 256);
-              HIP_CHECK(hipMemsetAsync(counter, 0, 8, ctx->stream));
-              hipLaunchKernelGGL(k_ws_collect, dim3(grid_for(n, BLOCK, ctx->num_cus * 16)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)ka, n, pshift, prefix, kb, counter, (uint64_t)ns); KERNEL_CHECK();
-              std::swap(ka, kb);
-              if (ns <= 16384) { hipLaunchKernelGGL(k_ws_rank_sort, dim3(grid_for(ns, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)ka, (int)ns, kb); KERNEL_CHECK(); std::swap(ka, kb); sorted_already = true; }
-            } else {
-              BufferPtr bm = alloc_buffer(ctx, (size_t)((n + 63) / 64) * 8);
-              hipLaunchKernelGGL(k_ws_mark, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)ka, n, pshift, prefix, (uint64_t*)bm->ptr); KERNEL_CHECK();
-              rows.a = mask_to_indices_uncounted(ctx, (const uint64_t*)bm->ptr, n);          // ascending rows; the first ns entries are written (ns is known from the histograms)
-              hipLaunchKernelGGL(k_ws_gather, dim3(grid_for(ns, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)ka, (const uint32_t*)rows.get()->values->ptr, ns, kb); KERNEL_CHECK();
-              std::swap(ka, kb); va = (uint32_t*)rows.get()->values->ptr;
-              if (ns <= 16384) { hipLaunchKernelGGL(k_ws_rank_sort_pairs, dim3(grid_for(ns, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)ka, (const uint32_t*)va, (int)ns, kb, vb); KERNEL_CHECK();
-                std::swap(ka, kb); std::swap(va, vb); sorted_already = true; }
-            }
-          }
-          if (sorted_already) {}
-          else if (onesweep) {
-            KernelTimer kt_(ctx, "sort_pass_onesweep");
-            hipLaunchKernelGGL(k_os_bases, dim3(npass), dim3(256), 0, ctx->stream, (const uint32_t*)os_hist, os_base);
-            // the last pass writes the result itself (row numbers + rebuilt key columns) when every key column can be rebuilt or none is asked for
-            fuse_finish = ctx->sort_onesweep_fused_finish;
-            const int64_t m = idx.get()->length;
-            if (fuse_finish && out_sorted) for (int c = 0; c < k; c++) if (!pc.c[c].valid) {
-              sk_fused[(size_t)c].a = new_fixed(ctx, cols[c]->type, m, cols[c]->precision, cols[c]->scale); pc.c[c].sorted_dst = sk_fused[(size_t)c].get()->values->ptr; }
-            for (int p = 0; p < npass; p++) {
-              const bool fin = fuse_finish && p == npass - 1;
-              OsFinish of{}; if (fin) { of.pc = pc; of.ib = ib; of.idx = (uint32_t*)idx.get()->values->ptr; of.m = m; }
-              const uint32_t* gb = os_base + p * 256; uint32_t* stp = os_status + (size_t)p * os_tiles * 256;
-#define OS_LAUNCH(R_, F_) hipLaunchKernelGGL((k_os_pass<R_, F_>), dim3((unsigned)os_tiles), dim3(OS_NT), 0, ctx->stream, (const uint64_t*)ka, kb, n, L.shift[p], L.mask[p], gb, stp, os_ticket + p, of, ctx->d_flags)
-              if (os_r == 16) { if (fin) OS_LAUNCH(16, true); else OS_LAUNCH(16, false); } else { if (fin) OS_LAUNCH(8, true); else OS_LAUNCH(8, false); }
-#undef OS_LAUNCH
-              std::swap(ka, kb);
-            }
-            KERNEL_CHECK();
-            { const int saved = ctx->defer_flag_checks; ctx->defer_flag_checks = 1; check_flags(ctx, "sort_onesweep"); ctx->defer_flag_checks = saved; }      // read with the next flag read-back (ctx_synchronize at the latest), no round trip of its own
-          }
-          // the words a select compacted arrive in no order: their passes also sort the row-number bits (ties = row order); everywhere else the input order breaks ties
-          const int sort_bits = topk && word ? total_bits + ib : total_bits, base_shift = word && !topk ? ib : 0;
-          const int npass_l = (sort_bits + 7) / 8, dbits_l = (sort_bits + npass_l - 1) / npass_l;
-          if (sorted_already || onesweep) {}
-          else for (int shift = 0; shift < sort_bits; shift += dbits_l) {
-            const int bits = sort_bits - shift < dbits_l ? sort_bits - shift : dbits_l; const bool last = shift + dbits_l >= sort_bits;
-            RpCols rc{};
-            if (word) { rc.n = 1; rc.c[0] = RpCol{ nullptr, kb, 8, RP_HASHKEY, 0 }; }       // the whole record is the word the digit is read from
-            else { rc.n = last ? 1 : 2; rc.c[0] = RpCol{ va, vb, 4, RP_RAW, 0 };
-              if (!last) rc.c[1] = RpCol{ nullptr, kb, 8, RP_HASHKEY, 0 }; }                // the last pass only needs the row ids
-            (void)rp_partition(ctx, RpHashDigit{ ka, shift + base_shift, (1u << bits) - 1u }, ns, 1u << bits, rc, true, ctx->d_scratch64 + 9, "sort_pass_hist", "sort_pass_scan", "sort_pass_scatter", false);
-            std::swap(ka, kb); std::swap(va, vb);
-          }
-          if (word) {
-            const int64_t m = idx.get()->length;
-            if (fuse_finish) { if (out_sorted) for (int c = 0; c < k; c++) out_sorted[c] = sk_fused[(size_t)c].release();
-              *out = idx.release(); return; }
-            std::vector<ArrayHolder> sk((size_t)k);
-            if (out_sorted) for (int c = 0; c < k; c++) if (!pc.c[c].valid) {          // a key column without NULLs comes back in sorted order for the price of its sequential write
-              sk[(size_t)c].a = new_fixed(ctx, cols[c]->type, m, cols[c]->precision, cols[c]->scale); pc.c[c].sorted_dst = sk[(size_t)c].get()->values->ptr; }
-            if (m) { KernelTimer kt_(ctx, "sort_finish");
-              hipLaunchKernelGGL(k_pk_finish, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, pc, (const uint64_t*)ka, m, ib, (uint32_t*)idx.get()->values->ptr); KERNEL_CHECK(); }
-            if (out_sorted) for (int c = 0; c < k; c++) out_sorted[c] = sk[(size_t)c].release();
-            *out = idx.release();
-            return;
-          }
-          if (topk) { HIP_CHECK(hipMemcpyAsync(idx.get()->values->ptr, va, (size_t)fetch * 4, hipMemcpyDeviceToDevice, ctx->stream)); *out = idx.release(); return; }     // the first fetch of the ns sorted rows
-          if (va != (uint32_t*)idx.get()->values->ptr) HIP_CHECK(hipMemcpyAsync(idx.get()->values->ptr, va, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-          if (fetch >= 0 && fetch < n) { dfgpu_array* s2 = nullptr; dfgpu_status st = dfgpu_array_slice(ctx, idx.get(), 0, fetch, &s2); if (st != DFGPU_OK) fail(st, "%s", ctx->err.c_str()); *out = s2; }
-          else *out = idx.release();
-          return;
-        }
-      }
-    }
-    ArrayHolder idx(new_fixed(ctx, DFGPU_UINT32, n));
-    launch_iota_u32(ctx, (uint32_t*)idx.get()->values->ptr, n, 0);
-    if (n > 1) {
-      BufferPtr planes = alloc_buffer(ctx, (size_t)W * n), varies = alloc_buffer(ctx, (size_t)W * 4, true);
-      hipLaunchKernelGGL(k_encode_sort_keys, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, sc, n, (uint8_t*)planes->ptr);
-      hipLaunchKernelGGL(k_plane_varies, dim3(grid_for(n, BLOCK * 16, 256), W), dim3(BLOCK), 0, ctx->stream, (const uint8_t*)planes->ptr, n, (uint32_t*)varies->ptr);
-      KERNEL_CHECK();
-      std::vector<uint32_t> h((size_t)W);
-      ctx->count_sync("sync:sort_planes"); fetch_to_host(ctx, h.data(), varies->ptr, h.size() * 4);
-      if (fetch > 0 && fetch * 16 <= n && n >= (1 << 16)) {          // TopK: select, then sort the few selected rows
-        std::vector<int> vp; for (int b = 0; b < W; b++) if (h[(size_t)b]) vp.push_back(b);
-        int64_t nwords = (n + 63) / 64, remaining = fetch, ncand = n; bool small = false;
-        BufferPtr cand = alloc_buffer(ctx, (size_t)nwords * 8), accept = alloc_buffer(ctx, (size_t)nwords * 8, true), hist = alloc_buffer(ctx, 256 * 4);
-        HIP_CHECK(hipMemsetAsync(cand->ptr, 0xFF, (size_t)nwords * 8, ctx->stream));        // bits >= n are masked by i < n in the kernel
-        KernelTimer kt_(ctx, "k_topk_select");
-        int grid = grid_for(nwords, BLOCK / WAVE, ctx->num_cus * 16);
-        int prev = -1, prev_digit = 0;
-        for (size_t it = 0; it <= vp.size() && !small; it++) {
-          int cur = it < vp.size() ? vp[it] : -1;
-          if (cur >= 0) HIP_CHECK(hipMemsetAsync(hist->ptr, 0, 256 * 4, ctx->stream));
-          hipLaunchKernelGGL(k_topk_step, dim3(grid), dim3(BLOCK), 0, ctx->stream, (const uint8_t*)planes->ptr, n, prev, prev_digit, cur, (uint64_t*)cand->ptr, (uint64_t*)accept->ptr, (uint32_t*)hist->ptr);
-          KERNEL_CHECK();
-          if (cur < 0) break;
-          uint32_t hh[256];
-          ctx->count_sync("sync:topk_histogram"); fetch_to_host(ctx, hh, hist->ptr, sizeof hh);
-          int64_t cum = 0; int d = 0;
-          for (; d < 255; d++) { if (cum + (int64_t)hh[d] >= remaining) break; cum += hh[d]; }
-          remaining -= cum; ncand = hh[d]; prev = cur; prev_digit = d;
-          if (ncand <= remaining + 4096) {                     // few enough: apply this decision and stop selecting
-            hipLaunchKernelGGL(k_topk_step, dim3(grid), dim3(BLOCK), 0, ctx->stream, (const uint8_t*)planes->ptr, n, prev, prev_digit, -1, (uint64_t*)cand->ptr, (uint64_t*)accept->ptr, (uint32_t*)hist->ptr);
-            KERNEL_CHECK(); small = true;
-          }
-        }
-        if (small) {
-          hipLaunchKernelGGL(k_or_words, dim3(grid_for(nwords, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)accept->ptr, (const uint64_t*)cand->ptr, (uint64_t*)accept->ptr, nwords);
-          KERNEL_CHECK();
-          ArrayHolder rows(mask_to_indices_impl(ctx, (const uint64_t*)accept->ptr, n));         // the top set plus boundary ties, ascending row order
-          std::vector<ArrayHolder> keys((size_t)k); std::vector<const dfgpu_array*> kp;
-          for (int c = 0; c < k; c++) { keys[(size_t)c].a = take_impl(ctx, cols[c], rows.get()->values->ptr, 4, nullptr, rows.get()->length); kp.push_back(keys[(size_t)c].get()); }
-          dfgpu_array* local = nullptr;
-          dfgpu_status st = dfgpu_sort_to_indices(ctx, kp.data(), descending, nulls_first, k, fetch, &local);      // small: the full path (stable)
-          if (st != DFGPU_OK) fail(st, "%s", ctx->err.c_str());
-          ArrayHolder lh(local);
-          *out = take_impl(ctx, rows.get(), lh.get()->values->ptr, 4, nullptr, lh.get()->length);
-          return;
-        }
-        // every varying plane is decided and the candidates (rows with identical keys) still outnumber what is needed: sort everything
-      }
-      RadixPlan p = plan_for(n);
-      BufferPtr tmp = alloc_buffer(ctx, (size_t)n * 4), hist = alloc_buffer(ctx, (size_t)256 * p.nb * 4);
-      uint32_t *v0 = (uint32_t*)idx.get()->values->ptr, *v1 = (uint32_t*)tmp->ptr;
-      if (n >= (1 << 20)) {
-        // Large inputs: a pass that looks its digit up by row id (plane[row]) is a random one-byte gather per row and pass -- 64-B sectors,
-        // twice (histogram + scatter): 13 GB per pass at 100 M rows.  Instead up to four varying planes at a time are packed into a u32 that
-        // MOVES with the row id (sequential 8 B per row and pass), fetched through the current order once per group of four.
-        std::vector<int> vp; for (int b = 0; b < W; b++) if (h[(size_t)b]) vp.push_back(b);
-        BufferPtr ka = alloc_buffer(ctx, (size_t)n * 4), kb = alloc_buffer(ctx, (size_t)n * 4), packed = alloc_buffer(ctx, (size_t)n * 4);
-        uint32_t *k0 = (uint32_t*)ka->ptr, *k1 = (uint32_t*)kb->ptr;
-        bool first = true;
-        for (int end = (int)vp.size(); end > 0; end -= 4) {
-          int beg = end - 4 < 0 ? 0 : end - 4, cnt = end - beg;
-          PackPlanes pp{}; pp.n = cnt; for (int j = 0; j < cnt; j++) pp.plane[j] = (const uint8_t*)planes->ptr + (int64_t)vp[(size_t)(end - 1 - j)] * n;      // byte 0 = least significant plane
-          hipLaunchKernelGGL(k_pack_planes, dim3(grid_for(n, BLOCK * 4)), dim3(BLOCK), 0, ctx->stream, pp, n, first ? k0 : (uint32_t*)packed->ptr);
-          KERNEL_CHECK();
-          if (!first) gather_u32(ctx, (const uint32_t*)packed->ptr, v0, n, k0);                 // the group's bytes in the order reached so far
-          for (int j = 0; j < cnt; j++) {
-            radix_pass(ctx, DigitKeys{ k0, 8 * j }, (const uint32_t*)k0, v0, k1, v1, n, (uint32_t*)hist->ptr, p);
-            std::swap(k0, k1); std::swap(v0, v1);
-          }
-          first = false;
-        }
-      } else if (n <= ctx->sort_one_block_max_rows && n <= OB_MAX) {
-        KernelTimer kt_(ctx, "radix_pass_one_block");
-        hipLaunchKernelGGL(k_rs_one_block, dim3(1), dim3(OB_NT), 0, ctx->stream, (const uint8_t*)planes->ptr, (int)n, W, (const uint32_t*)varies->ptr, (const uint32_t*)v0, v1);
-        KERNEL_CHECK(); std::swap(v0, v1);
-      } else if (p.nb <= 512 && ctx->sort_fused_small_passes) {
-        // two launches per varying plane: the histogram, then k_rs_plane_pass (scan folded into the scatter)
-        KernelTimer kt_(ctx, "radix_pass");
-        for (int b = W - 1; b >= 0; b--) {        // least significant plane first
-          if (!h[(size_t)b]) continue;
-          const uint8_t* plane = (const uint8_t*)planes->ptr + (int64_t)b * n;
-          hipLaunchKernelGGL((k_rs_hist<DigitPlane>), dim3(p.nb), dim3(BLOCK), 0, ctx->stream, DigitPlane{ plane }, (const uint32_t*)nullptr, (const uint32_t*)v0, n, p.chunk, p.nb, (uint32_t*)hist->ptr);
-          hipLaunchKernelGGL(k_rs_plane_pass, dim3(p.nb), dim3(BLOCK), 0, ctx->stream, plane, (const uint8_t*)nullptr, (const uint32_t*)v0, n, p.chunk, p.nb, (const uint32_t*)hist->ptr, (uint32_t*)nullptr, v1);
-          std::swap(v0, v1);
-        }
-        KERNEL_CHECK();
-      } else
-      for (int b = W - 1; b >= 0; b--) {        // least significant plane first
-        if (!h[(size_t)b]) continue;
-        radix_pass(ctx, DigitPlane{ (const uint8_t*)planes->ptr + (int64_t)b * n }, (const uint32_t*)nullptr, v0, (uint32_t*)nullptr, v1, n, (uint32_t*)hist->ptr, p);
-        std::swap(v0, v1);
-      }
-      if (v0 != (uint32_t*)idx.get()->values->ptr) HIP_CHECK(hipMemcpyAsync(idx.get()->values->ptr, v0, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (fetch >= 0 && fetch < n) { dfgpu_array* s = nullptr; dfgpu_status st = dfgpu_array_slice(ctx, idx.get(), 0, fetch, &s); if (st != DFGPU_OK) fail(st, "%s", ctx->err.c_str()); *out = s; }
-    else *out = idx.release();
+// ---------------------------------------------------------------------------------------------- host side: one function per route, sort_impl at the end calls them in order
+struct SortArgs {
+  const dfgpu_array* const* cols; const uint8_t* descending; const uint8_t* nulls_first; int32_t k; int64_t n, fetch; bool topk;      // topk: a fetch of at most n / 16 rows
+  int32_t desc(int c) const { return descending && descending[c]; }
+  int32_t nfirst(int c) const { return nulls_first ? nulls_first[c] : 1; }
+};
+// The two buffers of keys and the two of row ids the passes alternate between; every route leaves ka / va pointing at the current data.  The keys are the words of the
+// packed path, or the u32 keys that move with the row ids of a large byte-plane sort (nullptr where only row ids move)
+template <typename K>
+struct PingPong {
+  K *ka, *kb; uint32_t *va, *vb;
+  void swap() { std::swap(ka, kb); std::swap(va, vb); }
+  void swap_keys() { std::swap(ka, kb); }          // a step that moves the keys alone
+};
+static void sort_impl(dfgpu_ctx* ctx, const dfgpu_array* const* cols, const uint8_t* descending, const uint8_t* nulls_first, int32_t k, int64_t fetch, dfgpu_array** out, dfgpu_array** out_sorted);          // the byte-plane TopK sorts its selected rows through the whole path again
+
+// ---- shared by the packed-key and the byte-plane path
+// The digit holding the remaining-th row of a histogram (digits 0 .. last): the rows of the digits below it leave `remaining`, its own rows are the candidates left
+static int choose_digit(const uint32_t* hh, int last, int64_t& remaining, int64_t& ncand) {
+  int64_t cum = 0; int d = 0;
+  for (; d < last; d++) { if (cum + (int64_t)hh[d] >= remaining) break; cum += hh[d]; }
+  remaining -= cum; ncand = hh[d];
+  return d;
+}
+static dfgpu_array* slice_to_fetch(dfgpu_ctx* ctx, ArrayHolder& idx, int64_t fetch, int64_t n) {          // the first fetch of the n sorted row ids, or all of them
+  if (!(fetch >= 0 && fetch < n)) return idx.release();
+  dfgpu_array* s = nullptr; dfgpu_status st = dfgpu_array_slice(ctx, idx.get(), 0, fetch, &s); if (st != DFGPU_OK) fail(st, "%s", ctx->err.c_str());
+  return s;
+}
+
+// ---- arguments and layout: the checks and the byte-plane layout (W bytes per row).  A Utf8 column reads its longest value back here, before any packed-path work
+static int32_t max_utf8_len(dfgpu_ctx* ctx, const ColView& v, int64_t n) {
+  HIP_CHECK(hipMemsetAsync(ctx->d_scratch64 + 12, 0, 8, ctx->stream));
+  if (n) hipLaunchKernelGGL(k_max_utf8_len, dim3(grid_for(n, BLOCK * 8, 512)), dim3(BLOCK), 0, ctx->stream, v, n, (unsigned int*)(ctx->d_scratch64 + 12));
+  KERNEL_CHECK();
+  uint64_t ml = read_scratch(ctx, 12) & 0xFFFFFFFFull;
+  if (ml > 1024) fail(DFGPU_NOT_IMPLEMENTED, "Utf8 sort keys longer than 1024 bytes (%llu) are not supported on device", (unsigned long long)ml);
+  return (int32_t)ml;
+}
+static SortArgs sort_arguments(dfgpu_ctx* ctx, const dfgpu_array* const* cols, const uint8_t* descending, const uint8_t* nulls_first, int32_t k, int64_t fetch, dfgpu_array** out, SortCols& sc, int& W) {
+  if (!cols || k < 1 || !out) fail(DFGPU_INVALID_ARGUMENT, "Sort requires at least one column");
+  if (k > MAX_KEYS) fail(DFGPU_NOT_IMPLEMENTED, "more than %d sort columns", MAX_KEYS);
+  SortArgs a{ cols, descending, nulls_first, k, cols[0]->length, fetch, false };
+  a.topk = fetch > 0 && fetch * 16 <= a.n;
+  sc = SortCols{}; sc.n = k; W = 0;
+  for (int c = 0; c < k; c++) {
+    if (cols[c]->length != a.n) fail(DFGPU_INVALID_ARGUMENT, "sort columns differ in length");
+    int32_t lt = logical_type(cols[c]);
+    SortCol& s = sc.c[c]; s.v = make_view(cols[c]); s.byte_off = W; s.max_len = 0;
+    if (lt == DFGPU_UTF8) s.max_len = max_utf8_len(ctx, s.v, a.n);
+    s.has_null_byte = (s.v.validity || s.v.key_validity) ? 1 : 0; s.descending = a.desc(c); s.nulls_first = a.nfirst(c);
+    W += s.has_null_byte + (lt == DFGPU_BOOL ? 1 : (lt == DFGPU_UTF8 ? s.max_len + 4 : type_width(lt)));
   }
+  return a;
+}
+
+// ---- packed-key path: large input, fixed-width keys whose value ranges concatenate into 64 bits; with a fetch of at most n / 16 rows only from sort_topk_words_min_rows
+// rows on and only when key and row number share one word (the select over the words; below, the byte-plane select is the cheaper one)
+struct PkLayout { int total_bits, ib; bool word; };          // key bits, bits of the largest row number, and whether both share one 64-bit word (otherwise key and row id move as a pair)
+static bool pk_columns(const SortArgs& a, PkCols& pc) {          // false: some column is not a fixed-width value column
+  bool ok = true; pc = PkCols{}; pc.n = a.k;
+  for (int c = 0; c < a.k && ok; c++) {
+    const dfgpu_array* col = a.cols[c];
+    ok = col->type != DFGPU_DICTIONARY && col->type != DFGPU_UTF8 && col->type != DFGPU_BOOL && type_width(col->type) > 0;
+    pc.c[c].v = ok ? col->values->ptr : nullptr; pc.c[c].valid = col->validity ? (const uint64_t*)col->validity->ptr : nullptr; pc.c[c].type = storage_type(col->type);
+    pc.c[c].desc = a.desc(c); pc.c[c].nulls_first = a.nfirst(c);
+  }
+  return ok;
+}
+// One column's folded minimum and maximum (o: min high, min low, max high, max low; the order-preserving 128-bit patterns) -> lo / hi / span; returns the bits of its
+// offsets 0 .. span + 1, or 0 when the range is too wide to pack.  A sampled range is widened by 1/32 of the span on either side
+static int pk_column_range(PkCol& col, const uint64_t* o, bool sampled) {
+  uint64_t mnh = o[0], mnl = o[1]; const uint64_t mxh = o[2], mxl = o[3];
+  uint64_t span = 1;            // a column of NULLs only: one (unused) value slot
+  if (!(mnh == ~0ull && mnl == ~0ull && mxh == 0 && mxl == 0)) {
+    unsigned __int128 mn = ((unsigned __int128)mnh << 64) | mnl, mx = ((unsigned __int128)mxh << 64) | mxl, d = mx - mn;
+    if (sampled) { const unsigned __int128 margin = (d >> 5) + 1; mn = mn > margin ? mn - margin : 0; mx = mx + margin < mx ? ~(unsigned __int128)0 : mx + margin; d = mx - mn; mnl = (uint64_t)mn; mnh = (uint64_t)(mn >> 64); }
+    if (d >= ((unsigned __int128)1 << 62)) return 0;
+    span = (uint64_t)d + 1; col.lo_bits = mnl; col.hi_bits = mnh;
+  }
+  col.span = span;
+  int b = 1; while (((span + 2) >> b) != 0 && b < 64) b++;       // offsets 0 .. span + 1
+  return b;
+}
+// The value ranges cost a pass over the key columns (0.64 ms for a Decimal128 + Date32 pair over 100 M rows).  A large input takes them from a sample first (every
+// n / 2^19-th row), widened (the extremes of a sample lie inside the extremes of the rows); the encode pass checks every value against them and only a miss costs the
+// exact pass.  The packed keys, and with them the indices, do not depend on which ranges were used as long as they hold every value.
+// Launches min/max and fold, reads the four words per column back once, and returns whether the ranges pack into 64 bits (then pc and lay describe the packing)
+static bool pk_ranges(dfgpu_ctx* ctx, const SortArgs& a, PkCols& pc, bool sampled, PkLayout& lay) {
+  const int64_t n = a.n, step = sampled ? std::max<int64_t>(2, n >> 19) : (int64_t)1;
+  const int k = a.k, nblk = (int)std::min<int64_t>(ctx->num_cus * 4, std::max<int64_t>(1, n / step / BLOCK + 1));
+  BufferPtr mm = alloc_buffer(ctx, (size_t)(nblk + 1) * MAX_KEYS * 32);
+  unsigned long long* folded = (unsigned long long*)mm->ptr + (size_t)nblk * MAX_KEYS * 4;
+  { KernelTimer kt_(ctx, sampled ? "sort_key_sample" : "sort_key_ranges");
+    hipLaunchKernelGGL(k_pk_minmax, dim3(nblk), dim3(BLOCK), 0, ctx->stream, pc, n, step, (unsigned long long*)mm->ptr);
+    hipLaunchKernelGGL(k_pk_minmax_fold, dim3(1), dim3(BLOCK), 0, ctx->stream, (const unsigned long long*)mm->ptr, nblk, k, folded); KERNEL_CHECK(); }
+  std::vector<uint64_t> h((size_t)MAX_KEYS * 4);
+  ctx->count_sync("sync:sort_key_ranges"); fetch_to_host(ctx, h.data(), folded, (size_t)k * 32);
+  int total_bits = 0; int bits_of[MAX_KEYS];
+  for (int c = 0; c < k; c++) {
+    bits_of[c] = pk_column_range(pc.c[c], &h[(size_t)c * 4], sampled);
+    if (!bits_of[c]) return false;
+    total_bits += bits_of[c];
+  }
+  if (total_bits > 64) return false;
+  int sh = total_bits; for (int c = 0; c < k; c++) { sh -= bits_of[c]; pc.c[c].shift = sh; pc.c[c].bits = bits_of[c]; pc.c[c].sorted_dst = nullptr; }
+  int ib = 1; while (((uint64_t)(n - 1) >> ib) != 0) ib++;                     // bits of the largest row number
+  lay = PkLayout{ total_bits, ib, total_bits + ib <= 64 };
+  return true;
+}
+// one-sweep passes: the plan (rows per lane, tiles, digit of every pass) and the scratch, one allocation of four regions: histogram and base per pass and digit, a ticket
+// per pass, a status word per pass, tile and digit
+struct OneSweep { int rows = 8; int64_t tiles = 0; OsLayout L{}; BufferPtr buf; uint32_t *hist = nullptr, *base = nullptr, *ticket = nullptr, *status = nullptr; };
+static OneSweep make_onesweep(dfgpu_ctx* ctx, int64_t n, const PkLayout& lay, int npass, int dbits) {
+  OneSweep os;
+  os.rows = ctx->sort_onesweep_rows == 16 && n >= ((int64_t)1 << 21) ? 16 : 8;          // 8192-row tiles from 2 M rows on (256 tiles: one per CU); below, the 4096-row tile fills the chip better
+  os.tiles = (n + (int64_t)os.rows * OS_NT - 1) / ((int64_t)os.rows * OS_NT);
+  os.L.npass = npass;
+  for (int p = 0; p < npass; p++) { const int sh = p * dbits, bits = lay.total_bits - sh < dbits ? lay.total_bits - sh : dbits; os.L.shift[p] = sh + lay.ib; os.L.mask[p] = (1u << bits) - 1u; }
+  const size_t head = (size_t)(8 * 256 * 2 + 64) * 4;
+  os.buf = alloc_buffer(ctx, head + (size_t)npass * (size_t)os.tiles * 256 * 4);
+  os.hist = (uint32_t*)os.buf->ptr; os.base = os.hist + 8 * 256; os.ticket = os.base + 8 * 256; os.status = os.ticket + 64;
+  HIP_CHECK(hipMemsetAsync(os.buf->ptr, 0, head + (size_t)npass * (size_t)os.tiles * 256 * 4, ctx->stream));
+  return os;
+}
+// Both encode kernels (the one-sweep form counts every pass's histogram on the way).  Against sampled ranges the kernel counts the values outside them and the counter
+// is read back: false = some value lies outside, the exact ranges are needed
+static bool pk_encode(dfgpu_ctx* ctx, const PkCols& pc, int64_t n, const PkLayout& lay, const OneSweep* os, uint64_t* words, uint32_t* row_ids, bool sampled) {
+  uint32_t* outside = sampled ? (uint32_t*)(ctx->d_scratch64 + 14) : (uint32_t*)nullptr;
+  { KernelTimer kt_(ctx, "sort_key_encode");
+    if (sampled) HIP_CHECK(hipMemsetAsync(ctx->d_scratch64 + 14, 0, 8, ctx->stream));
+    if (os) hipLaunchKernelGGL(k_pk_encode_hist, dim3(grid_for(n, BLOCK, ctx->num_cus * 8)), dim3(BLOCK), 0, ctx->stream, pc, n, words, lay.ib, outside, os->L, os->hist);
+    else hipLaunchKernelGGL(k_pk_encode, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, pc, n, words, row_ids, lay.word ? lay.ib : 0, outside);
+    KERNEL_CHECK(); }
+  if (!sampled) return true;
+  const uint64_t miss = read_scratch(ctx, 14); ctx->count_sync("sync:sort_key_outside");
+  return miss == 0;
+}
+// ---- TopK over the packed keys: radix select.  A pass counts one 8-bit digit over the keys that share the digits chosen so far, the host picks the digit holding the
+// fetch-th key; it ends when at most fetch + 4096 rows are left up to the chosen prefix: those ns rows hold the fetch first of the sorted order
+struct WordPrefix { int pshift; uint64_t prefix; int64_t ns; };
+static WordPrefix ws_choose_prefix(dfgpu_ctx* ctx, const uint64_t* keys, int64_t n, int64_t fetch, int key_bits, uint32_t* hist) {
+  int sh = key_bits, pshift = 0, has_prefix = 0; uint64_t prefix = 0; int64_t remaining = fetch, ncand = n;
+  const int grid = grid_for(n, BLOCK * 4, ctx->num_cus * 8);
+  while (sh > 0) {
+    const int bits = sh < 8 ? sh : 8; sh -= bits;
+    HIP_CHECK(hipMemsetAsync(hist, 0, 256 * 4, ctx->stream));
+    hipLaunchKernelGGL(k_ws_hist, dim3(grid), dim3(BLOCK), 0, ctx->stream, keys, n, sh, (1u << bits) - 1u, has_prefix, pshift, prefix, hist); KERNEL_CHECK();
+    uint32_t hh[256]; ctx->count_sync("sync:topk_histogram"); fetch_to_host(ctx, hh, hist, sizeof hh);
+    const int d = choose_digit(hh, (1 << bits) - 1, remaining, ncand);
+    prefix = (prefix << bits) | (uint64_t)d; pshift = sh; has_prefix = 1;
+    if (ncand <= remaining + 4096) break;
+  }
+  return WordPrefix{ pshift, prefix, fetch - remaining + ncand };
+}
+// word mode: the words up to the prefix are compacted (in no order: every word is distinct, its low bits are the row number); up to 16384 are sorted by counting
+static bool ws_collect_words(dfgpu_ctx* ctx, PingPong<uint64_t>& pp, int64_t n, const WordPrefix& s, unsigned long long* counter) {
+  HIP_CHECK(hipMemsetAsync(counter, 0, 8, ctx->stream));
+  hipLaunchKernelGGL(k_ws_collect, dim3(grid_for(n, BLOCK, ctx->num_cus * 16)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)pp.ka, n, s.pshift, s.prefix, pp.kb, counter, (uint64_t)s.ns); KERNEL_CHECK();
+  pp.swap_keys();
+  if (s.ns > 16384) return false;
+  hipLaunchKernelGGL(k_ws_rank_sort, dim3(grid_for(s.ns, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)pp.ka, (int)s.ns, pp.kb); KERNEL_CHECK();
+  pp.swap_keys();
+  return true;
+}
+// pairs mode (keys may repeat): the rows up to the prefix are marked in a bitmap, listed in row order (`rows`, which pp.va then reads), their keys gathered
+static bool ws_collect_pairs(dfgpu_ctx* ctx, PingPong<uint64_t>& pp, int64_t n, const WordPrefix& s, ArrayHolder& rows) {
+  BufferPtr bm = alloc_buffer(ctx, (size_t)((n + 63) / 64) * 8);
+  hipLaunchKernelGGL(k_ws_mark, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)pp.ka, n, s.pshift, s.prefix, (uint64_t*)bm->ptr); KERNEL_CHECK();
+  rows.a = mask_to_indices_uncounted(ctx, (const uint64_t*)bm->ptr, n);          // ascending rows; the first ns entries are written (ns is known from the histograms)
+  hipLaunchKernelGGL(k_ws_gather, dim3(grid_for(s.ns, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)pp.ka, (const uint32_t*)rows.get()->values->ptr, s.ns, pp.kb); KERNEL_CHECK();
+  pp.swap_keys(); pp.va = (uint32_t*)rows.get()->values->ptr;
+  if (s.ns > 16384) return false;
+  hipLaunchKernelGGL(k_ws_rank_sort_pairs, dim3(grid_for(s.ns, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)pp.ka, (const uint32_t*)pp.va, (int)s.ns, pp.kb, pp.vb); KERNEL_CHECK();
+  pp.swap();
+  return true;
+}
+// Returns whether the small rank sort already ordered the ns rows it leaves in pp (otherwise the LSD passes follow)
+static bool topk_select_words(dfgpu_ctx* ctx, const SortArgs& a, const PkLayout& lay, PingPong<uint64_t>& pp, ArrayHolder& rows, int64_t& ns) {
+  KernelTimer kt_(ctx, "sort_topk_words");
+  BufferPtr hist = alloc_buffer(ctx, 256 * 4 + 8);
+  const WordPrefix s = ws_choose_prefix(ctx, pp.ka, a.n, a.fetch, lay.total_bits + (lay.word ? lay.ib : 0), (uint32_t*)hist->ptr);
+  ns = s.ns;
+  if (lay.word) return ws_collect_words(ctx, pp, a.n, s, (unsigned long long*)((uint32_t*)hist->ptr + 256));
+  return ws_collect_pairs(ctx, pp, a.n, s, rows);
+}
+// ---- the passes
+template <int R, bool FINISH>
+static void launch_os_pass(dfgpu_ctx* ctx, const OneSweep& os, int p, const PingPong<uint64_t>& pp, int64_t n, const OsFinish& of) {
+  const uint32_t* gb = os.base + p * 256; uint32_t* stp = os.status + (size_t)p * os.tiles * 256;
+  hipLaunchKernelGGL((k_os_pass<R, FINISH>), dim3((unsigned)os.tiles), dim3(OS_NT), 0, ctx->stream, (const uint64_t*)pp.ka, pp.kb, n, os.L.shift[p], os.L.mask[p], gb, stp, os.ticket + p, of, ctx->d_flags);
+}
+// The key columns the sorted words rebuild: a column without NULLs gets an array of m rows (sk[c]) that the finishing code writes in sorted order for the price of its
+// sequential write; the others stay empty
+static void alloc_sorted_keys(dfgpu_ctx* ctx, const SortArgs& a, PkCols& pc, int64_t m, std::vector<ArrayHolder>& sk) {
+  for (int c = 0; c < a.k; c++) {
+    if (pc.c[c].valid) continue;
+    sk[(size_t)c].a = new_fixed(ctx, a.cols[c]->type, m, a.cols[c]->precision, a.cols[c]->scale); pc.c[c].sorted_dst = sk[(size_t)c].get()->values->ptr;
+  }
+}
+// Every LSD pass as one launch over the histograms the encode pass counted.  With sort_onesweep_fused_finish the last pass writes the result itself (row numbers into idx,
+// rebuilt key columns into sk when they are asked for) instead of the words: returns whether it did
+static bool onesweep_passes(dfgpu_ctx* ctx, const SortArgs& a, PkCols& pc, const PkLayout& lay, const OneSweep& os, PingPong<uint64_t>& pp, dfgpu_array* idx, std::vector<ArrayHolder>& sk, bool want_sorted) {
+  KernelTimer kt_(ctx, "sort_pass_onesweep");
+  const int npass = os.L.npass;
+  hipLaunchKernelGGL(k_os_bases, dim3(npass), dim3(256), 0, ctx->stream, (const uint32_t*)os.hist, os.base);
+  const bool fuse_finish = ctx->sort_onesweep_fused_finish;
+  const int64_t m = idx->length;
+  if (fuse_finish && want_sorted) alloc_sorted_keys(ctx, a, pc, m, sk);
+  for (int p = 0; p < npass; p++) {
+    const bool fin = fuse_finish && p == npass - 1;
+    OsFinish of{}; if (fin) { of.pc = pc; of.ib = lay.ib; of.idx = (uint32_t*)idx->values->ptr; of.m = m; }
+    if (os.rows == 16) { if (fin) launch_os_pass<16, true>(ctx, os, p, pp, a.n, of); else launch_os_pass<16, false>(ctx, os, p, pp, a.n, of); }
+    else { if (fin) launch_os_pass<8, true>(ctx, os, p, pp, a.n, of); else launch_os_pass<8, false>(ctx, os, p, pp, a.n, of); }
+    pp.swap_keys();
+  }
+  KERNEL_CHECK();
+  { const int saved = ctx->defer_flag_checks; ctx->defer_flag_checks = 1; check_flags(ctx, "sort_onesweep"); ctx->defer_flag_checks = saved; }      // read with the next flag read-back (ctx_synchronize at the latest), no round trip of its own
+  return fuse_finish;
+}
+// The three-launch passes over ns rows, up to 8-bit digits evened out over the passes.  The words a select compacted arrive in no order: their passes also sort the
+// row-number bits (ties = row order); everywhere else the input order breaks ties
+static void lsd_passes(dfgpu_ctx* ctx, const SortArgs& a, const PkLayout& lay, PingPong<uint64_t>& pp, int64_t ns) {
+  const int sort_bits = a.topk && lay.word ? lay.total_bits + lay.ib : lay.total_bits, base_shift = lay.word && !a.topk ? lay.ib : 0;
+  const int npass_l = (sort_bits + 7) / 8, dbits_l = (sort_bits + npass_l - 1) / npass_l;
+  for (int shift = 0; shift < sort_bits; shift += dbits_l) {
+    const int bits = sort_bits - shift < dbits_l ? sort_bits - shift : dbits_l; const bool last = shift + dbits_l >= sort_bits;
+    RpCols rc{};
+    if (lay.word) { rc.n = 1; rc.c[0] = RpCol{ nullptr, pp.kb, 8, RP_HASHKEY, 0 }; }       // the whole record is the word the digit is read from
+    else { rc.n = last ? 1 : 2; rc.c[0] = RpCol{ pp.va, pp.vb, 4, RP_RAW, 0 };
+      if (!last) rc.c[1] = RpCol{ nullptr, pp.kb, 8, RP_HASHKEY, 0 }; }                // the last pass only needs the row ids
+    (void)rp_partition(ctx, RpHashDigit{ pp.ka, shift + base_shift, (1u << bits) - 1u }, ns, 1u << bits, rc, true, ctx->d_scratch64 + 9, "sort_pass_hist", "sort_pass_scan", "sort_pass_scatter", false);
+    pp.swap();
+  }
+}
+// ---- the result
+// word mode: a fused last pass has written everything and it is only handed over; otherwise k_pk_finish takes the row numbers and the key columns out of the sorted words
+static void emit_from_words(dfgpu_ctx* ctx, const SortArgs& a, PkCols& pc, int ib, const uint64_t* words, ArrayHolder& idx, std::vector<ArrayHolder>& sk, bool fused, dfgpu_array** out, dfgpu_array** out_sorted) {
+  const int64_t m = idx.get()->length;
+  if (!fused && out_sorted) alloc_sorted_keys(ctx, a, pc, m, sk);
+  if (!fused && m) { KernelTimer kt_(ctx, "sort_finish");
+    hipLaunchKernelGGL(k_pk_finish, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, ctx->stream, pc, words, m, ib, (uint32_t*)idx.get()->values->ptr); KERNEL_CHECK(); }
+  if (out_sorted) for (int c = 0; c < a.k; c++) out_sorted[c] = sk[(size_t)c].release();
+  *out = idx.release();
+}
+static void emit_row_ids(dfgpu_ctx* ctx, const SortArgs& a, const uint32_t* va, ArrayHolder& idx, dfgpu_array** out) {          // pairs mode: the row ids moved with the keys
+  if (a.topk) { HIP_CHECK(hipMemcpyAsync(idx.get()->values->ptr, va, (size_t)a.fetch * 4, hipMemcpyDeviceToDevice, ctx->stream)); *out = idx.release(); return; }     // the first fetch of the ns sorted rows
+  if (va != (uint32_t*)idx.get()->values->ptr) HIP_CHECK(hipMemcpyAsync(idx.get()->values->ptr, va, (size_t)a.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  *out = slice_to_fetch(ctx, idx, a.fetch, a.n);
+}
+// One attempt with the sampled or the exact ranges.  false: the ranges do not pack, or a value lies outside the sampled ones; nothing has been produced
+static bool pk_sort(dfgpu_ctx* ctx, const SortArgs& a, PkCols& pc, bool sampled, dfgpu_array** out, dfgpu_array** out_sorted) {
+  PkLayout lay{};
+  if (!pk_ranges(ctx, a, pc, sampled, lay)) return false;
+  const int64_t n = a.n; const bool word = lay.word;
+  BufferPtr k0 = alloc_buffer(ctx, (size_t)n * 8), k1 = alloc_buffer(ctx, (size_t)n * 8), v1 = word ? BufferPtr() : alloc_buffer(ctx, (size_t)n * 4);
+  ArrayHolder idx(new_fixed(ctx, DFGPU_UINT32, (word || a.topk) && a.fetch >= 0 && a.fetch < n ? a.fetch : n));
+  const int npass = (lay.total_bits + 7) / 8, dbits = (lay.total_bits + npass - 1) / npass;          // up to 8-bit digits, evened out over the passes (9-bit digits double the count table of the stable scatter: 4 passes of 9 measured 6.6 ms against 4.5 ms for 5 of 8 on 100 M rows)
+  // one-sweep passes: word mode, inputs large enough that a pass is bandwidth and not launches, row counts a 30-bit status value holds
+  const bool onesweep = word && !a.topk && ctx->sort_onesweep_rows > 0 && npass <= 8 && n >= ctx->sort_onesweep_min_rows && n < ((int64_t)1 << 30);
+  OneSweep os; if (onesweep) os = make_onesweep(ctx, n, lay, npass, dbits);
+  uint32_t* const ids = (uint32_t*)idx.get()->values->ptr;
+  if (!pk_encode(ctx, pc, n, lay, onesweep ? &os : nullptr, (uint64_t*)k0->ptr, word || a.topk ? (uint32_t*)nullptr : ids, sampled)) return false;
+  PingPong<uint64_t> pp{ (uint64_t*)k0->ptr, (uint64_t*)k1->ptr, ids, word ? nullptr : (uint32_t*)v1->ptr };
+  int64_t ns = n;                                // rows the passes sort
+  bool sorted_already = false, fused = false; ArrayHolder rows; std::vector<ArrayHolder> sk((size_t)a.k);          // rows: the row list of a pairs-mode select; sk: rebuilt key columns
+  if (a.topk) sorted_already = topk_select_words(ctx, a, lay, pp, rows, ns);
+  if (onesweep) fused = onesweep_passes(ctx, a, pc, lay, os, pp, idx.get(), sk, out_sorted != nullptr);          // never behind a select
+  else if (!sorted_already) lsd_passes(ctx, a, lay, pp, ns);
+  if (word) emit_from_words(ctx, a, pc, lay.ib, pp.ka, idx, sk, fused, out, out_sorted);
+  else emit_row_ids(ctx, a, pp.va, idx, out);
+  return true;
+}
+// false: the path does not apply (small input, a column that does not pack, ranges too wide for 64 bits) and the byte planes sort
+static bool sort_packed(dfgpu_ctx* ctx, const SortArgs& a, dfgpu_array** out, dfgpu_array** out_sorted) {
+  if (!(a.n >= ctx->sort_packed_min_rows && ctx->sort_packed_keys && (!a.topk || a.n >= ctx->sort_topk_words_min_rows))) return false;
+  PkCols pc;
+  if (!pk_columns(a, pc)) return false;
+  // a TopK asks for the extremes, which a sample misses more often than not (SUM per group over 20 M groups: the sampled maximum plus 1/32 of the span was too low, the sample pass and one encode pass wasted)
+  const bool estimate = ctx->sort_estimate_ranges && a.n >= ((int64_t)1 << 22) && !a.topk;
+  if (estimate && pk_sort(ctx, a, pc, true, out, out_sorted)) return true;
+  return pk_sort(ctx, a, pc, false, out, out_sorted);          // no sample, the widened sample does not pack (the exact ranges may), or a value outside it
+}
+
+// ---- byte-plane path: every key becomes W bytes whose byte-wise order is the sort order, stored as W planes of n bytes; LSD passes over the planes that vary
+struct PlaneKeys { BufferPtr planes, varies; std::vector<uint32_t> h; int W; };          // varies / h: per plane, non-zero when its byte differs between rows (device / host copy)
+static PlaneKeys encode_planes(dfgpu_ctx* ctx, const SortCols& sc, int W, int64_t n) {
+  PlaneKeys pk{ alloc_buffer(ctx, (size_t)W * n), alloc_buffer(ctx, (size_t)W * 4, true), std::vector<uint32_t>((size_t)W), W };
+  hipLaunchKernelGGL(k_encode_sort_keys, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, sc, n, (uint8_t*)pk.planes->ptr);
+  hipLaunchKernelGGL(k_plane_varies, dim3(grid_for(n, BLOCK * 16, 256), W), dim3(BLOCK), 0, ctx->stream, (const uint8_t*)pk.planes->ptr, n, (uint32_t*)pk.varies->ptr);
+  KERNEL_CHECK();
+  ctx->count_sync("sync:sort_planes"); fetch_to_host(ctx, pk.h.data(), pk.varies->ptr, pk.h.size() * 4);
+  return pk;
+}
+static std::vector<int> varying_planes(const PlaneKeys& pk) {          // most significant first
+  std::vector<int> vp; for (int b = 0; b < pk.W; b++) if (pk.h[(size_t)b]) vp.push_back(b);
+  return vp;
+}
+// TopK, the select: plane by plane from the most significant, k_topk_step applies the digit chosen for the previous plane to the candidate and accept bitmaps and counts
+// the current plane's digits over the candidates; the host picks the digit holding the fetch-th row.  true: few enough candidates are left and the last decision is applied
+static bool topk_planes_narrow(dfgpu_ctx* ctx, const PlaneKeys& pk, int64_t n, int64_t fetch, int grid, uint64_t* cand, uint64_t* accept, uint32_t* hist) {
+  const std::vector<int> vp = varying_planes(pk);
+  int64_t remaining = fetch, ncand = n;
+  int prev = -1, prev_digit = 0;
+  for (size_t it = 0; it <= vp.size(); it++) {
+    int cur = it < vp.size() ? vp[it] : -1;
+    if (cur >= 0) HIP_CHECK(hipMemsetAsync(hist, 0, 256 * 4, ctx->stream));
+    hipLaunchKernelGGL(k_topk_step, dim3(grid), dim3(BLOCK), 0, ctx->stream, (const uint8_t*)pk.planes->ptr, n, prev, prev_digit, cur, cand, accept, hist);
+    KERNEL_CHECK();
+    if (cur < 0) break;
+    uint32_t hh[256];
+    ctx->count_sync("sync:topk_histogram"); fetch_to_host(ctx, hh, hist, sizeof hh);
+    prev_digit = choose_digit(hh, 255, remaining, ncand); prev = cur;
+    if (ncand > remaining + 4096) continue;
+    hipLaunchKernelGGL(k_topk_step, dim3(grid), dim3(BLOCK), 0, ctx->stream, (const uint8_t*)pk.planes->ptr, n, prev, prev_digit, -1, cand, accept, hist);          // few enough: apply this decision and stop selecting
+    KERNEL_CHECK();
+    return true;
+  }
+  return false;
+}
+// TopK: select, then sort the few selected rows (the top set plus boundary ties) through the full path, which is stable.  false: every varying plane is decided and the
+// candidates (rows with identical keys) still outnumber what is needed: the caller sorts everything
+static bool topk_select_planes(dfgpu_ctx* ctx, const SortArgs& a, const PlaneKeys& pk, dfgpu_array** out) {
+  const int64_t n = a.n, nwords = (n + 63) / 64;
+  BufferPtr cand = alloc_buffer(ctx, (size_t)nwords * 8), accept = alloc_buffer(ctx, (size_t)nwords * 8, true), hist = alloc_buffer(ctx, 256 * 4);
+  HIP_CHECK(hipMemsetAsync(cand->ptr, 0xFF, (size_t)nwords * 8, ctx->stream));        // bits >= n are masked by i < n in the kernel
+  KernelTimer kt_(ctx, "k_topk_select");
+  const int grid = grid_for(nwords, BLOCK / WAVE, ctx->num_cus * 16);
+  if (!topk_planes_narrow(ctx, pk, n, a.fetch, grid, (uint64_t*)cand->ptr, (uint64_t*)accept->ptr, (uint32_t*)hist->ptr)) return false;
+  hipLaunchKernelGGL(k_or_words, dim3(grid_for(nwords, BLOCK)), dim3(BLOCK), 0, ctx->stream, (const uint64_t*)accept->ptr, (const uint64_t*)cand->ptr, (uint64_t*)accept->ptr, nwords);
+  KERNEL_CHECK();
+  ArrayHolder rows(mask_to_indices_impl(ctx, (const uint64_t*)accept->ptr, n));         // ascending row order
+  std::vector<ArrayHolder> keys((size_t)a.k); std::vector<const dfgpu_array*> kp;
+  for (int c = 0; c < a.k; c++) { keys[(size_t)c].a = take_impl(ctx, a.cols[c], rows.get()->values->ptr, 4, nullptr, rows.get()->length); kp.push_back(keys[(size_t)c].get()); }
+  ArrayHolder lh;
+  sort_impl(ctx, kp.data(), a.descending, a.nulls_first, a.k, a.fetch, &lh.a, nullptr);
+  *out = take_impl(ctx, rows.get(), lh.get()->values->ptr, 4, nullptr, lh.get()->length);
+  return true;
+}
+// Large inputs (>= 2^20 rows): a pass that looks its digit up by row id (plane[row]) is a random one-byte gather per row and pass -- 64-B sectors, twice (histogram +
+// scatter): 13 GB per pass at 100 M rows.  Instead up to four varying planes at a time are packed into a u32 that MOVES with the row id (sequential 8 B per row and pass),
+// fetched through the current order once per group of four.
+static void planes_moving_keys(dfgpu_ctx* ctx, const PlaneKeys& pk, int64_t n, PingPong<uint32_t>& pp, uint32_t* hist, RadixPlan p) {
+  const std::vector<int> vp = varying_planes(pk);
+  BufferPtr ka = alloc_buffer(ctx, (size_t)n * 4), kb = alloc_buffer(ctx, (size_t)n * 4), packed = alloc_buffer(ctx, (size_t)n * 4);
+  pp.ka = (uint32_t*)ka->ptr; pp.kb = (uint32_t*)kb->ptr;
+  bool first = true;
+  for (int end = (int)vp.size(); end > 0; end -= 4) {
+    int beg = end - 4 < 0 ? 0 : end - 4, cnt = end - beg;
+    PackPlanes pl{}; pl.n = cnt; for (int j = 0; j < cnt; j++) pl.plane[j] = (const uint8_t*)pk.planes->ptr + (int64_t)vp[(size_t)(end - 1 - j)] * n;      // byte 0 = least significant plane
+    hipLaunchKernelGGL(k_pack_planes, dim3(grid_for(n, BLOCK * 4)), dim3(BLOCK), 0, ctx->stream, pl, n, first ? pp.ka : (uint32_t*)packed->ptr);
+    KERNEL_CHECK();
+    if (!first) gather_u32(ctx, (const uint32_t*)packed->ptr, pp.va, n, pp.ka);                 // the group's bytes in the order reached so far
+    for (int j = 0; j < cnt; j++) {
+      radix_pass(ctx, DigitKeys{ pp.ka, 8 * j }, (const uint32_t*)pp.ka, pp.va, pp.kb, pp.vb, n, hist, p);
+      pp.swap();
+    }
+    first = false;
+  }
+  pp.ka = pp.kb = nullptr;          // the key buffers end here
+}
+static void planes_one_block(dfgpu_ctx* ctx, const PlaneKeys& pk, int64_t n, PingPong<uint32_t>& pp) {          // up to 8192 rows: every pass inside one launch of one workgroup
+  KernelTimer kt_(ctx, "radix_pass_one_block");
+  hipLaunchKernelGGL(k_rs_one_block, dim3(1), dim3(OB_NT), 0, ctx->stream, (const uint8_t*)pk.planes->ptr, (int)n, pk.W, (const uint32_t*)pk.varies->ptr, (const uint32_t*)pp.va, pp.vb);
+  KERNEL_CHECK(); pp.swap();
+}
+static void planes_fused_small(dfgpu_ctx* ctx, const PlaneKeys& pk, int64_t n, PingPong<uint32_t>& pp, uint32_t* hist, RadixPlan p) {          // two launches per varying plane: the histogram, then k_rs_plane_pass (scan folded into the scatter)
+  KernelTimer kt_(ctx, "radix_pass");
+  for (int b = pk.W - 1; b >= 0; b--) {        // least significant plane first
+    if (!pk.h[(size_t)b]) continue;
+    const uint8_t* plane = (const uint8_t*)pk.planes->ptr + (int64_t)b * n;
+    hipLaunchKernelGGL((k_rs_hist<DigitPlane>), dim3(p.nb), dim3(BLOCK), 0, ctx->stream, DigitPlane{ plane }, (const uint32_t*)nullptr, (const uint32_t*)pp.va, n, p.chunk, p.nb, hist);
+    hipLaunchKernelGGL(k_rs_plane_pass, dim3(p.nb), dim3(BLOCK), 0, ctx->stream, plane, (const uint8_t*)nullptr, (const uint32_t*)pp.va, n, p.chunk, p.nb, (const uint32_t*)hist, (uint32_t*)nullptr, pp.vb);
+    pp.swap();
+  }
+  KERNEL_CHECK();
+}
+static void planes_three_launch(dfgpu_ctx* ctx, const PlaneKeys& pk, int64_t n, PingPong<uint32_t>& pp, uint32_t* hist, RadixPlan p) {          // histogram, scan, scatter per varying plane
+  for (int b = pk.W - 1; b >= 0; b--) {        // least significant plane first
+    if (!pk.h[(size_t)b]) continue;
+    radix_pass(ctx, DigitPlane{ (const uint8_t*)pk.planes->ptr + (int64_t)b * n }, (const uint32_t*)nullptr, pp.va, (uint32_t*)nullptr, pp.vb, n, hist, p);
+    pp.swap();
+  }
+}
+static void sort_planes(dfgpu_ctx* ctx, const SortArgs& a, const SortCols& sc, int W, dfgpu_array** out) {
+  const int64_t n = a.n;
+  ArrayHolder idx(new_fixed(ctx, DFGPU_UINT32, n));
+  launch_iota_u32(ctx, (uint32_t*)idx.get()->values->ptr, n, 0);
+  if (n > 1) {
+    const PlaneKeys pk = encode_planes(ctx, sc, W, n);
+    if (a.topk && n >= (1 << 16) && topk_select_planes(ctx, a, pk, out)) return;
+    RadixPlan p = plan_for(n);
+    BufferPtr tmp = alloc_buffer(ctx, (size_t)n * 4), hist = alloc_buffer(ctx, (size_t)256 * p.nb * 4);
+    PingPong<uint32_t> pp{ nullptr, nullptr, (uint32_t*)idx.get()->values->ptr, (uint32_t*)tmp->ptr };
+    if (n >= (1 << 20)) planes_moving_keys(ctx, pk, n, pp, (uint32_t*)hist->ptr, p);
+    else if (n <= ctx->sort_one_block_max_rows && n <= OB_MAX) planes_one_block(ctx, pk, n, pp);
+    else if (p.nb <= 512 && ctx->sort_fused_small_passes) planes_fused_small(ctx, pk, n, pp, (uint32_t*)hist->ptr, p);
+    else planes_three_launch(ctx, pk, n, pp, (uint32_t*)hist->ptr, p);
+    if (pp.va != (uint32_t*)idx.get()->values->ptr) HIP_CHECK(hipMemcpyAsync(idx.get()->values->ptr, pp.va, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  *out = slice_to_fetch(ctx, idx, a.fetch, n);
+}
+
+static void sort_impl(dfgpu_ctx* ctx, const dfgpu_array* const* cols, const uint8_t* descending, const uint8_t* nulls_first, int32_t k, int64_t fetch, dfgpu_array** out, dfgpu_array** out_sorted) {
+  SortCols sc; int W;
+  const SortArgs a = sort_arguments(ctx, cols, descending, nulls_first, k, fetch, out, sc, W);
+  if (!sort_packed(ctx, a, out, out_sorted)) sort_planes(ctx, a, sc, W, out);
 }
 extern "C" dfgpu_status dfgpu_sort_to_indices(dfgpu_ctx* ctx, const dfgpu_array* const* cols, const uint8_t* descending, const uint8_t* nulls_first, int32_t k, int64_t fetch, dfgpu_array** out) {
   return guard(ctx, [&] { sort_impl(ctx, cols, descending, nulls_first, k, fetch, out, nullptr); });

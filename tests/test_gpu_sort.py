@@ -89,18 +89,17 @@ def test_topk_selection_equals_full_sort_then_slice(ctx, kind, desc, nf_first):
         assert np.array_equal(got, full[:fetch]), f"fetch={fetch}"
 
 
-@pytest.mark.parametrize("desc,nf_first", [(False, True), (True, False)])
-def test_utf8_and_mixed_sort_keys(ctx, desc, nf_first):
-    """Q1 sorts on two Utf8 columns (tpch/q1.slt.part SortExec [l_returnflag ASC, l_linestatus ASC]): byte-wise order, prefix first."""
+def test_utf8_and_mixed_sort_keys(ctx):
+    """Q1 sorts on two Utf8 columns (tpch/q1.slt.part SortExec [l_returnflag ASC, l_linestatus ASC]): byte-wise order, prefix first; ASC NULLS FIRST and DESC NULLS LAST."""
     words = ["", "a", "ab", "abc", "b", "A", "R", "N", "O", "F", "zz", "日本", "a\x00", "ab\x00\x00"]
-    for n, nf in [(0, 0), (1, 0), (300, 0.2), (20000, 0.05)]:
+    for desc, nf_first, n, nf in [(d, f, n, nf) for d, f in [(False, True), (True, False)] for n, nf in [(0, 0), (1, 0), (300, 0.2), (20000, 0.05)]]:
         a = pa.array([None if RNG.random() < nf else words[i] for i in RNG.integers(0, len(words), n)], type=pa.utf8())
         b = rand_array("int32", n, 0.1, RNG)
         c = pa.array([None if RNG.random() < nf else "x" * int(k) for k in RNG.integers(0, 40, n)], type=pa.utf8()).dictionary_encode()
         got = ctx.sort_to_indices([ctx.from_arrow(a)], [desc], [nf_first]).to_numpy()
-        assert np.array_equal(got, po.lexsort_to_indices([a], [desc], [nf_first])), f"n={n}"
+        assert np.array_equal(got, po.lexsort_to_indices([a], [desc], [nf_first])), f"desc={desc} n={n}"
         got3 = ctx.sort_to_indices([ctx.from_arrow(c), ctx.from_arrow(a), ctx.from_arrow(b)], [desc, not desc, False], [nf_first, True, False]).to_numpy()
-        assert np.array_equal(got3, po.lexsort_to_indices([c, a, b], [desc, not desc, False], [nf_first, True, False]))
+        assert np.array_equal(got3, po.lexsort_to_indices([c, a, b], [desc, not desc, False], [nf_first, True, False])), f"desc={desc} n={n}"
 
 
 def test_utf8_sort_key_too_long_reports_not_implemented(ctx):
@@ -350,6 +349,71 @@ def test_topk_over_packed_words_equals_sort_then_slice(ctx, shape, fetch):
     assert np.array_equal(got.astype(np.int64), want[:fetch])
 
 
+def test_sorted_key_columns_come_back_behind_the_word_topk(ctx):
+    """dfgpu_sort_to_indices_keys with fetch <= n / 16 on the select over the packed words: the result has `fetch` rows and the finishing pass rebuilds the key columns over
+    those rows alone.  330 001 rows (both thresholds moved down to 2), two Int64 keys without NULLs of 20 + 18 key bits beside 19 row bits (one word), DESC on the first;
+    fetch 5000 leaves at most 5000 + 4096 <= 16384 compacted words (sorted by counting), fetch 20 000 more than 16384 (the LSD passes).  Keys of 31 + 26 bits do not share
+    a word with the row number: the indices are the same stable order and no column comes back."""
+    rng = np.random.default_rng(41)
+    n = 330_001
+    desc, nf = [True, False], [True, False]
+    for shape, fetches in [("one_word", (5000, 20_000)), ("wide_keys_not_a_word", (5000,))]:
+        if shape == "one_word":
+            a = rng.integers(0, (1 << 20) - 3, n).astype(np.int64); b = rng.integers(0, (1 << 18) - 3, n).astype(np.int64)
+        else:
+            a = rng.integers(0, 1 << 30, 1000)[rng.integers(0, 1000, n)].astype(np.int64); b = rng.integers(0, 1 << 25, 50)[rng.integers(0, 50, n)].astype(np.int64)
+        cols = [pa.array(a), pa.array(b)]
+        full = np.lexsort((np.arange(n), b, -a))
+        dcols = [ctx.from_arrow(c) for c in cols]
+        for fetch in fetches:
+            want = full[:fetch]
+            ctx.profile_select(None); ctx.profile_enable(True); ctx.profile_read()
+            try:
+                ctx.set_option("sort_packed_min_rows", 2); ctx.set_option("sort_topk_words_min_rows", 2)
+                idx, sk = ctx.sort_to_indices_keys(dcols, desc, nf, fetch=fetch)
+                ks = set(ctx.profile_read())
+            finally:
+                ctx.profile_enable(False); ctx.set_option("sort_packed_min_rows", 1 << 20); ctx.set_option("sort_topk_words_min_rows", 1 << 23)
+            assert "sort_topk_words" in ks, (shape, fetch)
+            assert np.array_equal(idx.to_numpy().astype(np.int64), want), (shape, fetch)
+            if shape == "one_word":
+                for c, k in zip(cols, sk):
+                    assert k is not None and k.to_arrow().equals(c.take(pa.array(want))), (shape, fetch)
+            else:
+                assert sk == [None, None]
+
+
+def test_sampled_ranges_that_do_not_pack_where_the_exact_ranges_do(ctx):
+    """Two Int64 columns holding [0, 2^32 - 4] with both extremes present: the exact ranges take 32 + 32 = 64 bits (offsets 0 .. span + 1 with span = 2^32 - 3) and pack,
+    key and row id moving as a pair; the sampled ranges, widened by 1/32 of the span on either side, take 33 bits each, 66 in all, and do not.  The sort must then take the
+    exact ranges and stay on the packed path (no byte-plane pass) instead of giving the packed path up."""
+    rng = np.random.default_rng(43)
+    n = (1 << 22) + 4321
+    top = (1 << 32) - 4
+    a = rng.integers(0, top + 1, n).astype(np.int64); b = rng.integers(0, top + 1, n).astype(np.int64)
+    a[1] = 0; a[3] = top; b[5] = top; b[7] = 0                              # the extremes, on rows the strided sample does not visit
+
+    def key_bits(lo, hi, sampled):                                         # the host's arithmetic: bits of the offsets 0 .. span + 1
+        d = hi - lo
+        if sampled:
+            d += 2 * ((d >> 5) + 1)
+        return (d + 3).bit_length()
+    step = max(2, n >> 19)
+    exact = [key_bits(int(c.min()), int(c.max()), False) for c in (a, b)]
+    sampled = [key_bits(int(c[::step].min()), int(c[::step].max()), True) for c in (a, b)]
+    assert exact == [32, 32] and sampled == [33, 33]
+    cols = [pa.array(a), pa.array(b)]
+    ctx.profile_select(None); ctx.profile_enable(True); ctx.profile_read()
+    try:
+        got = ctx.sort_to_indices([ctx.from_arrow(c) for c in cols], [False, False], [True, True]).to_numpy()
+        ks = set(ctx.profile_read())
+    finally:
+        ctx.profile_enable(False)
+    assert np.array_equal(got.astype(np.int64), np.lexsort((np.arange(n), b, a)))
+    assert {"sort_key_sample", "sort_key_ranges", "sort_key_encode", "sort_pass_scatter"} <= ks
+    assert "radix_pass" not in ks
+
+
 @pytest.mark.parametrize("n", [2, 63, 255, 4097, 8192, 8193])
 def test_sorts_of_one_workgroup_run_every_pass_in_one_launch(ctx, n):
     """Up to 8192 rows every varying key byte's pass runs inside ONE launch of one workgroup (k_rs_one_block: row ids in LDS, four barriers per pass): the indices are the
@@ -376,10 +440,10 @@ def test_sorts_of_one_workgroup_run_every_pass_in_one_launch(ctx, n):
     assert np.array_equal(got.astype(np.int64), np.array(order, dtype=np.int64))
 
 
-@pytest.mark.parametrize("fetch", [None, 900_000])
-def test_sort_exec_gathers_other_columns_behind_one_word_keys(ctx, fetch):
+def test_sort_exec_gathers_other_columns_behind_one_word_keys(ctx):
     """A sort of 2^20 + 555 rows whose keys and row number share one word (the one-launch passes): the indices equal numpy's stable lexsort, and SortExec's output over a
-    batch with 8-, 4- and 16-byte, nullable and Utf8 columns beside the keys == the batch taken through those indices."""
+    batch with 8-, 4- and 16-byte, nullable and Utf8 columns beside the keys == the batch taken through those indices; without a fetch and with one of 900 000 rows, over
+    the same columns and one reference order."""
     import decimal
     from dfgpu import physical_plan as ops
     rng = np.random.default_rng(61)
@@ -390,16 +454,18 @@ def test_sort_exec_gathers_other_columns_behind_one_word_keys(ctx, fetch):
     pn = pa.array(rng.integers(0, 100, n).astype(np.int64), mask=rng.random(n) < 0.2)
     ps = pa.array(np.array(["a", "bb", "ccc"], dtype=object)[rng.integers(0, 3, n)], type=pa.utf8())
     keys = [ctx.from_arrow(pa.array(k1)), ctx.from_arrow(pa.array(k2))]
-    idx, _ = ctx.sort_to_indices_keys(keys, [True, False], [True, True], fetch=fetch)
-    want_order = np.lexsort((np.arange(n), k2, -k1.astype(np.int64)))[:fetch]
-    assert np.array_equal(idx.to_numpy().astype(np.int64), want_order)
-    # through SortExec
+    full_order = np.lexsort((np.arange(n), k2, -k1.astype(np.int64)))
     t = pa.table({"k1": pa.array(k1), "k2": pa.array(k2), "p8": pa.array(p8), "p4": pa.array(p4), "pn": pn, "p16": p16, "ps": ps})
     batch = ops.batch_from_arrow(ctx, t)
     tc = ops.TaskContext(ctx, batch_size=8192)
-    mk = lambda: ops.SortExec([ops.PhysicalSortExpr(ops.Column("k1", 0), True, True), ops.PhysicalSortExpr(ops.Column("k2", 1), False, True)], ops.MemoryExec([[batch]], batch.schema), fetch=fetch)
-    out = pa.concat_tables([b.to_arrow() for b in mk().execute(0, tc)]).combine_chunks()
-    assert out.equals(t.take(pa.array(want_order)).combine_chunks())
+    for fetch in (None, 900_000):
+        idx, _ = ctx.sort_to_indices_keys(keys, [True, False], [True, True], fetch=fetch)
+        want_order = full_order[:fetch]
+        assert np.array_equal(idx.to_numpy().astype(np.int64), want_order), fetch
+        # through SortExec
+        mk = lambda: ops.SortExec([ops.PhysicalSortExpr(ops.Column("k1", 0), True, True), ops.PhysicalSortExpr(ops.Column("k2", 1), False, True)], ops.MemoryExec([[batch]], batch.schema), fetch=fetch)
+        out = pa.concat_tables([b.to_arrow() for b in mk().execute(0, tc)]).combine_chunks()
+        assert out.equals(t.take(pa.array(want_order)).combine_chunks()), fetch
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3, 4, 5, 6])
