@@ -23,6 +23,8 @@ OP_AND, OP_OR = 20, 21
 # join types (datafusion/common/src/join_type.rs:30-47)
 JOIN_INNER, JOIN_LEFT, JOIN_RIGHT, JOIN_FULL, JOIN_LEFT_SEMI, JOIN_RIGHT_SEMI, JOIN_LEFT_ANTI, JOIN_RIGHT_ANTI = range(8)
 AGG_SUM, AGG_AVG, AGG_COUNT, AGG_MIN, AGG_MAX = range(5)
+AGG_COUNT_DISTINCT = 5                                                           # plan layer only (include/dfgpu_exec.h)
+AGG_VAR_SAMP, AGG_VAR_POP, AGG_STDDEV_SAMP, AGG_STDDEV_POP = 6, 7, 8, 9          # dfgpu_moments_* (their own accumulator type)
 
 STATUS_NAMES = {0: "Ok", 1: "Execution", 2: "Internal", 3: "ResourcesExhausted", 4: "NotImplemented", 5: "InvalidArgument"}
 
@@ -161,6 +163,13 @@ PROTOTYPES = {
     "dfgpu_acc_state": (C.c_int32, [_P, _P, _PP, C.POINTER(C.c_int32)]),
     "dfgpu_acc_size": (C.c_int64, [_P]),
     "dfgpu_acc_emit_first": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _PP, C.POINTER(C.c_int32)]),
+    "dfgpu_moments_new": (C.c_int32, [_P, C.c_int32, C.c_int32, _PP]),
+    "dfgpu_moments_free": (None, [_P]),
+    "dfgpu_moments_update_batch": (C.c_int32, [_P, _P, _P, _P, _P, C.c_int64]),
+    "dfgpu_moments_merge_batch": (C.c_int32, [_P, _P, _PP, C.c_int32, _P, _P, C.c_int64]),
+    "dfgpu_moments_state": (C.c_int32, [_P, _P, _PP]),
+    "dfgpu_moments_evaluate": (C.c_int32, [_P, _P, _PP]),
+    "dfgpu_moments_size": (C.c_int64, [_P]),
     "dfgpu_groups_emit_first": (C.c_int32, [_P, _P, C.c_int64, _PP]),
     "dfgpu_array_iota": (C.c_int32, [_P, C.c_int64, _PP]),
     "dfgpu_cross_join_indices": (C.c_int32, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _PP, _PP]),

@@ -12,13 +12,12 @@
 //   ROW_ATOMIC         MIN / MAX otherwise: k_acc_update, one atomic per row; Decimal128 adds two passes around it (row_atomic_minmax128)
 // Decimal128 wrapping add: two 64-bit atomics, carry from the value the low add returned (exact mod 2^128).  Float64 SUM is order dependent in the reference too
 // (prim_op.rs:101-109): <= 1e-9 relative.  Profile label of every path: k_acc_update.  count_only_valid is always 1; removing it would change tuned device code.
-#include "int128.h"
+#include "acc_cells.h"
 #include <algorithm>
 #include <tuple>
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 namespace dfgpu {
-constexpr uint32_t GID_NONE = 0xFFFFFFFFu;
 enum { CLS_I64 = 0, CLS_U64 = 1, CLS_F64 = 2, CLS_I128 = 3 };
 }
 using namespace dfgpu;
@@ -37,21 +36,6 @@ struct dfgpu_acc {
 };
 
 namespace dfgpu {
-
-__device__ inline bool filter_pass(const uint64_t* fbits, const uint64_t* fvalid, int64_t i) {
-  return fbits == nullptr || (bit_get(fbits, i) && valid_at(fvalid, i));
-}
-__device__ inline i128 acc_cell_int(const ColView& c, int64_t r) {
-  switch (c.type) {
-    case DFGPU_INT8: return ((const int8_t*)c.values)[r]; case DFGPU_INT16: return ((const int16_t*)c.values)[r];
-    case DFGPU_INT32: case DFGPU_DATE32: return ((const int32_t*)c.values)[r]; case DFGPU_INT64: return ((const int64_t*)c.values)[r];
-    case DFGPU_UINT8: return ((const uint8_t*)c.values)[r]; case DFGPU_UINT16: return ((const uint16_t*)c.values)[r];
-    case DFGPU_UINT32: return ((const uint32_t*)c.values)[r]; case DFGPU_UINT64: return (i128)((const uint64_t*)c.values)[r];
-    case DFGPU_DECIMAL128: return load_i128(c.values, r);
-    default: return 0;
-  }
-}
-__device__ inline double acc_cell_f64(const ColView& c, int64_t r) { return c.type == DFGPU_FLOAT32 ? (double)((const float*)c.values)[r] : ((const double*)c.values)[r]; }
 
 __device__ inline void atomic_add_i128(uint64_t* slot, i128 v) {
   uint64_t lo = (uint64_t)(u128)v, hi = (uint64_t)((u128)v >> 64);

@@ -1375,7 +1375,9 @@ struct NestedLoopJoinExec : Plan {
 struct AggExpr { int kind; ExprPtr arg, filter; std::string name; int32_t type, precision, scale; };    // ≙ AggregateExpr for Sum/Avg/Count/Min/Max
 struct GroupsRef { dfgpu_groups* g = nullptr; ~GroupsRef() { if (g) dfgpu_groups_free(g); } };
 struct AccRef { dfgpu_acc* a = nullptr; ~AccRef() { if (a) dfgpu_acc_free(a); } };
-static const char* agg_fun_name(int k) { switch (k) { case DFGPU_AGG_SUM: return "sum"; case DFGPU_AGG_AVG: return "avg"; case DFGPU_AGG_COUNT: return "count"; case DFGPU_AGG_MIN: return "min"; case DFGPU_AGG_COUNT_DISTINCT: return "count distinct"; default: return "max"; } }
+static bool is_moment_kind(int k) { return k >= DFGPU_AGG_VAR_SAMP && k <= DFGPU_AGG_STDDEV_POP; }
+static const char* agg_fun_name(int k) { switch (k) { case DFGPU_AGG_SUM: return "sum"; case DFGPU_AGG_AVG: return "avg"; case DFGPU_AGG_COUNT: return "count"; case DFGPU_AGG_MIN: return "min"; case DFGPU_AGG_COUNT_DISTINCT: return "count distinct";
+  case DFGPU_AGG_VAR_SAMP: return "var_samp"; case DFGPU_AGG_VAR_POP: return "var_pop"; case DFGPU_AGG_STDDEV_SAMP: return "stddev_samp"; case DFGPU_AGG_STDDEV_POP: return "stddev_pop"; default: return "max"; } }
 
 // ---- aggregates without a GroupsAccumulator of their own in the kernel library, composed from its other entry points
 // MIN / MAX over Utf8 (physical-expr/src/aggregate/min_max.rs: the row-at-a-time Accumulator behind GroupsAccumulatorAdapter): the state is one (group, value) row per
@@ -1458,6 +1460,19 @@ struct CountDistinct {
     update(tc, ge, vals, fe, total);
   }
 };
+// VAR_SAMP / VAR_POP / STDDEV_SAMP / STDDEV_POP (physical-expr/src/aggregate/variance.rs, stddev.rs): the kernel library's dfgpu_moments, an accumulator type of its own beside
+// dfgpu_acc with three state columns (count, mean, m2: variance.rs:86-100).  It takes the route of COUNT(DISTINCT) through the operator: stored group ids, no fused, pre-aggregated,
+// spilling or early-emitting path.
+struct MomentsRef { dfgpu_moments* m = nullptr; MomentsRef() = default; MomentsRef(MomentsRef&& o) noexcept : m(o.m) { o.m = nullptr; } MomentsRef(const MomentsRef&) = delete; ~MomentsRef() { if (m) dfgpu_moments_free(m); } };
+struct Moments {
+  MomentsRef h;
+  void init(const TaskContext& tc, int kind, int32_t in_type) { tc.check(dfgpu_moments_new(tc.ctx, kind, in_type, &h.m)); }
+  void update(const TaskContext& tc, const ArrayRef& gids, const ArrayRef& vals, const ArrayRef& filter, int64_t total) { tc.check(dfgpu_moments_update_batch(tc.ctx, h.m, vals.a, gids.a, filter.a, total)); }
+  void merge(const TaskContext& tc, const ArrayRef& gids, const dfgpu_array* const* states, const ArrayRef& row_mask, int64_t total) { tc.check(dfgpu_moments_merge_batch(tc.ctx, h.m, states, 3, gids.a, row_mask.a, total)); }
+  void grow(const TaskContext& tc, int64_t total) { ArrayRef no_ids = host_u32(tc, nullptr, 0); tc.check(dfgpu_moments_update_batch(tc.ctx, h.m, nullptr, no_ids.a, nullptr, total)); }       // zero-row update: grow the state to `total` groups
+  std::vector<ArrayRef> state(const TaskContext& tc, int64_t total) { grow(tc, total); dfgpu_array* st[3] = {nullptr, nullptr, nullptr}; tc.check(dfgpu_moments_state(tc.ctx, h.m, st)); return {ArrayRef::adopt(st[0]), ArrayRef::adopt(st[1]), ArrayRef::adopt(st[2])}; }
+  ArrayRef emit(const TaskContext& tc, int64_t total) { grow(tc, total); dfgpu_array* v = nullptr; tc.check(dfgpu_moments_evaluate(tc.ctx, h.m, &v)); return ArrayRef::adopt(v); }
+};
 
 // what a spill keeps in host memory: Arrow arrays (dfgpu_array_export_arrow), one piece per key range of a sorted run (AggregateExec's state, SortExec's input)
 struct HostColumn { ArrowArray a{}; ArrowSchema s{}; bool live = false;
@@ -1521,7 +1536,8 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
   const char* name() const override { return "AggregateExec"; }
   bool merging() const { return mode == 1 || mode == 2; }
   bool is_string_minmax(size_t i) const { return (aggs[i].kind == DFGPU_AGG_MIN || aggs[i].kind == DFGPU_AGG_MAX) && aggs[i].type == DFGPU_UTF8; }
-  bool special(size_t i) const { return aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT || is_string_minmax(i); }
+  bool is_moment(size_t i) const { return is_moment_kind(aggs[i].kind); }
+  bool special(size_t i) const { return aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT || is_string_minmax(i) || is_moment(i); }
   bool any_special() const { for (size_t i = 0; i < aggs.size(); i++) if (special(i)) return true; return false; }
   struct AggState;
   // One input batch as the update paths see it: `b` is the batch above the input ProjectionExec when that was looked through (`raw` is the batch below it); its columns
@@ -1641,7 +1657,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
     merge_partial(S, pkeyv, states, 0);
     return true;
   }
-  int nstates(size_t i) const { return aggs[i].kind == DFGPU_AGG_AVG ? 2 : 1; }
+  int nstates(size_t i) const { return is_moment(i) ? 3 : aggs[i].kind == DFGPU_AGG_AVG ? 2 : 1; }
   // merge_batch of every aggregate's state columns into its accumulator.  `states` starts at the first state column: one per aggregate, two (count, sum) for AVG, in
   // the order of the aggregates.  An aggregate without a kernel accumulator is passed over with its column: its owner merges that one.
   void merge_states(const TaskContext& tc, std::vector<AccRef>& accs, const dfgpu_array* const* states, const ArrayRef& gids, const ArrayRef& row_mask, int64_t total) const {
@@ -1689,7 +1705,9 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
   std::vector<std::string> out_names() const { return out_names(mode == 0); }
   std::vector<std::string> out_names(bool as_state) const {
     std::vector<std::string> n = gnames;
-    for (auto& a : aggs) { if (as_state) { if (a.kind == DFGPU_AGG_AVG) { n.push_back(a.name + "[count]"); n.push_back(a.name + "[sum]"); } else n.push_back(a.name + "[" + agg_fun_name(a.kind) + "]"); } else n.push_back(a.name); }
+    for (auto& a : aggs) { if (as_state) { if (a.kind == DFGPU_AGG_AVG) { n.push_back(a.name + "[count]"); n.push_back(a.name + "[sum]"); }
+      else if (is_moment_kind(a.kind)) { n.push_back(a.name + "[count]"); n.push_back(a.name + "[mean]"); n.push_back(a.name + "[m2]"); }       // variance.rs:86-100
+      else n.push_back(a.name + "[" + agg_fun_name(a.kind) + "]"); } else n.push_back(a.name); }
     return n;
   }
   SchemaPtr schema() const override { std::lock_guard<std::mutex> l(mu); if (!sch) { auto s = std::make_shared<Schema>(); for (auto& n : out_names()) s->f.push_back(Field{n}); sch = s; } return sch; }
@@ -1699,7 +1717,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
   struct AggState {
     TaskContext tc; const ProjectionExec* pj = nullptr; PlanPtr src; std::vector<int> parts; size_t next_part = 0; std::unique_ptr<Stream> cur;
     bool grouped = false, specials = false, input_done = false, emitted_any = false; int64_t fuse_min_rows = 1 << 20, preagg_min_rows = 1 << 22;
-    GroupsRef groups; std::vector<AccRef> accs; std::vector<StringMinMax> smm; std::vector<CountDistinct> cds; ArrayRef pending;
+    GroupsRef groups; std::vector<AccRef> accs; std::vector<StringMinMax> smm; std::vector<CountDistinct> cds; std::vector<Moments> mts; ArrayRef pending;
     GroupsRef sort_groups; int64_t current_sort = 0;          // GroupOrderingPartial: the sort-key prefixes seen (only the latest is kept), first group of the latest prefix
     std::deque<Batch> ready; std::shared_ptr<SpillState> spill;
     explicit AggState(const TaskContext& t) : tc(t) {}
@@ -1717,10 +1735,11 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
     S.grouped = !gexprs.empty();      // false: AggregateStream (aggregates/no_grouping.rs): one implicit group
     if (S.grouped) tc.check(dfgpu_groups_new(tc.ctx, (int32_t)gexprs.size(), &S.groups.g));
     S.specials = any_special();
-    new_accs(S); S.smm = std::vector<StringMinMax>(aggs.size()); S.cds = std::vector<CountDistinct>(aggs.size());
+    new_accs(S); S.smm = std::vector<StringMinMax>(aggs.size()); S.cds = std::vector<CountDistinct>(aggs.size()); S.mts = std::vector<Moments>(aggs.size());
     for (size_t i = 0; i < aggs.size(); i++) {
       if (is_string_minmax(i)) S.smm[i].is_max = aggs[i].kind == DFGPU_AGG_MAX;
       else if (aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT) S.cds[i].init(tc);
+      else if (is_moment(i)) S.mts[i].init(tc, aggs[i].kind, aggs[i].type);
     }
     int64_t lim = 0, ranges = 16; dfgpu_ctx_get_option(tc.ctx, "agg_spill_state_bytes", &lim); dfgpu_ctx_get_option(tc.ctx, "agg_spill_ranges", &ranges);
     if (lim > 0 && S.grouped && !S.specials && sets.empty()) { S.spill = std::make_shared<SpillState>(); S.spill->limit = lim; S.spill->ranges = ranges; }
@@ -1753,6 +1772,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
     else consume_update(S, in, mask);
   }
   void consume_sets(AggState& S, InBatch& in, const ArrayRef& mask) const {
+    for (size_t i = 0; i < aggs.size(); i++) if (is_moment(i)) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: VAR / STDDEV aggregates (%s) under grouping sets on the device", aggs[i].name.c_str());
     if (S.specials) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: COUNT(DISTINCT) / string MIN-MAX under grouping sets on the device");
     in.ensure_all(); group_aggregate_sets(S.tc, in.b, mask, S.groups, S.accs);
   }
@@ -1792,6 +1812,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
     for (size_t i = 0, col = 0; i < aggs.size(); col += (size_t)nstates(i), i++) {
       if (is_string_minmax(i)) S.smm[i].update(tc, gids, ArrayRef::share(st[col]), mask);           // the state column is the value (min_max.rs state()); rows a fused selection dropped carry no state
       else if (aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT) S.cds[i].merge(tc, gids, ArrayRef::share(st[col]), mask, total, aggs[i].type, aggs[i].precision, aggs[i].scale);      // the state column is the list of the group's distinct values
+      else if (is_moment(i)) S.mts[i].merge(tc, gids, st.data() + col, S.grouped ? ArrayRef() : mask, total);       // count, mean, m2; a dropped row's group id skips it under GROUP BY
     }
     merge_states(tc, S.accs, st.data(), gids, S.grouped ? ArrayRef() : mask, total);
   }
@@ -1813,6 +1834,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
       if (!S.grouped || special(i)) filt[i] = and_masks(tc, filt[i], mask);
       if (is_string_minmax(i)) S.smm[i].update(tc, gids, vals[i], filt[i]);
       else if (aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT) S.cds[i].update(tc, gids, vals[i], filt[i], total);
+      else if (is_moment(i)) S.mts[i].update(tc, gids, vals[i], filt[i], total);
       else { ap.push_back(S.accs[i].a); vp.push_back(vals[i].a); fp.push_back(filt[i].a); }
     }
     if (!ap.empty()) tc.check(dfgpu_acc_update_batch_multi(tc.ctx, ap.data(), vp.data(), fp.data(), (int32_t)ap.size(), gids.a, total));
@@ -1841,6 +1863,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
       for (size_t i = 0; i < aggs.size(); i++) {
         if (is_string_minmax(i)) { o.cols.push_back(col_of(S.smm[i].emit(tc, total))); continue; }          // state and final value are the same column
         if (aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT) { o.cols.push_back(col_of(as_state ? S.cds[i].state(tc, total, aggs[i].type) : S.cds[i].emit(tc, total))); continue; }
+        if (is_moment(i)) { if (as_state) for (auto& c : S.mts[i].state(tc, total)) o.cols.push_back(col_of(c)); else o.cols.push_back(col_of(S.mts[i].emit(tc, total))); continue; }
         grow_to(tc, S.accs[i].a, total);
         if (as_state) { dfgpu_array* st[2] = {nullptr, nullptr}; int32_t n = 0; tc.check(dfgpu_acc_state(tc.ctx, S.accs[i].a, st, &n)); for (int k = 0; k < n; k++) o.cols.push_back(col_of(ArrayRef::adopt(st[k]))); }
         else { dfgpu_array* v = nullptr; tc.check(dfgpu_acc_evaluate(tc.ctx, S.accs[i].a, &v)); o.cols.push_back(col_of(ArrayRef::adopt(v))); }
@@ -2432,7 +2455,10 @@ dfgpu_status dfgpu_plan_aggregate(int32_t mode, const dfgpu_expr* const* gexprs,
     for (int i = 0; i < na; i++) {
       AggExpr x; x.kind = kinds[i]; if (args && args[i]) x.arg = args[i]->e; if (filters && filters[i]) x.filter = filters[i]->e; x.name = names[i] ? names[i] : "";
       x.type = types[3 * i]; x.precision = types[3 * i + 1]; x.scale = types[3 * i + 2];
-      if (x.kind < DFGPU_AGG_SUM || x.kind > DFGPU_AGG_COUNT_DISTINCT) fail(DFGPU_NOT_IMPLEMENTED, "aggregate kind %d has no GroupsAccumulator on device", x.kind);
+      const bool moment = is_moment_kind(x.kind);
+      if (moment && !(x.type >= DFGPU_INT8 && x.type <= DFGPU_FLOAT64))
+        fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: aggregate kind %d (%s) over a type %d argument on the device (Int8 .. UInt64, Float32 and Float64 are)", x.kind, agg_fun_name(x.kind), x.type);
+      if (!moment && (x.kind < DFGPU_AGG_SUM || x.kind > DFGPU_AGG_COUNT_DISTINCT)) fail(DFGPU_NOT_IMPLEMENTED, "aggregate kind %d has no GroupsAccumulator on device", x.kind);
       if (x.kind == DFGPU_AGG_COUNT_DISTINCT && mode != 3 && mode != 4 && (x.type == DFGPU_DICTIONARY || x.type == DFGPU_BOOL))
         fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: COUNT(DISTINCT) over a type %d argument in AggregateMode %d on the device (its Partial state is a List per group, carried for fixed-width and Utf8 values); Single / SinglePartitioned are", x.type, mode);
       if (!x.arg && x.kind != DFGPU_AGG_COUNT && mode != 1 && mode != 2) fail(DFGPU_INVALID_ARGUMENT, "aggregate %s needs an argument", x.name.c_str());

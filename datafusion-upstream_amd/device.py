@@ -573,3 +573,44 @@ class GroupsAccumulator:
 
     def size(self) -> int:
         return self.ctx.lib.dfgpu_acc_size(self.h)
+
+
+class MomentsAccumulator:
+    """VAR_SAMP / VAR_POP / STDDEV_SAMP / STDDEV_POP per group (dfgpu_moments_*) ≙ VarianceAccumulator / StddevAccumulator (physical-expr/src/aggregate/variance.rs:202-333,
+    stddev.rs:202-241) behind GroupsAccumulatorAdapter.  kind: capi.AGG_VAR_SAMP .. capi.AGG_STDDEV_POP; in_type: Int8 .. UInt64, Float32, Float64."""
+
+    def __init__(self, ctx: Context, kind: int, in_type: int):
+        self.ctx, self.kind, self.h = ctx, kind, None
+        h = C.c_void_p()
+        ctx.check(ctx.lib.dfgpu_moments_new(ctx.h, kind, in_type, C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if self.h is not None and self.h.value:
+                self.ctx.lib.dfgpu_moments_free(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def update_batch(self, values: Optional[Array], group_ids: Array, opt_filter: Optional[Array], total_num_groups: int):
+        self.ctx.check(self.ctx.lib.dfgpu_moments_update_batch(self.ctx.h, self.h, values.h if values is not None else None, group_ids.h,
+                                                               opt_filter.h if opt_filter is not None else None, total_num_groups))
+
+    def merge_batch(self, states: Sequence[Array], group_ids: Array, opt_filter: Optional[Array], total_num_groups: int):
+        hs, n = capi.handle_array([a.h.value for a in states])
+        self.ctx.check(self.ctx.lib.dfgpu_moments_merge_batch(self.ctx.h, self.h, hs, n, group_ids.h, opt_filter.h if opt_filter is not None else None, total_num_groups))
+
+    def state(self) -> List[Array]:
+        """[count UInt64, mean Float64, m2 Float64], no NULLs (variance.rs:234-240)"""
+        outs = (C.c_void_p * 3)()
+        self.ctx.check(self.ctx.lib.dfgpu_moments_state(self.ctx.h, self.h, outs))
+        return [Array(self.ctx, C.c_void_p(outs[i])) for i in range(3)]
+
+    def evaluate(self) -> Array:
+        out = C.c_void_p()
+        self.ctx.check(self.ctx.lib.dfgpu_moments_evaluate(self.ctx.h, self.h, C.byref(out)))
+        return Array(self.ctx, out)
+
+    def size(self) -> int:
+        return self.ctx.lib.dfgpu_moments_size(self.h)

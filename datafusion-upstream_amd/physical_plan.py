@@ -783,7 +783,13 @@ class AggregateFunctionExpr:
 
     @property
     def kind(self) -> int:
-        return {"SUM": capi.AGG_SUM, "AVG": capi.AGG_AVG, "COUNT": capi.AGG_COUNT, "MIN": capi.AGG_MIN, "MAX": capi.AGG_MAX, "COUNT DISTINCT": 5}[self.fun.upper()]
+        return _AGG_KINDS[self.fun.upper()]
+
+
+# BuiltinAggregateFunction::from_str (expr/src/aggregate_function.rs): var / var_samp, var_pop, stddev / stddev_samp, stddev_pop
+_AGG_KINDS = {"SUM": capi.AGG_SUM, "AVG": capi.AGG_AVG, "COUNT": capi.AGG_COUNT, "MIN": capi.AGG_MIN, "MAX": capi.AGG_MAX, "COUNT DISTINCT": capi.AGG_COUNT_DISTINCT,
+              "VAR_SAMP": capi.AGG_VAR_SAMP, "VAR": capi.AGG_VAR_SAMP, "VARIANCE": capi.AGG_VAR_SAMP, "VAR_POP": capi.AGG_VAR_POP,
+              "STDDEV_SAMP": capi.AGG_STDDEV_SAMP, "STDDEV": capi.AGG_STDDEV_SAMP, "STDDEV_POP": capi.AGG_STDDEV_POP}
 
 
 _AGG_MODES = {"Partial": 0, "Final": 1, "FinalPartitioned": 2, "Single": 3, "SinglePartitioned": 4}

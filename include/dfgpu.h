@@ -538,6 +538,31 @@ DFGPU_API dfgpu_status dfgpu_acc_state(dfgpu_ctx *ctx, dfgpu_acc *a, dfgpu_array
 DFGPU_API dfgpu_status dfgpu_acc_emit_first(dfgpu_ctx *ctx, dfgpu_acc *a, int64_t n, int32_t as_state, dfgpu_array **out, int32_t *n_out);
 DFGPU_API int64_t dfgpu_acc_size(const dfgpu_acc *a);
 
+/* a9, continued: VAR_SAMP / VAR_POP / STDDEV_SAMP / STDDEV_POP -- an accumulator type of its own (csrc/moments.hip); dfgpu_acc_new does not know these kinds. */
+enum { DFGPU_AGG_VAR_SAMP = 6, DFGPU_AGG_VAR_POP = 7, DFGPU_AGG_STDDEV_SAMP = 8, DFGPU_AGG_STDDEV_POP = 9 };   /* 5 is DFGPU_AGG_COUNT_DISTINCT (dfgpu_exec.h) */
+typedef struct dfgpu_moments dfgpu_moments;
+/* ≙ Variance / VariancePop::create_accumulator (physical-expr/src/aggregate/variance.rs:78-80, :146-150), Stddev / StddevPop (stddev.rs).  in_type: Int8 .. UInt64,
+ * Float32, Float64 -- the argument is cast to Float64 inside the accumulator (variance.rs:243); any other type is DFGPU_NOT_IMPLEMENTED, any other kind
+ * DFGPU_INVALID_ARGUMENT.  The state per group is (count UInt64, mean Float64, m2 Float64), (0, 0.0, 0.0) before the first value (:86-100, :234-240; stddev.rs:203-209). */
+DFGPU_API dfgpu_status dfgpu_moments_new(dfgpu_ctx *ctx, int32_t kind, int32_t in_type, dfgpu_moments **out);
+DFGPU_API void dfgpu_moments_free(dfgpu_moments *m);   /* drops every group's state (the Box<dyn Accumulator>s of variance.rs:78-80); NULL is allowed */
+/* ≙ VarianceAccumulator::update_batch (variance.rs:242-259) per group: NULL values and rows the filter drops are skipped; group_ids UINT32 (0xFFFFFFFF = skip);
+ * opt_filter BOOL (NULL / false rows skipped).  The state grows to total_num_groups, also when the batch has no rows (values may be NULL then).  The sums are taken in two passes instead of
+ * Welford's recurrence (:246-256): results within 1e-9 relative of the reference's, which depend on the row order themselves. */
+DFGPU_API dfgpu_status dfgpu_moments_update_batch(dfgpu_ctx *ctx, dfgpu_moments *m, const dfgpu_array *values, const dfgpu_array *group_ids,
+                                                  const dfgpu_array *opt_filter, int64_t total_num_groups);
+/* ≙ VarianceAccumulator::merge_batch (variance.rs:280-303): states = (UInt64 counts, Float64 means, Float64 m2s) as dfgpu_moments_state returns them, one row per
+ * group id; rows with count 0 are skipped (:287-289); a group may appear in several rows.  nstates != 3, a column of another type or of another length than
+ * group_ids: DFGPU_INVALID_ARGUMENT, nothing merged. */
+DFGPU_API dfgpu_status dfgpu_moments_merge_batch(dfgpu_ctx *ctx, dfgpu_moments *m, const dfgpu_array *const *states, int32_t nstates,
+                                                 const dfgpu_array *group_ids, const dfgpu_array *opt_filter, int64_t total_num_groups);
+/* ≙ state() (variance.rs:234-240, stddev.rs:203-209): out_states[0 .. 3) = count, mean, m2 of every group, without NULLs. */
+DFGPU_API dfgpu_status dfgpu_moments_state(dfgpu_ctx *ctx, dfgpu_moments *m, dfgpu_array **out_states);
+/* ≙ evaluate() (variance.rs:305-328, stddev.rs:223-232): Float64, NULL at count 0; at count 1 0.0 for the population forms and NULL for the sample forms; else
+ * m2 / count or m2 / (count - 1), and its square root for STDDEV. */
+DFGPU_API dfgpu_status dfgpu_moments_evaluate(dfgpu_ctx *ctx, dfgpu_moments *m, dfgpu_array **out);
+DFGPU_API int64_t dfgpu_moments_size(const dfgpu_moments *m);   /* bytes (≙ Accumulator::size, variance.rs:330-332, summed over the groups) */
+
 /* ------------------------------------------------------------------ a13: SortExec */
 /* ≙ lexsort_to_indices (sorts/sort.rs:599) with per column SortOptions (physical-expr/src/sort_expr.rs:34-74);
  * fetch < 0 = none.  Stable (ties keep input order; the reference leaves tie order unspecified).

@@ -113,7 +113,11 @@ DFGPU_API dfgpu_status dfgpu_plan_nested_loop_join(const dfgpu_plan *left, const
 /* Aggregate kinds of the plan layer beyond DFGPU_AGG_* (include/dfgpu.h): COUNT(DISTINCT x) (aggregate/count_distinct/) -- every mode for fixed-width arguments: the Partial state is the reference's List of distinct values per group, carried in the
  * Utf8 layout (dfgpu_list_from_counts / dfgpu_list_flatten, include/dfgpu.h; a ListArray is the same buffers with the offsets divided by the value width); Utf8 arguments in Single /
  * SinglePartitioned modes only.  MIN / MAX
- * over Utf8 (input type DFGPU_UTF8) are also served by the plan layer, in every mode. */
+ * over Utf8 (input type DFGPU_UTF8) are also served by the plan layer, in every mode.
+ * DFGPU_AGG_VAR_SAMP / VAR_POP / STDDEV_SAMP / STDDEV_POP (6 .. 9, include/dfgpu.h; aggregate/variance.rs, stddev.rs) are accepted in every mode over Int8 .. UInt64, Float32 and
+ * Float64 arguments (any other argument type: DFGPU_NOT_IMPLEMENTED when the plan is built): each has a dfgpu_moments accumulator and three state columns, name[count] UInt64,
+ * name[mean] Float64, name[m2] Float64 (variance.rs:86-100).  An AggregateExec that holds one of these, a COUNT(DISTINCT) or a string MIN / MAX takes none of the fused,
+ * pre-aggregated, spilling or early-emitting paths; with an ordered input mode its groups leave at the end of the input.  Under grouping sets they are DFGPU_NOT_IMPLEMENTED. */
 enum { DFGPU_AGG_COUNT_DISTINCT = 5 };
 /* AggregateExec::try_new(mode, group_by, aggr_expr, input): mode 0 Partial, 1 Final, 2 FinalPartitioned, 3 Single,
  * 4 SinglePartitioned.  Aggregate i: kind DFGPU_AGG_*, argument expr (NULL = COUNT(*)), optional FILTER expr, output name,
