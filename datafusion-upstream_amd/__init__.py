@@ -3,7 +3,7 @@
 Layers (DESIGN.md):
   csrc/        hand-written HIP kernels + the C ABI of include/dfgpu.h  -> libdfgpu.so (built in-tree)
   capi.py      ctypes binding of exactly those symbols
-  device.py    Context / Array / JoinTable / GroupValues / GroupsAccumulator / MomentsAccumulator wrappers
+  device.py    Context / Array / JoinTable / GroupValues / GroupsAccumulator / MomentsAccumulator / CoMomentsAccumulator wrappers
   csrc/exec/   C++ host layer: ExecutionPlan / PhysicalExpr mirror (FilterExec, ProjectionExec, HashJoinExec, AggregateExec,
                SortExec, RepartitionExec, CoalesceBatchesExec ...) over the kernel ABI; C ABI in include/dfgpu_exec.h
   physical_plan.py  typed Python builders over that C++ layer (same class names as the reference operators)
@@ -16,9 +16,9 @@ The package never falls back to a CPU implementation: without libdfgpu.so or a H
 """
 from . import capi
 from .capi import DfgpuError, load_library
-from .device import Array, Context, GroupValues, GroupsAccumulator, JoinTable, MomentsAccumulator, agg_preaggregate, join_adjust_indices
+from .device import Array, CoMomentsAccumulator, Context, GroupValues, GroupsAccumulator, JoinTable, MomentsAccumulator, agg_preaggregate, join_adjust_indices
 from . import operators
 from . import physical_plan
 
-__all__ = ["capi", "DfgpuError", "load_library", "Array", "Context", "GroupValues", "GroupsAccumulator", "JoinTable", "MomentsAccumulator",
+__all__ = ["capi", "DfgpuError", "load_library", "Array", "Context", "GroupValues", "GroupsAccumulator", "JoinTable", "MomentsAccumulator", "CoMomentsAccumulator",
            "join_adjust_indices", "operators", "physical_plan"]

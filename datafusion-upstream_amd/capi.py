@@ -25,6 +25,9 @@ JOIN_INNER, JOIN_LEFT, JOIN_RIGHT, JOIN_FULL, JOIN_LEFT_SEMI, JOIN_RIGHT_SEMI, J
 AGG_SUM, AGG_AVG, AGG_COUNT, AGG_MIN, AGG_MAX = range(5)
 AGG_COUNT_DISTINCT = 5                                                           # plan layer only (include/dfgpu_exec.h)
 AGG_VAR_SAMP, AGG_VAR_POP, AGG_STDDEV_SAMP, AGG_STDDEV_POP = 6, 7, 8, 9          # dfgpu_moments_* (their own accumulator type)
+# dfgpu_comoments_*: the two-argument aggregates (10 stays the kind no accumulator knows)
+(AGG_COVAR_SAMP, AGG_COVAR_POP, AGG_CORR, AGG_REGR_SLOPE, AGG_REGR_INTERCEPT, AGG_REGR_COUNT, AGG_REGR_R2, AGG_REGR_AVGX, AGG_REGR_AVGY, AGG_REGR_SXX, AGG_REGR_SYY,
+ AGG_REGR_SXY) = range(11, 23)
 
 STATUS_NAMES = {0: "Ok", 1: "Execution", 2: "Internal", 3: "ResourcesExhausted", 4: "NotImplemented", 5: "InvalidArgument"}
 
@@ -170,6 +173,13 @@ PROTOTYPES = {
     "dfgpu_moments_state": (C.c_int32, [_P, _P, _PP]),
     "dfgpu_moments_evaluate": (C.c_int32, [_P, _P, _PP]),
     "dfgpu_moments_size": (C.c_int64, [_P]),
+    "dfgpu_comoments_new": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, _PP]),
+    "dfgpu_comoments_free": (None, [_P]),
+    "dfgpu_comoments_update_batch": (C.c_int32, [_P, _P, _P, _P, _P, _P, C.c_int64]),
+    "dfgpu_comoments_merge_batch": (C.c_int32, [_P, _P, _PP, C.c_int32, _P, _P, C.c_int64]),
+    "dfgpu_comoments_state": (C.c_int32, [_P, _P, _PP]),
+    "dfgpu_comoments_evaluate": (C.c_int32, [_P, _P, _PP]),
+    "dfgpu_comoments_size": (C.c_int64, [_P]),
     "dfgpu_groups_emit_first": (C.c_int32, [_P, _P, C.c_int64, _PP]),
     "dfgpu_array_iota": (C.c_int32, [_P, C.c_int64, _PP]),
     "dfgpu_cross_join_indices": (C.c_int32, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _PP, _PP]),
@@ -239,6 +249,7 @@ PROTOTYPES.update({
     "dfgpu_plan_repartition": (C.c_int32, [_P, _PP, C.c_int32, C.c_int32, _PP]),
     "dfgpu_plan_hash_join": (C.c_int32, [_P, _P, _PP, _PP, C.c_int32, _P, _I32P, _I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _PP]),
     "dfgpu_plan_aggregate_input_order": (C.c_int32, [_P, C.c_int32, _I32P, C.c_int32]),
+    "dfgpu_plan_aggregate_second_arg": (C.c_int32, [_P, C.c_int32, _P, _I32P]),
     "dfgpu_plan_aggregate_grouping_sets": (C.c_int32, [_P, _PP, C.c_int32, C.POINTER(C.c_uint8), C.c_int32]),
     "dfgpu_plan_aggregate": (C.c_int32, [C.c_int32, _PP, _CPP, C.c_int32, _I32P, _PP, _PP, _CPP, _I32P, C.c_int32, _P, _PP]),
     "dfgpu_plan_sort": (C.c_int32, [_PP, C.c_char_p, C.c_char_p, C.c_int32, C.c_int64, C.c_int32, _P, _PP]),

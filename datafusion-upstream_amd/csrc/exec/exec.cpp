@@ -1372,12 +1372,18 @@ struct NestedLoopJoinExec : Plan {
 };
 
 // ------------------------------------------------------------------ AggregateExec
-struct AggExpr { int kind; ExprPtr arg, filter; std::string name; int32_t type, precision, scale; };    // ≙ AggregateExpr for Sum/Avg/Count/Min/Max
+struct AggExpr { int kind; ExprPtr arg, filter; std::string name; int32_t type, precision, scale;    // ≙ AggregateExpr for Sum/Avg/Count/Min/Max
+                 ExprPtr arg2; int32_t type2 = -1; };       // the second argument of COVAR / CORR / REGR_* (dfgpu_plan_aggregate_second_arg); type2 < 0: not attached
 struct GroupsRef { dfgpu_groups* g = nullptr; ~GroupsRef() { if (g) dfgpu_groups_free(g); } };
 struct AccRef { dfgpu_acc* a = nullptr; ~AccRef() { if (a) dfgpu_acc_free(a); } };
 static bool is_moment_kind(int k) { return k >= DFGPU_AGG_VAR_SAMP && k <= DFGPU_AGG_STDDEV_POP; }
+static bool is_comoment_kind(int k) { return k >= DFGPU_AGG_COVAR_SAMP && k <= DFGPU_AGG_REGR_SXY; }       // the two-argument aggregates
+static bool is_moment_input(int32_t t) { return t >= DFGPU_INT8 && t <= DFGPU_FLOAT64; }
 static const char* agg_fun_name(int k) { switch (k) { case DFGPU_AGG_SUM: return "sum"; case DFGPU_AGG_AVG: return "avg"; case DFGPU_AGG_COUNT: return "count"; case DFGPU_AGG_MIN: return "min"; case DFGPU_AGG_COUNT_DISTINCT: return "count distinct";
-  case DFGPU_AGG_VAR_SAMP: return "var_samp"; case DFGPU_AGG_VAR_POP: return "var_pop"; case DFGPU_AGG_STDDEV_SAMP: return "stddev_samp"; case DFGPU_AGG_STDDEV_POP: return "stddev_pop"; default: return "max"; } }
+  case DFGPU_AGG_VAR_SAMP: return "var_samp"; case DFGPU_AGG_VAR_POP: return "var_pop"; case DFGPU_AGG_STDDEV_SAMP: return "stddev_samp"; case DFGPU_AGG_STDDEV_POP: return "stddev_pop";
+  case DFGPU_AGG_COVAR_SAMP: return "covar_samp"; case DFGPU_AGG_COVAR_POP: return "covar_pop"; case DFGPU_AGG_CORR: return "corr"; case DFGPU_AGG_REGR_SLOPE: return "regr_slope";
+  case DFGPU_AGG_REGR_INTERCEPT: return "regr_intercept"; case DFGPU_AGG_REGR_COUNT: return "regr_count"; case DFGPU_AGG_REGR_R2: return "regr_r2"; case DFGPU_AGG_REGR_AVGX: return "regr_avgx";
+  case DFGPU_AGG_REGR_AVGY: return "regr_avgy"; case DFGPU_AGG_REGR_SXX: return "regr_sxx"; case DFGPU_AGG_REGR_SYY: return "regr_syy"; case DFGPU_AGG_REGR_SXY: return "regr_sxy"; default: return "max"; } }
 
 // ---- aggregates without a GroupsAccumulator of their own in the kernel library, composed from its other entry points
 // MIN / MAX over Utf8 (physical-expr/src/aggregate/min_max.rs: the row-at-a-time Accumulator behind GroupsAccumulatorAdapter): the state is one (group, value) row per
@@ -1473,6 +1479,28 @@ struct Moments {
   std::vector<ArrayRef> state(const TaskContext& tc, int64_t total) { grow(tc, total); dfgpu_array* st[3] = {nullptr, nullptr, nullptr}; tc.check(dfgpu_moments_state(tc.ctx, h.m, st)); return {ArrayRef::adopt(st[0]), ArrayRef::adopt(st[1]), ArrayRef::adopt(st[2])}; }
   ArrayRef emit(const TaskContext& tc, int64_t total) { grow(tc, total); dfgpu_array* v = nullptr; tc.check(dfgpu_moments_evaluate(tc.ctx, h.m, &v)); return ArrayRef::adopt(v); }
 };
+// COVAR_SAMP / COVAR_POP / CORR / REGR_* (physical-expr/src/aggregate/covariance.rs, correlation.rs, regr.rs): the kernel library's dfgpu_comoments, the two-argument sibling of
+// dfgpu_moments, on the same route through the operator.  State columns, in the reference's order: COVAR count, mean1, mean2, algo_const (covariance.rs:86-108); CORR count, mean1,
+// m2_1, mean2, m2_2, algo_const (correlation.rs:77-108); REGR count, mean_x, mean_y, m2_x, m2_y, algo_const (regr.rs:131-162).
+static int comoment_nstates(int kind) { return kind == DFGPU_AGG_COVAR_SAMP || kind == DFGPU_AGG_COVAR_POP ? 4 : 6; }
+static std::vector<const char*> comoment_state_names(int kind) {
+  if (comoment_nstates(kind) == 4) return {"count", "mean1", "mean2", "algo_const"};
+  if (kind == DFGPU_AGG_CORR) return {"count", "mean1", "m2_1", "mean2", "m2_2", "algo_const"};
+  return {"count", "mean_x", "mean_y", "m2_x", "m2_y", "algo_const"};
+}
+struct CoMomentsRef { dfgpu_comoments* m = nullptr; CoMomentsRef() = default; CoMomentsRef(CoMomentsRef&& o) noexcept : m(o.m) { o.m = nullptr; } CoMomentsRef(const CoMomentsRef&) = delete; ~CoMomentsRef() { if (m) dfgpu_comoments_free(m); } };
+struct CoMoments {
+  CoMomentsRef h; int nst = 0;
+  void init(const TaskContext& tc, int kind, int32_t type_a, int32_t type_b) { nst = comoment_nstates(kind); tc.check(dfgpu_comoments_new(tc.ctx, kind, type_a, type_b, &h.m)); }
+  void update(const TaskContext& tc, const ArrayRef& gids, const ArrayRef& a, const ArrayRef& b, const ArrayRef& filter, int64_t total) { tc.check(dfgpu_comoments_update_batch(tc.ctx, h.m, a.a, b.a, gids.a, filter.a, total)); }
+  void merge(const TaskContext& tc, const ArrayRef& gids, const dfgpu_array* const* states, const ArrayRef& row_mask, int64_t total) { tc.check(dfgpu_comoments_merge_batch(tc.ctx, h.m, states, nst, gids.a, row_mask.a, total)); }
+  void grow(const TaskContext& tc, int64_t total) { ArrayRef no_ids = host_u32(tc, nullptr, 0); tc.check(dfgpu_comoments_update_batch(tc.ctx, h.m, nullptr, nullptr, no_ids.a, nullptr, total)); }       // zero-row update: grow the state to `total` groups
+  std::vector<ArrayRef> state(const TaskContext& tc, int64_t total) {
+    grow(tc, total); dfgpu_array* st[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; tc.check(dfgpu_comoments_state(tc.ctx, h.m, st));
+    std::vector<ArrayRef> out; for (int k = 0; k < nst; k++) out.push_back(ArrayRef::adopt(st[k])); return out;
+  }
+  ArrayRef emit(const TaskContext& tc, int64_t total) { grow(tc, total); dfgpu_array* v = nullptr; tc.check(dfgpu_comoments_evaluate(tc.ctx, h.m, &v)); return ArrayRef::adopt(v); }
+};
 
 // what a spill keeps in host memory: Arrow arrays (dfgpu_array_export_arrow), one piece per key range of a sorted run (AggregateExec's state, SortExec's input)
 struct HostColumn { ArrowArray a{}; ArrowSchema s{}; bool live = false;
@@ -1537,7 +1565,8 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
   bool merging() const { return mode == 1 || mode == 2; }
   bool is_string_minmax(size_t i) const { return (aggs[i].kind == DFGPU_AGG_MIN || aggs[i].kind == DFGPU_AGG_MAX) && aggs[i].type == DFGPU_UTF8; }
   bool is_moment(size_t i) const { return is_moment_kind(aggs[i].kind); }
-  bool special(size_t i) const { return aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT || is_string_minmax(i) || is_moment(i); }
+  bool is_comoment(size_t i) const { return is_comoment_kind(aggs[i].kind); }
+  bool special(size_t i) const { return aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT || is_string_minmax(i) || is_moment(i) || is_comoment(i); }
   bool any_special() const { for (size_t i = 0; i < aggs.size(); i++) if (special(i)) return true; return false; }
   struct AggState;
   // One input batch as the update paths see it: `b` is the batch above the input ProjectionExec when that was looked through (`raw` is the batch below it); its columns
@@ -1657,7 +1686,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
     merge_partial(S, pkeyv, states, 0);
     return true;
   }
-  int nstates(size_t i) const { return is_moment(i) ? 3 : aggs[i].kind == DFGPU_AGG_AVG ? 2 : 1; }
+  int nstates(size_t i) const { return is_moment(i) ? 3 : is_comoment(i) ? comoment_nstates(aggs[i].kind) : aggs[i].kind == DFGPU_AGG_AVG ? 2 : 1; }
   // merge_batch of every aggregate's state columns into its accumulator.  `states` starts at the first state column: one per aggregate, two (count, sum) for AVG, in
   // the order of the aggregates.  An aggregate without a kernel accumulator is passed over with its column: its owner merges that one.
   void merge_states(const TaskContext& tc, std::vector<AccRef>& accs, const dfgpu_array* const* states, const ArrayRef& gids, const ArrayRef& row_mask, int64_t total) const {
@@ -1707,6 +1736,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
     std::vector<std::string> n = gnames;
     for (auto& a : aggs) { if (as_state) { if (a.kind == DFGPU_AGG_AVG) { n.push_back(a.name + "[count]"); n.push_back(a.name + "[sum]"); }
       else if (is_moment_kind(a.kind)) { n.push_back(a.name + "[count]"); n.push_back(a.name + "[mean]"); n.push_back(a.name + "[m2]"); }       // variance.rs:86-100
+      else if (is_comoment_kind(a.kind)) { for (const char* c : comoment_state_names(a.kind)) n.push_back(a.name + "[" + c + "]"); }
       else n.push_back(a.name + "[" + agg_fun_name(a.kind) + "]"); } else n.push_back(a.name); }
     return n;
   }
@@ -1717,7 +1747,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
   struct AggState {
     TaskContext tc; const ProjectionExec* pj = nullptr; PlanPtr src; std::vector<int> parts; size_t next_part = 0; std::unique_ptr<Stream> cur;
     bool grouped = false, specials = false, input_done = false, emitted_any = false; int64_t fuse_min_rows = 1 << 20, preagg_min_rows = 1 << 22;
-    GroupsRef groups; std::vector<AccRef> accs; std::vector<StringMinMax> smm; std::vector<CountDistinct> cds; std::vector<Moments> mts; ArrayRef pending;
+    GroupsRef groups; std::vector<AccRef> accs; std::vector<StringMinMax> smm; std::vector<CountDistinct> cds; std::vector<Moments> mts; std::vector<CoMoments> cms; ArrayRef pending;
     GroupsRef sort_groups; int64_t current_sort = 0;          // GroupOrderingPartial: the sort-key prefixes seen (only the latest is kept), first group of the latest prefix
     std::deque<Batch> ready; std::shared_ptr<SpillState> spill;
     explicit AggState(const TaskContext& t) : tc(t) {}
@@ -1735,11 +1765,15 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
     S.grouped = !gexprs.empty();      // false: AggregateStream (aggregates/no_grouping.rs): one implicit group
     if (S.grouped) tc.check(dfgpu_groups_new(tc.ctx, (int32_t)gexprs.size(), &S.groups.g));
     S.specials = any_special();
-    new_accs(S); S.smm = std::vector<StringMinMax>(aggs.size()); S.cds = std::vector<CountDistinct>(aggs.size()); S.mts = std::vector<Moments>(aggs.size());
+    new_accs(S); S.smm = std::vector<StringMinMax>(aggs.size()); S.cds = std::vector<CountDistinct>(aggs.size()); S.mts = std::vector<Moments>(aggs.size()); S.cms = std::vector<CoMoments>(aggs.size());
     for (size_t i = 0; i < aggs.size(); i++) {
       if (is_string_minmax(i)) S.smm[i].is_max = aggs[i].kind == DFGPU_AGG_MAX;
       else if (aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT) S.cds[i].init(tc);
       else if (is_moment(i)) S.mts[i].init(tc, aggs[i].kind, aggs[i].type);
+      else if (is_comoment(i)) {
+        if (aggs[i].type2 < 0 || (!aggs[i].arg2 && !merging())) fail(DFGPU_INVALID_ARGUMENT, "aggregate %s (%s) takes two arguments: attach the second with dfgpu_plan_aggregate_second_arg before the plan executes", aggs[i].name.c_str(), agg_fun_name(aggs[i].kind));
+        S.cms[i].init(tc, aggs[i].kind, aggs[i].type, aggs[i].type2);
+      }
     }
     int64_t lim = 0, ranges = 16; dfgpu_ctx_get_option(tc.ctx, "agg_spill_state_bytes", &lim); dfgpu_ctx_get_option(tc.ctx, "agg_spill_ranges", &ranges);
     if (lim > 0 && S.grouped && !S.specials && sets.empty()) { S.spill = std::make_shared<SpillState>(); S.spill->limit = lim; S.spill->ranges = ranges; }
@@ -1773,6 +1807,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
   }
   void consume_sets(AggState& S, InBatch& in, const ArrayRef& mask) const {
     for (size_t i = 0; i < aggs.size(); i++) if (is_moment(i)) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: VAR / STDDEV aggregates (%s) under grouping sets on the device", aggs[i].name.c_str());
+    for (size_t i = 0; i < aggs.size(); i++) if (is_comoment(i)) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: COVAR / CORR / REGR aggregates (%s) under grouping sets on the device", aggs[i].name.c_str());
     if (S.specials) fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: COUNT(DISTINCT) / string MIN-MAX under grouping sets on the device");
     in.ensure_all(); group_aggregate_sets(S.tc, in.b, mask, S.groups, S.accs);
   }
@@ -1813,6 +1848,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
       if (is_string_minmax(i)) S.smm[i].update(tc, gids, ArrayRef::share(st[col]), mask);           // the state column is the value (min_max.rs state()); rows a fused selection dropped carry no state
       else if (aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT) S.cds[i].merge(tc, gids, ArrayRef::share(st[col]), mask, total, aggs[i].type, aggs[i].precision, aggs[i].scale);      // the state column is the list of the group's distinct values
       else if (is_moment(i)) S.mts[i].merge(tc, gids, st.data() + col, S.grouped ? ArrayRef() : mask, total);       // count, mean, m2; a dropped row's group id skips it under GROUP BY
+      else if (is_comoment(i)) S.cms[i].merge(tc, gids, st.data() + col, S.grouped ? ArrayRef() : mask, total);     // the kind's four or six columns
     }
     merge_states(tc, S.accs, st.data(), gids, S.grouped ? ArrayRef() : mask, total);
   }
@@ -1835,6 +1871,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
       if (is_string_minmax(i)) S.smm[i].update(tc, gids, vals[i], filt[i]);
       else if (aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT) S.cds[i].update(tc, gids, vals[i], filt[i], total);
       else if (is_moment(i)) S.mts[i].update(tc, gids, vals[i], filt[i], total);
+      else if (is_comoment(i)) S.cms[i].update(tc, gids, vals[i], into_array(tc, aggs[i].arg2->eval(tc, b), b.base_rows), filt[i], total);
       else { ap.push_back(S.accs[i].a); vp.push_back(vals[i].a); fp.push_back(filt[i].a); }
     }
     if (!ap.empty()) tc.check(dfgpu_acc_update_batch_multi(tc.ctx, ap.data(), vp.data(), fp.data(), (int32_t)ap.size(), gids.a, total));
@@ -1864,6 +1901,7 @@ struct AggregateExec : Plan {     // aggregates/mod.rs:242-269; GroupedHashAggre
         if (is_string_minmax(i)) { o.cols.push_back(col_of(S.smm[i].emit(tc, total))); continue; }          // state and final value are the same column
         if (aggs[i].kind == DFGPU_AGG_COUNT_DISTINCT) { o.cols.push_back(col_of(as_state ? S.cds[i].state(tc, total, aggs[i].type) : S.cds[i].emit(tc, total))); continue; }
         if (is_moment(i)) { if (as_state) for (auto& c : S.mts[i].state(tc, total)) o.cols.push_back(col_of(c)); else o.cols.push_back(col_of(S.mts[i].emit(tc, total))); continue; }
+        if (is_comoment(i)) { if (as_state) for (auto& c : S.cms[i].state(tc, total)) o.cols.push_back(col_of(c)); else o.cols.push_back(col_of(S.cms[i].emit(tc, total))); continue; }
         grow_to(tc, S.accs[i].a, total);
         if (as_state) { dfgpu_array* st[2] = {nullptr, nullptr}; int32_t n = 0; tc.check(dfgpu_acc_state(tc.ctx, S.accs[i].a, st, &n)); for (int k = 0; k < n; k++) o.cols.push_back(col_of(ArrayRef::adopt(st[k]))); }
         else { dfgpu_array* v = nullptr; tc.check(dfgpu_acc_evaluate(tc.ctx, S.accs[i].a, &v)); o.cols.push_back(col_of(ArrayRef::adopt(v))); }
@@ -2455,8 +2493,8 @@ dfgpu_status dfgpu_plan_aggregate(int32_t mode, const dfgpu_expr* const* gexprs,
     for (int i = 0; i < na; i++) {
       AggExpr x; x.kind = kinds[i]; if (args && args[i]) x.arg = args[i]->e; if (filters && filters[i]) x.filter = filters[i]->e; x.name = names[i] ? names[i] : "";
       x.type = types[3 * i]; x.precision = types[3 * i + 1]; x.scale = types[3 * i + 2];
-      const bool moment = is_moment_kind(x.kind);
-      if (moment && !(x.type >= DFGPU_INT8 && x.type <= DFGPU_FLOAT64))
+      const bool moment = is_moment_kind(x.kind) || is_comoment_kind(x.kind);
+      if (moment && !is_moment_input(x.type))
         fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: aggregate kind %d (%s) over a type %d argument on the device (Int8 .. UInt64, Float32 and Float64 are)", x.kind, agg_fun_name(x.kind), x.type);
       if (!moment && (x.kind < DFGPU_AGG_SUM || x.kind > DFGPU_AGG_COUNT_DISTINCT)) fail(DFGPU_NOT_IMPLEMENTED, "aggregate kind %d has no GroupsAccumulator on device", x.kind);
       if (x.kind == DFGPU_AGG_COUNT_DISTINCT && mode != 3 && mode != 4 && (x.type == DFGPU_DICTIONARY || x.type == DFGPU_BOOL))
@@ -2475,6 +2513,19 @@ dfgpu_status dfgpu_plan_aggregate_input_order(dfgpu_plan* aggregate, int32_t inp
     a->order_indices.clear();
     if (input_order_mode == 1) for (int i = 0; i < n; i++) { if (order_indices[i] < 0 || order_indices[i] >= (int32_t)a->gexprs.size()) fail(DFGPU_INVALID_ARGUMENT, "plan_aggregate_input_order: order index %d of %zu group expressions", order_indices[i], a->gexprs.size()); a->order_indices.push_back(order_indices[i]); }
     a->order_mode = input_order_mode;
+  });
+}
+dfgpu_status dfgpu_plan_aggregate_second_arg(dfgpu_plan* aggregate, int32_t agg_index, const dfgpu_expr* arg, const int32_t* arg_type) {
+  return guard([&] {
+    auto* a = aggregate ? const_cast<AggregateExec*>(dynamic_cast<const AggregateExec*>(aggregate->p.get())) : nullptr;       // the node is still private to its builder
+    if (!a) fail(DFGPU_INVALID_ARGUMENT, "plan_aggregate_second_arg: not an AggregateExec");
+    if (!arg_type || agg_index < 0 || agg_index >= (int32_t)a->aggs.size()) fail(DFGPU_INVALID_ARGUMENT, "plan_aggregate_second_arg: aggregate %d of %zu, or no argument type", agg_index, a->aggs.size());
+    AggExpr& x = a->aggs[(size_t)agg_index];
+    if (!is_comoment_kind(x.kind)) fail(DFGPU_INVALID_ARGUMENT, "plan_aggregate_second_arg: aggregate %s (%s) takes one argument", x.name.c_str(), agg_fun_name(x.kind));
+    if (!arg && !a->merging()) fail(DFGPU_INVALID_ARGUMENT, "aggregate %s needs a second argument", x.name.c_str());
+    if (!is_moment_input(arg_type[0]))
+      fail(DFGPU_NOT_IMPLEMENTED, "This feature is not implemented: aggregate kind %d (%s) over a type %d argument on the device (Int8 .. UInt64, Float32 and Float64 are)", x.kind, agg_fun_name(x.kind), arg_type[0]);
+    x.arg2 = arg ? arg->e : nullptr; x.type2 = arg_type[0];
   });
 }
 dfgpu_status dfgpu_plan_aggregate_grouping_sets(dfgpu_plan* aggregate, const dfgpu_expr* const* null_exprs, int32_t nkeys, const uint8_t* groups, int32_t nsets) {

@@ -614,3 +614,47 @@ class MomentsAccumulator:
 
     def size(self) -> int:
         return self.ctx.lib.dfgpu_moments_size(self.h)
+
+
+class CoMomentsAccumulator:
+    """COVAR_SAMP / COVAR_POP / CORR / REGR_* per group (dfgpu_comoments_*) ≙ CovarianceAccumulator / CorrelationAccumulator / RegrAccumulator (physical-expr/src/aggregate/
+    covariance.rs:225-406, correlation.rs:134-246, regr.rs:228-466) behind GroupsAccumulatorAdapter.  kind: capi.AGG_COVAR_SAMP .. capi.AGG_REGR_SXY; in_type_a / in_type_b:
+    the types of argument 0 and argument 1 (REGR_*(y, x): y is argument 0), each Int8 .. UInt64, Float32 or Float64."""
+
+    def __init__(self, ctx: Context, kind: int, in_type_a: int, in_type_b: int):
+        self.ctx, self.kind, self.h = ctx, kind, None
+        self.nstates = 4 if kind in (capi.AGG_COVAR_SAMP, capi.AGG_COVAR_POP) else 6
+        h = C.c_void_p()
+        ctx.check(ctx.lib.dfgpu_comoments_new(ctx.h, kind, in_type_a, in_type_b, C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if self.h is not None and self.h.value:
+                self.ctx.lib.dfgpu_comoments_free(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def update_batch(self, values_a: Optional[Array], values_b: Optional[Array], group_ids: Array, opt_filter: Optional[Array], total_num_groups: int):
+        self.ctx.check(self.ctx.lib.dfgpu_comoments_update_batch(self.ctx.h, self.h, values_a.h if values_a is not None else None, values_b.h if values_b is not None else None,
+                                                                 group_ids.h, opt_filter.h if opt_filter is not None else None, total_num_groups))
+
+    def merge_batch(self, states: Sequence[Array], group_ids: Array, opt_filter: Optional[Array], total_num_groups: int):
+        hs, n = capi.handle_array([a.h.value for a in states])
+        self.ctx.check(self.ctx.lib.dfgpu_comoments_merge_batch(self.ctx.h, self.h, hs, n, group_ids.h, opt_filter.h if opt_filter is not None else None, total_num_groups))
+
+    def state(self) -> List[Array]:
+        """the reference's state columns, no NULLs: COVAR [count, mean1, mean2, algo_const]; CORR [count, mean1, m2_1, mean2, m2_2, algo_const];
+        REGR [count, mean_x, mean_y, m2_x, m2_y, algo_const] -- count UInt64, the rest Float64"""
+        outs = (C.c_void_p * 6)()
+        self.ctx.check(self.ctx.lib.dfgpu_comoments_state(self.ctx.h, self.h, outs))
+        return [Array(self.ctx, C.c_void_p(outs[i])) for i in range(self.nstates)]
+
+    def evaluate(self) -> Array:
+        out = C.c_void_p()
+        self.ctx.check(self.ctx.lib.dfgpu_comoments_evaluate(self.ctx.h, self.h, C.byref(out)))
+        return Array(self.ctx, out)
+
+    def size(self) -> int:
+        return self.ctx.lib.dfgpu_comoments_size(self.h)

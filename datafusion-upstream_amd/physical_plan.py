@@ -780,16 +780,21 @@ class AggregateFunctionExpr:
     name: str
     filter: Optional[PhysicalExpr] = None
     input_field: Optional[Field] = None      # argument data type (the AggregateExpr knows it in every mode)
+    expr2: Optional[PhysicalExpr] = None     # the second argument of COVAR / CORR / REGR_* (REGR_*(y, x): expr is y, expr2 is x)
+    input_field2: Optional[Field] = None     # and its data type
 
     @property
     def kind(self) -> int:
         return _AGG_KINDS[self.fun.upper()]
 
 
-# BuiltinAggregateFunction::from_str (expr/src/aggregate_function.rs): var / var_samp, var_pop, stddev / stddev_samp, stddev_pop
+# BuiltinAggregateFunction::from_str (expr/src/aggregate_function.rs): var / var_samp, var_pop, stddev / stddev_samp, stddev_pop, covar / covar_samp, covar_pop, corr, regr_*
 _AGG_KINDS = {"SUM": capi.AGG_SUM, "AVG": capi.AGG_AVG, "COUNT": capi.AGG_COUNT, "MIN": capi.AGG_MIN, "MAX": capi.AGG_MAX, "COUNT DISTINCT": capi.AGG_COUNT_DISTINCT,
               "VAR_SAMP": capi.AGG_VAR_SAMP, "VAR": capi.AGG_VAR_SAMP, "VARIANCE": capi.AGG_VAR_SAMP, "VAR_POP": capi.AGG_VAR_POP,
-              "STDDEV_SAMP": capi.AGG_STDDEV_SAMP, "STDDEV": capi.AGG_STDDEV_SAMP, "STDDEV_POP": capi.AGG_STDDEV_POP}
+              "STDDEV_SAMP": capi.AGG_STDDEV_SAMP, "STDDEV": capi.AGG_STDDEV_SAMP, "STDDEV_POP": capi.AGG_STDDEV_POP,
+              "COVAR": capi.AGG_COVAR_SAMP, "COVAR_SAMP": capi.AGG_COVAR_SAMP, "COVAR_POP": capi.AGG_COVAR_POP, "CORR": capi.AGG_CORR,
+              "REGR_SLOPE": capi.AGG_REGR_SLOPE, "REGR_INTERCEPT": capi.AGG_REGR_INTERCEPT, "REGR_COUNT": capi.AGG_REGR_COUNT, "REGR_R2": capi.AGG_REGR_R2,
+              "REGR_AVGX": capi.AGG_REGR_AVGX, "REGR_AVGY": capi.AGG_REGR_AVGY, "REGR_SXX": capi.AGG_REGR_SXX, "REGR_SYY": capi.AGG_REGR_SYY, "REGR_SXY": capi.AGG_REGR_SXY}
 
 
 _AGG_MODES = {"Partial": 0, "Final": 1, "FinalPartitioned": 2, "Single": 3, "SinglePartitioned": 4}
@@ -843,6 +848,12 @@ class AggregateExec(ExecutionPlan):
         out = C.c_void_p()
         _check(_lib().dfgpu_plan_aggregate(_AGG_MODES[self.mode], _ptrs([e.handle(ctx).h for e, _ in self.group_by]), _strs([n for _, n in self.group_by]), len(self.group_by),
                                            kinds, args, filts, _strs([a.name for a in self.aggr_expr]), tarr, na, _child_handle(self.input, context).h, C.byref(out)))
+        for i, a in enumerate(self.aggr_expr):             # a two-argument aggregate left without its second argument is refused when the plan executes
+            if a.expr2 is not None or a.input_field2 is not None:
+                if a.input_field2 is None:
+                    raise DfgpuError(5, f"aggregate {a.name}: input_field2 (data type of the second argument) is required")
+                f = a.input_field2
+                _check(_lib().dfgpu_plan_aggregate_second_arg(out, i, a.expr2.handle(ctx).h if a.expr2 is not None else None, (C.c_int32 * 3)(f.dtype, f.precision, f.scale)))
         om = self.input_order_mode
         if om != "Linear":
             idx = list(om[1]) if isinstance(om, (tuple, list)) else []

@@ -563,6 +563,40 @@ DFGPU_API dfgpu_status dfgpu_moments_state(dfgpu_ctx *ctx, dfgpu_moments *m, dfg
 DFGPU_API dfgpu_status dfgpu_moments_evaluate(dfgpu_ctx *ctx, dfgpu_moments *m, dfgpu_array **out);
 DFGPU_API int64_t dfgpu_moments_size(const dfgpu_moments *m);   /* bytes (≙ Accumulator::size, variance.rs:330-332, summed over the groups) */
 
+/* a9, continued: the two-argument aggregates COVAR_SAMP / COVAR_POP / CORR / REGR_* -- dfgpu_comoments, a sibling of dfgpu_moments (csrc/comoments.hip).  Kind 10 stays
+ * unassigned: it is the kind no accumulator knows (dfgpu_acc_new, dfgpu_moments_new and dfgpu_plan_aggregate keep refusing it). */
+enum { DFGPU_AGG_COVAR_SAMP = 11, DFGPU_AGG_COVAR_POP = 12, DFGPU_AGG_CORR = 13, DFGPU_AGG_REGR_SLOPE = 14, DFGPU_AGG_REGR_INTERCEPT = 15, DFGPU_AGG_REGR_COUNT = 16,
+       DFGPU_AGG_REGR_R2 = 17, DFGPU_AGG_REGR_AVGX = 18, DFGPU_AGG_REGR_AVGY = 19, DFGPU_AGG_REGR_SXX = 20, DFGPU_AGG_REGR_SYY = 21, DFGPU_AGG_REGR_SXY = 22 };
+typedef struct dfgpu_comoments dfgpu_comoments;
+/* ≙ Covariance / CovariancePop / Correlation / Regr::create_accumulator (physical-expr/src/aggregate/covariance.rs:225-406, correlation.rs:134-246, regr.rs:228-466).
+ * Argument 0 has in_type_a and argument 1 in_type_b (REGR_*(y, x): y is argument 0); each is Int8 .. UInt64, Float32 or Float64 and is cast to Float64 on its own inside
+ * the accumulator; any other type is DFGPU_NOT_IMPLEMENTED, any other kind DFGPU_INVALID_ARGUMENT.  One state serves all twelve kinds: count UInt64 and mean, m2 of each
+ * argument and their co-moment c_ab as Float64, all zero before the first pair; COVAR_* carries no m2. */
+DFGPU_API dfgpu_status dfgpu_comoments_new(dfgpu_ctx *ctx, int32_t kind, int32_t in_type_a, int32_t in_type_b, dfgpu_comoments **out);
+DFGPU_API void dfgpu_comoments_free(dfgpu_comoments *m);   /* NULL is allowed */
+/* ≙ update_batch (covariance.rs:272-311, correlation.rs:163-183, regr.rs:265-306) per group: a row counts only when BOTH values are valid; group_ids UINT32
+ * (0xFFFFFFFF = skip); opt_filter BOOL (NULL / false rows skipped).  The state grows to total_num_groups, also when the batch has no rows (the values may be NULL then).
+ * The sums are taken in two passes instead of the reference's recurrences: results within 1e-9 relative of the reference's, which depend on the row order themselves --
+ * except that an argument that carries ONE value in every row of a group leaves that argument's m2 and the group's c_ab at exactly 0.0 over any number of batches, as in
+ * the reference, whose evaluate() branches on those zeros. */
+DFGPU_API dfgpu_status dfgpu_comoments_update_batch(dfgpu_ctx *ctx, dfgpu_comoments *m, const dfgpu_array *values_a, const dfgpu_array *values_b,
+                                                    const dfgpu_array *group_ids, const dfgpu_array *opt_filter, int64_t total_num_groups);
+/* ≙ merge_batch (covariance.rs:354-382, correlation.rs:202-216, regr.rs:359-419): states as dfgpu_comoments_state returns them for this kind, one row per group id; rows
+ * with count 0 (or a NULL in any column) are skipped; a group may appear in several rows.  Another number of columns than the kind's, a column of another type or of
+ * another length than group_ids: DFGPU_INVALID_ARGUMENT, nothing merged. */
+DFGPU_API dfgpu_status dfgpu_comoments_merge_batch(dfgpu_ctx *ctx, dfgpu_comoments *m, const dfgpu_array *const *states, int32_t nstates,
+                                                   const dfgpu_array *group_ids, const dfgpu_array *opt_filter, int64_t total_num_groups);
+/* ≙ state(), the reference's columns in the reference's order, without NULLs, count UInt64 and the rest Float64:
+ *   COVAR_*  out_states[0 .. 4) = count, mean1, mean2, algo_const                       (covariance.rs:263-270)
+ *   CORR     out_states[0 .. 6) = count, mean1, m2_1, mean2, m2_2, algo_const           (correlation.rs:152-161)
+ *   REGR_*   out_states[0 .. 6) = count, mean_x, mean_y, m2_x, m2_y, algo_const         (regr.rs:254-262; x is argument 1) */
+DFGPU_API dfgpu_status dfgpu_comoments_state(dfgpu_ctx *ctx, dfgpu_comoments *m, dfgpu_array **out_states);
+/* ≙ evaluate(): Float64.  COVAR: algo_const / count or / (count - 1), NULL when that divisor is 0 (covariance.rs:384-401).  CORR: NULL at count 0, 0.0 at count 1 and
+ * when either population stddev is 0.0, else covar / stddev1 / stddev2 (correlation.rs:218-236).  REGR_*: regr.rs:420-460 -- SLOPE, INTERCEPT and R2 are NULL at
+ * count <= 1 and when var_pop(x) (R2: or var_pop(y)) is 0.0; AVGX, AVGY, SXX, SYY, SXY are NULL at count 0; COUNT is never NULL. */
+DFGPU_API dfgpu_status dfgpu_comoments_evaluate(dfgpu_ctx *ctx, dfgpu_comoments *m, dfgpu_array **out);
+DFGPU_API int64_t dfgpu_comoments_size(const dfgpu_comoments *m);   /* bytes: the state and the per-batch scratch */
+
 /* ------------------------------------------------------------------ a13: SortExec */
 /* ≙ lexsort_to_indices (sorts/sort.rs:599) with per column SortOptions (physical-expr/src/sort_expr.rs:34-74);
  * fetch < 0 = none.  Stable (ties keep input order; the reference leaves tie order unspecified).

@@ -117,7 +117,12 @@ DFGPU_API dfgpu_status dfgpu_plan_nested_loop_join(const dfgpu_plan *left, const
  * DFGPU_AGG_VAR_SAMP / VAR_POP / STDDEV_SAMP / STDDEV_POP (6 .. 9, include/dfgpu.h; aggregate/variance.rs, stddev.rs) are accepted in every mode over Int8 .. UInt64, Float32 and
  * Float64 arguments (any other argument type: DFGPU_NOT_IMPLEMENTED when the plan is built): each has a dfgpu_moments accumulator and three state columns, name[count] UInt64,
  * name[mean] Float64, name[m2] Float64 (variance.rs:86-100).  An AggregateExec that holds one of these, a COUNT(DISTINCT) or a string MIN / MAX takes none of the fused,
- * pre-aggregated, spilling or early-emitting paths; with an ordered input mode its groups leave at the end of the input.  Under grouping sets they are DFGPU_NOT_IMPLEMENTED. */
+ * pre-aggregated, spilling or early-emitting paths; with an ordered input mode its groups leave at the end of the input.  Under grouping sets they are DFGPU_NOT_IMPLEMENTED.
+ * DFGPU_AGG_COVAR_SAMP / COVAR_POP / CORR / REGR_SLOPE .. REGR_SXY (11 .. 22, include/dfgpu.h; aggregate/covariance.rs, correlation.rs, regr.rs) take TWO arguments: the first goes
+ * through dfgpu_plan_aggregate like any other, the second is attached with dfgpu_plan_aggregate_second_arg (below); REGR_*(y, x): y is the first.  Each argument is Int8 .. UInt64,
+ * Float32 or Float64, on its own.  Each aggregate has a dfgpu_comoments accumulator and the reference's state columns, UInt64 count and Float64 otherwise: COVAR name[count],
+ * name[mean1], name[mean2], name[algo_const]; CORR name[count], name[mean1], name[m2_1], name[mean2], name[m2_2], name[algo_const]; REGR name[count], name[mean_x], name[mean_y],
+ * name[m2_x], name[m2_y], name[algo_const].  They take the route of the VAR / STDDEV kinds through the operator and are DFGPU_NOT_IMPLEMENTED under grouping sets. */
 enum { DFGPU_AGG_COUNT_DISTINCT = 5 };
 /* AggregateExec::try_new(mode, group_by, aggr_expr, input): mode 0 Partial, 1 Final, 2 FinalPartitioned, 3 Single,
  * 4 SinglePartitioned.  Aggregate i: kind DFGPU_AGG_*, argument expr (NULL = COUNT(*)), optional FILTER expr, output name,
@@ -133,6 +138,11 @@ DFGPU_API dfgpu_status dfgpu_plan_aggregate(int32_t mode, const dfgpu_expr *cons
  * that can receive no more rows leave as an output batch (EmitTo::First(n), row_hash.rs:455-461): all but the last group (Sorted) / all groups in front of the latest sort
  * prefix (PartiallySorted); the group table holds only the open groups.  The concatenated output is the same as in Linear mode. */
 DFGPU_API dfgpu_status dfgpu_plan_aggregate_input_order(dfgpu_plan *aggregate, int32_t input_order_mode, const int32_t *order_indices, int32_t n);
+/* The second argument of aggregate agg_index, a two-argument kind (DFGPU_AGG_COVAR_SAMP .. DFGPU_AGG_REGR_SXY): its expression (NULL is allowed in the Final modes, which
+ * evaluate no argument) and its data type (type, precision, scale).  Call before the plan first executes: a two-argument aggregate that reaches execution without it is
+ * DFGPU_INVALID_ARGUMENT, and so is a second argument for a one-argument kind.  A type other than Int8 .. UInt64, Float32, Float64: DFGPU_NOT_IMPLEMENTED.  Copies of the
+ * plan (dfgpu_plan_with_fresh_state) carry it. */
+DFGPU_API dfgpu_status dfgpu_plan_aggregate_second_arg(dfgpu_plan *aggregate, int32_t agg_index, const dfgpu_expr *arg, const int32_t *arg_type /* 3 */);
 DFGPU_API dfgpu_status dfgpu_plan_aggregate_grouping_sets(dfgpu_plan *aggregate, const dfgpu_expr *const *null_exprs, int32_t nkeys, const uint8_t *groups, int32_t nsets);
 /* SortExec::new(expr, input).with_fetch(fetch).with_preserve_partitioning(..); fetch < 0 = none */
 DFGPU_API dfgpu_status dfgpu_plan_sort(const dfgpu_expr *const *exprs, const uint8_t *descending, const uint8_t *nulls_first, int32_t n, int64_t fetch,

@@ -8,7 +8,7 @@ use arrow::ffi::{from_ffi, to_ffi, FFI_ArrowArray, FFI_ArrowSchema};
 use datafusion_common::{DataFusionError, Result};
 
 macro_rules! opaque { ($($n:ident),*) => { $(#[repr(C)] pub struct $n { _p: [u8; 0] })* } }
-opaque!(dfgpu_ctx, dfgpu_array, dfgpu_expr, dfgpu_plan, dfgpu_batch, dfgpu_stream, dfgpu_comm, dfgpu_parquet, dfgpu_join_table);
+opaque!(dfgpu_ctx, dfgpu_array, dfgpu_expr, dfgpu_plan, dfgpu_batch, dfgpu_stream, dfgpu_comm, dfgpu_parquet, dfgpu_join_table, dfgpu_moments, dfgpu_comoments);
 
 /// dfgpu_comm_vtable (include/dfgpu.h): a transport the host provides instead of RCCL
 #[repr(C)]
@@ -27,6 +27,13 @@ pub const DFGPU_TIMESTAMP_SECOND: i32 = 16; pub const DFGPU_TIMESTAMP_MILLISECON
 pub const DFGPU_FN_DATE_TRUNC: i32 = 7;
 // DFGPU_AGG_*
 pub const AGG_SUM: i32 = 0; pub const AGG_AVG: i32 = 1; pub const AGG_COUNT: i32 = 2; pub const AGG_MIN: i32 = 3; pub const AGG_MAX: i32 = 4;
+pub const AGG_COUNT_DISTINCT: i32 = 5;      // plan layer only (include/dfgpu_exec.h)
+// dfgpu_moments_*: Variance / VariancePop / Stddev / StddevPop
+pub const AGG_VAR_SAMP: i32 = 6; pub const AGG_VAR_POP: i32 = 7; pub const AGG_STDDEV_SAMP: i32 = 8; pub const AGG_STDDEV_POP: i32 = 9;
+// dfgpu_comoments_*: Covariance / CovariancePop / Correlation / Regr(RegrType::*), two arguments each (10 is unassigned)
+pub const AGG_COVAR_SAMP: i32 = 11; pub const AGG_COVAR_POP: i32 = 12; pub const AGG_CORR: i32 = 13; pub const AGG_REGR_SLOPE: i32 = 14; pub const AGG_REGR_INTERCEPT: i32 = 15;
+pub const AGG_REGR_COUNT: i32 = 16; pub const AGG_REGR_R2: i32 = 17; pub const AGG_REGR_AVGX: i32 = 18; pub const AGG_REGR_AVGY: i32 = 19; pub const AGG_REGR_SXX: i32 = 20;
+pub const AGG_REGR_SYY: i32 = 21; pub const AGG_REGR_SXY: i32 = 22;
 
 extern "C" {
     // ---- include/dfgpu.h
@@ -51,6 +58,23 @@ extern "C" {
     pub fn dfgpu_parquet_num_row_groups(file: *const dfgpu_parquet) -> i32;
     pub fn dfgpu_parquet_column_stats(file: *const dfgpu_parquet, row_group: i32, column: i32, min_value: *mut i64, max_value: *mut i64, null_count: *mut i64, has_min_max: *mut i32) -> i32;
     pub fn dfgpu_parquet_read(ctx: *mut dfgpu_ctx, file: *mut dfgpu_parquet, first_row_group: i32, num_row_groups: i32, columns: *const i32, ncols: i32, out: *mut *mut dfgpu_array) -> i32;
+    // ---- a9 (include/dfgpu.h): the accumulator types beside dfgpu_acc.  VAR / STDDEV: one argument, state (count, mean, m2)
+    pub fn dfgpu_moments_new(ctx: *mut dfgpu_ctx, kind: i32, in_type: i32, out: *mut *mut dfgpu_moments) -> i32;
+    pub fn dfgpu_moments_free(m: *mut dfgpu_moments);
+    pub fn dfgpu_moments_update_batch(ctx: *mut dfgpu_ctx, m: *mut dfgpu_moments, values: *const dfgpu_array, group_ids: *const dfgpu_array, opt_filter: *const dfgpu_array, total_num_groups: i64) -> i32;
+    pub fn dfgpu_moments_merge_batch(ctx: *mut dfgpu_ctx, m: *mut dfgpu_moments, states: *const *const dfgpu_array, nstates: i32, group_ids: *const dfgpu_array, opt_filter: *const dfgpu_array, total_num_groups: i64) -> i32;
+    pub fn dfgpu_moments_state(ctx: *mut dfgpu_ctx, m: *mut dfgpu_moments, out_states: *mut *mut dfgpu_array /* 3 */) -> i32;
+    pub fn dfgpu_moments_evaluate(ctx: *mut dfgpu_ctx, m: *mut dfgpu_moments, out: *mut *mut dfgpu_array) -> i32;
+    pub fn dfgpu_moments_size(m: *const dfgpu_moments) -> i64;
+    // COVAR / CORR / REGR_*: two arguments (REGR_*(y, x): y is values_a), the reference's state columns: 4 for COVAR, 6 for CORR and REGR
+    pub fn dfgpu_comoments_new(ctx: *mut dfgpu_ctx, kind: i32, in_type_a: i32, in_type_b: i32, out: *mut *mut dfgpu_comoments) -> i32;
+    pub fn dfgpu_comoments_free(m: *mut dfgpu_comoments);
+    pub fn dfgpu_comoments_update_batch(ctx: *mut dfgpu_ctx, m: *mut dfgpu_comoments, values_a: *const dfgpu_array, values_b: *const dfgpu_array, group_ids: *const dfgpu_array, opt_filter: *const dfgpu_array,
+                                        total_num_groups: i64) -> i32;
+    pub fn dfgpu_comoments_merge_batch(ctx: *mut dfgpu_ctx, m: *mut dfgpu_comoments, states: *const *const dfgpu_array, nstates: i32, group_ids: *const dfgpu_array, opt_filter: *const dfgpu_array, total_num_groups: i64) -> i32;
+    pub fn dfgpu_comoments_state(ctx: *mut dfgpu_ctx, m: *mut dfgpu_comoments, out_states: *mut *mut dfgpu_array /* 4 or 6 */) -> i32;
+    pub fn dfgpu_comoments_evaluate(ctx: *mut dfgpu_ctx, m: *mut dfgpu_comoments, out: *mut *mut dfgpu_array) -> i32;
+    pub fn dfgpu_comoments_size(m: *const dfgpu_comoments) -> i64;
     // ---- include/dfgpu_exec.h
     pub fn dfgpu_sort_to_indices_keys(ctx: *mut dfgpu_ctx, cols: *const *const dfgpu_array, descending: *const u8, nulls_first: *const u8, k: i32, fetch: i64, out: *mut *mut dfgpu_array, out_sorted: *mut *mut dfgpu_array) -> i32;
     /// Partial stage inside the operator; flags: 1 = DFGPU_PREAGG_ANY_ORDER (set below a SortExec over all group columns); value_casts[i] = DFGPU_FLOAT64: argument i is CAST(values[i] AS DOUBLE).
@@ -58,6 +82,8 @@ extern "C" {
                                         opt_mask: *const dfgpu_array, flags: i32, out_keys: *mut *mut dfgpu_array, out_states: *mut *mut dfgpu_array) -> i32;
     pub fn dfgpu_csv_read(ctx: *mut dfgpu_ctx, bytes: *const u8, len: i64, bytes_on_device: i32, delimiter: i32, quote: i32, escape: i32, has_header: i32, ncols_file: i32, columns: *const i32, types: *const i32, ncols: i32, out: *mut *mut dfgpu_array, out_rows: *mut i64) -> i32;
     pub fn dfgpu_plan_aggregate_input_order(aggregate: *mut dfgpu_plan, input_order_mode: i32, order_indices: *const i32, n: i32) -> i32;
+    /// the second entry of AggregateExpr::expressions() of Covariance / Correlation / Regr; arg_type = (type, precision, scale).  Before the plan first executes.
+    pub fn dfgpu_plan_aggregate_second_arg(aggregate: *mut dfgpu_plan, agg_index: i32, arg: *const dfgpu_expr, arg_type: *const i32) -> i32;
     pub fn dfgpu_plan_parquet(file: *mut dfgpu_parquet, columns: *const i32, ncols: i32, npartitions: i32, row_groups_per_batch: i32, out: *mut *mut dfgpu_plan) -> i32;
     pub fn dfgpu_plan_csv(bytes: *const u8, len: i64, delimiter: i32, quote: i32, escape: i32, has_header: i32, names: *const *const c_char, types: *const i32, ncols_file: i32, columns: *const i32, ncols: i32, npartitions: i32, batch_bytes: i64, out: *mut *mut dfgpu_plan) -> i32;
     pub fn dfgpu_plan_parquet_prune(parquet_exec: *mut dfgpu_plan, column: i32, min_value: i64, max_value: i64) -> i32;
